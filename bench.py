@@ -16,13 +16,19 @@ fused Adam -- all through the C ABI (include/jrr.h) on device-resident synthetic
 N > 1 is weak scaling: every rank owns 4096 poses (global batch 4096*N), the MSE means are
 normalised by the GLOBAL batch, and the shared J_regressor is stepped every --j_step_every inner
 iterations (reference cadence 100, scripts/optimize.py:300-312) with ONE RCCL all-reduce on its
-gradient.  A timed region is EXACTLY --steps iterations between barrier + synchronize pairs; it is
-repeated until >= ~3 s of device time has been timed and the MEDIAN region is reported (every
-region's time is listed under `repeat_ms_per_step`).  Reported separately, never part of `value`:
-`cadence1` (J step + all-reduce after EVERY iteration: BASELINE configs[3] "each step"), the
-pose-discriminator update, the folded-regressor mode, BASELINE configs[4] (`config5`), the CPU baseline.
+gradient.  After --warmup iterations (and one untimed stretch of at most 100 iterations that ends in
+a J step), EXACTLY --steps iterations are timed in one region between barrier + synchronize pairs;
+`value` and `ms_per_step` come from that region alone.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`.
+A plain run does nothing else: it prints ONE JSON line on rank 0 (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the configuration, the collective's evidence, the
+library's provenance).  `--dump-outputs DIR` writes what the timed iterations computed (poses,
+shapes, per-pose errors, Adam state, the regressor) as DIR/<name>.npy after the timed region.
+`--full` adds everything else, never part of `value`: the same region repeated until >= ~3 s have
+been timed (`config.repeated_regions`), `roofline` and per-kernel times, `cadence1` (J step +
+all-reduce after EVERY iteration: BASELINE configs[3] "each step"), the pose-discriminator update,
+the folded-regressor mode, BASELINE configs[1] / [4] (`config2`, `config5`), the other bodies, the
+driver per outer batch, and the CPU baseline.
 """
 import argparse
 import importlib
@@ -31,6 +37,7 @@ import os
 import statistics
 import sys
 import time
+import types
 
 import numpy as np
 import torch
@@ -99,7 +106,14 @@ def parse():
     ap.add_argument('--j_step_every', type=int, default=100,
                     help='inner iterations per J_regressor step (reference: 100); the timed region always contains at least '
                          'one J step with its all-reduce: the effective cadence is min(j_step_every, steps)')
-    ap.add_argument('--min_timed_ms', type=float, default=3000.0, help='repeat the K-step timed region until this much is timed')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every measurement beside the headline (repeated regions, roofline and per-kernel times, cadence-1, '
+                         'outer step, side modes, other configurations and bodies, the driver, the CPU baseline); the --no_* '
+                         'options below and --min_timed_ms / --max_repeats / --cpu_* apply to it')
+    ap.add_argument('--dump-outputs', dest='dump_outputs', metavar='DIR', default=None,
+                    help='after the timed region, write what the timed iterations computed as DIR/<name>.npy (float32 / float64, '
+                         '<= 64 MB in all: a fixed, seeded sample of poses when the batch is larger)')
+    ap.add_argument('--min_timed_ms', type=float, default=3000.0, help='--full: repeat the K-step timed region until this much is timed')
     ap.add_argument('--max_repeats', type=int, default=150)
     ap.add_argument('--no_cpu_baseline', action='store_true')
     ap.add_argument('--cpu_batch', type=int, default=1024, help='cpu_baseline sample batch (scaled to batch-4096 units)')
@@ -260,6 +274,31 @@ def self_launch(a):
         print(json_lines[-1])
     sys.stdout.flush()
     sys.exit(r.returncode if r.returncode != 0 or json_lines else 1)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, per_pose, shared, limit=DUMP_LIMIT_BYTES):
+    """write the arrays of the timed path as DIR/<name>.npy: `per_pose` (first axis = poses) and `shared` (everything else), all
+    float32 / float64.  When together they exceed `limit` bytes, the per-pose arrays keep a fixed, seeded sample of poses (the same
+    rows in every array, `pose_index.npy` lists them).  Returns {name: shape} of what was written."""
+    n = next(iter(per_pose.values())).shape[0]
+    fixed = sum(v.nbytes for v in shared.values())
+    row = sum(v.nbytes // max(1, v.shape[0]) for v in per_pose.values())
+    keep = min(n, max(1, (limit - fixed - 8 * n) // max(1, row + 8)))
+    arrays = dict(shared)
+    if keep < n:
+        idx = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        arrays.update({k: v[idx] for k, v in per_pose.items()})
+        arrays['pose_index'] = idx.astype(np.float64)
+    else:
+        arrays.update(per_pose)
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(os.path.join(dirname, name + '.npy'), v)
+    return {name: list(v.shape) for name, v in arrays.items()}
 
 
 def block_folded(c):
@@ -469,10 +508,49 @@ def block_driver(c, support_tiles):
 
 
 def build_line(c):
-    """the JSON line of rank 0 from the measurements of main() (c: its locals): headline, roofline of the dominant kernel and of the whole
-    step, per-kernel times, cadence-1 blocks, outer-step rates, and the separately reported blocks"""
+    """the JSON line of rank 0 from the measurements of main() (c: its locals): headline; under --full also the repeated regions, roofline
+    of the dominant kernel and of the whole step, per-kernel times, cadence-1 blocks, outer-step rates, and the separately reported blocks"""
     ms_per_step = c.elapsed / c.a.steps * 1e3
     it_s = c.a.steps / c.elapsed
+    out = {
+        # BASELINE.json's metric string.  --scaling weak (default): batch = poses per GPU, `value` = N x iterations/s of 4096-pose batches;
+        # --scaling strong: batch = the global batch, sharded N ways, `value` = iterations/s of that one batch
+        'metric': 'pose-refinement iters/sec, batch 4096, at 1/2/4/8 MI355X',
+        'value': round(it_s * c.agg, 3), 'unit': f'it/s (x{c.UB} poses)', 'n_gpus': c.world, 'steps': c.a.steps, 'warmup': c.a.warmup,
+        'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': c.a.scaling, 'vs_baseline': None,
+        'dtype': 'f32', 'data': 'synthetic', 'full': bool(c.a.full),
+        'config': {'workload': f'BASELINE configs[{c.a.config - 1}]: batch={c.B}/GPU inner loop, 3D-joint loss'
+                               + (' + pose-discriminator adversarial term' if c.use_disc else '')
+                               + (' + soft-silhouette loss (224x224 rasteriser)' if c.use_sil else ''),
+                   'global_batch': c.B * c.world, 'poses_per_gpu': c.B, 'poses_per_sec': round(it_s * c.world * c.B, 1),
+                   'j_step_every': c.cadence, 'j_steps_in_timed_regions': c.nj_region, 'parallelism': f'dp{c.world}', 'joint_loss_last': c.loss_joint,
+                   'timed_regions': 1, 'timed_steps': c.a.steps,
+                   'value_is': 'timed steps / timed seconds of ONE region of exactly --steps iterations (the J step follows every '
+                               'j_step_every-th of them, counted from the first timed iteration: the reference cadence)',
+                   'host_calls_per_region': 'one C call (jrr_refine_run_j_steps)' if c.dist is None else 'refine_run + j_regressor_grad + all_reduce + j_step_apply per J step',
+                   'forward_reuse_after_j_step': False,
+                   'vertex_tiles': 'all 216 (every iteration skins all 6890 vertices; the iteration restricted to the tiles of the '
+                                   'regressor\'s support -- what optimize.py runs by default -- is the separate block `support_tiles` of --full)',
+                   'geometry': dict(c.eng.info, **c.dmodel.info)},
+        'collective': c.collective,
+        'provenance': c.prov,
+        'per_rank_ms_per_step': {'min': round(min(c.per_rank_ms), 4), 'median': round(statistics.median(c.per_rank_ms), 4), 'max': round(max(c.per_rank_ms), 4),
+                                 'each': [round(x, 4) for x in c.per_rank_ms],
+                                 'note': 'every rank\'s own time per step over the headline region (before the closing barrier); `ms_per_step` is the max over ranks incl. barriers'},
+    }
+    if c.dumped is not None:
+        out['outputs'] = c.dumped
+    if not c.a.full:
+        return out
+    nreg = len(c.regions)
+    out['config']['repeated_regions'] = {
+        'value': round(c.a.steps * nreg / sum(c.regions) * c.agg, 3), 'ms_per_step': round(sum(c.regions) / nreg / c.a.steps * 1e3, 4),
+        'timed_regions': nreg, 'timed_steps': nreg * c.a.steps, 'j_steps_in_timed_regions': sum(c.region_nj),
+        'median_region_ms_per_step': round(statistics.median(c.regions) / c.a.steps * 1e3, 4),
+        'j_steps_per_region': c.region_nj if len(set(c.region_nj)) > 1 else c.region_nj[0],
+        'repeat_ms_per_step': [round(r / c.a.steps * 1e3, 4) for r in c.regions],
+        'value_is': 'the headline region and its repeats until --min_timed_ms is timed, in whole cadences: all timed steps / all timed '
+                    'seconds (the J step follows every j_step_every-th iteration, counted across regions); not `value`'}
     dom_ms, dom_n = c.prof['k_lbs_fwd']
     kjs = int(c.eng.info.get('joint_sparse') or 0)      # joint slots per vertex tile and pass the LBS kernels multiply by (0: all 24)
     sparse = kjs > 0
@@ -501,34 +579,7 @@ def build_line(c):
     step_flop = flop_fwd + flop_bwd + FLOP_BLEND_ADJ_PER_POSE + (FLOP_DISC_PER_POSE if c.use_disc else 0)
     step_flop_dense = FLOP_LBS_FWD_PER_POSE + FLOP_LBS_BWD_PER_POSE + FLOP_BLEND_ADJ_PER_POSE + (FLOP_DISC_PER_POSE if c.use_disc else 0)
     c1_ms = c.c1_el / c.a.steps * 1e3
-    out = {
-        # BASELINE.json's metric string.  --scaling weak (default): batch = poses per GPU, `value` = N x iterations/s of 4096-pose batches;
-        # --scaling strong: batch = the global batch, sharded N ways, `value` = iterations/s of that one batch
-        'metric': 'pose-refinement iters/sec, batch 4096, at 1/2/4/8 MI355X',
-        'value': round(it_s * c.agg, 3), 'unit': f'it/s (x{c.UB} poses)', 'n_gpus': c.world, 'steps': c.a.steps, 'warmup': c.a.warmup,
-        'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': c.a.scaling, 'vs_baseline': None,
-        'dtype': 'f32', 'data': 'synthetic',
-        'config': {'workload': f'BASELINE configs[{c.a.config - 1}]: batch={c.B}/GPU inner loop, 3D-joint loss'
-                               + (' + pose-discriminator adversarial term' if c.use_disc else '')
-                               + (' + soft-silhouette loss (224x224 rasteriser)' if c.use_sil else ''),
-                   'global_batch': c.B * c.world, 'poses_per_gpu': c.B, 'poses_per_sec': round(it_s * c.world * c.B, 1),
-                   'j_step_every': c.cadence, 'j_steps_in_timed_regions': c.nj_region, 'parallelism': f'dp{c.world}', 'joint_loss_last': c.loss_joint,
-                   'timed_regions': len(c.regions), 'timed_steps': len(c.regions) * c.a.steps,
-                   'value_is': 'all timed regions: timed steps / timed seconds (the J step follows every j_step_every-th iteration, counted '
-                               'across regions: the reference cadence, not one J step per region)',
-                   'median_region_ms_per_step': round(statistics.median(c.regions) / c.a.steps * 1e3, 4),
-                   'j_steps_per_region': c.region_nj if len(set(c.region_nj)) > 1 else c.region_nj[0],
-                   'repeat_ms_per_step': [round(r / c.a.steps * 1e3, 4) for r in c.regions],
-                   'host_calls_per_region': 'one C call (jrr_refine_run_j_steps)' if c.dist is None else 'refine_run + j_regressor_grad + all_reduce + j_step_apply per J step',
-                   'forward_reuse_after_j_step': False,
-                   'vertex_tiles': 'all 216 (every iteration skins all 6890 vertices; the iteration restricted to the tiles of the '
-                                   'regressor\'s support -- what optimize.py runs by default -- is the separate block `support_tiles`)',
-                   'geometry': dict(c.eng.info, **c.dmodel.info)},
-        'collective': c.collective,
-        'provenance': c.prov,
-        'per_rank_ms_per_step': {'min': round(min(c.per_rank_ms), 4), 'median': round(statistics.median(c.per_rank_ms), 4), 'max': round(max(c.per_rank_ms), 4),
-                                 'each': [round(x, 4) for x in c.per_rank_ms],
-                                 'note': 'every rank\'s own time per step over the headline regions (before the closing barrier); `ms_per_step` is the max over ranks incl. barriers'},
+    out.update({
         'roofline': {'bound': 'mfma', 'kernel': 'k_lbs_fwd<true,false>', 'achieved': round(achieved, 2),
                      'peak': PEAK_F32_MFMA_TFLOPS, 'unit': 'TFLOP/s', 'frac': round(achieved / PEAK_F32_MFMA_TFLOPS, 4),
                      'traffic': traffic,
@@ -587,7 +638,7 @@ def build_line(c):
                      'note': 'BASELINE configs[3] / north_star "all-reduce on the J_regressor gradient each step": '
                              'the J step (+ its all-reduce) after EVERY inner iteration, timed like `value`; the iteration after a J '
                              'step re-regresses its joints from the J step\'s stored vertices (same poses: explicit reuse)'},
-    }
+    })
     if c.c1h_el is not None:
         out['cadence1_host_driven'] = {
             'value': round(c.a.steps / c.c1h_el, 3), 'unit': f'it/s (x{c.B} poses)', 'ms_per_step': round(c.c1h_el / c.a.steps * 1e3, 4),
@@ -804,29 +855,53 @@ def main():
     cadence = max(1, a.j_step_every)   # the reference's: one J step (SMPL fwd, dJ, RCCL all-reduce, Adam) per 100 inner iterations
     run(a.warmup, cadence)
     j_step()                       # untimed: the first J step zero-fills the padded vertex buffer
+    pre = min(cadence, 100)
+    it_count[0] = cadence - pre
+    timed_region(pre, cadence)     # untimed: <= 100 iterations that end in a J step (loads the code objects of the J step path)
     it_count[0] = 0
-    timed_region(max(a.steps, cadence), cadence)  # untimed: loads the code objects of the J step path (holds >= 1 J step)
-    it_count[0] = 0
-    regions, region_nj = [], []
     del own_times[:]
-    el, nj0 = timed_region(a.steps, cadence)
-    regions.append(el); region_nj.append(nj0)
-    # whole cadences: the timed regions together hold the reference's share of J steps exactly (1 per `cadence` iterations)
-    reps = repeats_for(el)
-    per_cad = max(1, cadence // np.gcd(cadence, a.steps))          # regions per whole number of cadences
-    reps = min(a.max_repeats, (reps + per_cad - 1) // per_cad * per_cad)
-    for _ in range(reps - 1):
-        el, njr = timed_region(a.steps, cadence)
-        regions.append(el); region_nj.append(njr)
-    # `value`: every timed step over every timed second (the J steps amortised at the reference cadence)
-    elapsed = sum(regions) / len(regions)
-    nj_region = sum(region_nj)
-    own_ms = sum(own_times) / len(own_times) / a.steps * 1e3     # this rank alone, mean over the headline's regions
+    # `value` / `ms_per_step`: EXACTLY --steps iterations in ONE timed region (the J steps at the reference cadence)
+    elapsed, nj_region = timed_region(a.steps, cadence)
+    own_ms = own_times[0] / a.steps * 1e3          # this rank alone, the headline region
     per_rank_ms = [own_ms]
     if dist is not None:
         per_rank_ms = [None] * world
         dist.all_gather_object(per_rank_ms, own_ms)
     loss_joint = float(sq.sum().item()) / (B * 51)
+
+    # ---- --dump-outputs: what the timed iterations computed, as their caller receives it (every rank's poses, rank order) ----
+    dumped = None
+    if a.dump_outputs:
+        per_pose = {'pose6d': x6d, 'betas': betas, 'sqerr': sq, 'adam_m': m, 'adam_v': v}
+        if use_sil:
+            per_pose['camera'] = sil_refs[1]
+        per_pose = {k: t.detach().cpu().numpy() for k, t in per_pose.items()}
+        if dist is not None:
+            shards = [None] * world
+            dist.all_gather_object(shards, per_pose)
+            per_pose = {k: np.concatenate([s[k] for s in shards]) for k in per_pose}
+        if rank == 0:
+            shared = {'j_regressor': J, 'j_adam_m': Jm, 'j_adam_v': Jv}
+            shared = {k: t.detach().cpu().numpy() for k, t in shared.items()}
+            shared.update({'adam_step': step.cpu().numpy().astype(np.float64), 'j_adam_step': Jstep.cpu().numpy().astype(np.float64)})
+            dumped = {'dir': a.dump_outputs, 'arrays': dump_outputs(a.dump_outputs, per_pose, shared)}
+
+    if not a.full:                 # a plain run: the headline line and nothing else
+        if rank == 0:
+            print(json.dumps(build_line(types.SimpleNamespace(**locals()))))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: the headline region repeated in whole cadences, so that the regions together hold the reference's share of J steps
+    #      exactly (1 per `cadence` iterations), until --min_timed_ms is timed (`config.repeated_regions`, never `value`) ----
+    regions, region_nj = [elapsed], [nj_region]
+    reps = repeats_for(elapsed)
+    per_cad = max(1, cadence // np.gcd(cadence, a.steps))          # regions per whole number of cadences
+    reps = min(a.max_repeats, (reps + per_cad - 1) // per_cad * per_cad)
+    for _ in range(reps - 1):
+        el, njr = timed_region(a.steps, cadence)
+        regions.append(el); region_nj.append(njr)
 
     # ---- BASELINE configs[3] "all-reduce on the J_regressor gradient EACH step": J step after every iteration,
     #      timed like `value` (median of >= 5 regions) ----
@@ -1085,7 +1160,6 @@ def main():
         return out_
 
     # ---- the separately reported blocks (one function each, above main()): never part of `value` ----
-    import types
     c = types.SimpleNamespace(a=a, dev=dev, world=world, dist=dist, B=B, use_disc=use_disc, use_sil=use_sil, eng_mod=eng_mod, sm=sm, dmodel=dmodel,
                               model_np=model_np, J_np=J_np, batch_np=batch_np, side_run=side_run, silhouette_setup=silhouette_setup, prof=prof,
                               inner_ms=inner_ms, d_ms=d_ms, j_ms=j_ms, strong=strong, agg=agg)

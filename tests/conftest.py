@@ -65,23 +65,29 @@ def pytest_collection_finish(session):
         'w2s': _torchrun(2, 29551, [worker, os.path.join(tmp, 'w2s')] + SIL_FLAGS + ['--dist_backend', 'gloo', '--single_device']),
         # bench.py --gpus 2 WITHOUT torchrun: bench.py starts its own 2-rank child (what the driver's command line does)
         'bench2': [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--j_step_every', '2', '--batch', '256',
-                   '--backend', 'gloo', '--single_device', '--no_cpu_baseline', '--no_folded', '--no_skin_variants', '--no_config5',
+                   '--backend', 'gloo', '--single_device', '--full', '--no_cpu_baseline', '--no_folded', '--no_skin_variants', '--no_config5',
                    '--min_timed_ms', '50'],
         # ... and at the node's world size
         'bench8': [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '4', '--warmup', '1', '--j_step_every', '2', '--batch', '128',
-                   '--backend', 'gloo', '--single_device', '--no_cpu_baseline', '--no_folded', '--no_skin_variants', '--no_config5',
+                   '--backend', 'gloo', '--single_device', '--full', '--no_cpu_baseline', '--no_folded', '--no_skin_variants', '--no_config5',
                    '--min_timed_ms', '50'],
         # --scaling strong: the GLOBAL batch fixed (512), shards of 256 / 64 poses
         'bench2s': [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--j_step_every', '2', '--batch', '512',
-                    '--scaling', 'strong', '--backend', 'gloo', '--single_device', '--no_cpu_baseline', '--no_folded', '--no_skin_variants', '--no_config5',
+                    '--scaling', 'strong', '--backend', 'gloo', '--single_device', '--full', '--no_cpu_baseline', '--no_folded', '--no_skin_variants', '--no_config5',
                     '--min_timed_ms', '50'],
         'bench8s': [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '8', '--steps', '4', '--warmup', '1', '--j_step_every', '2', '--batch', '512',
-                    '--scaling', 'strong', '--backend', 'gloo', '--single_device', '--no_cpu_baseline', '--no_folded', '--no_skin_variants', '--no_config5',
+                    '--scaling', 'strong', '--backend', 'gloo', '--single_device', '--full', '--no_cpu_baseline', '--no_folded', '--no_skin_variants', '--no_config5',
                     '--min_timed_ms', '50'],
         # the same under an explicit torchrun (the README's / the contract's N > 1 command line)
         'bench2t': _torchrun(2, 29542, [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--j_step_every', '2', '--batch', '256',
-                                        '--backend', 'gloo', '--single_device', '--no_cpu_baseline', '--no_folded',
+                                        '--backend', 'gloo', '--single_device', '--full', '--no_cpu_baseline', '--no_folded',
                                         '--no_skin_variants', '--no_config5', '--min_timed_ms', '50']),
+        # PLAIN runs (no --full): the headline line only, exactly --steps timed iterations, and what they computed (--dump-outputs);
+        # at 2 ranks rank 0 writes every rank's poses in rank order
+        'bench1p': [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '7', '--warmup', '2', '--j_step_every', '5',
+                    '--batch', '256', '--dump-outputs', os.path.join(tmp, 'bench1p_out')],
+        'bench2p': [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '7', '--warmup', '2', '--j_step_every', '5',
+                    '--batch', '256', '--backend', 'gloo', '--single_device', '--dump-outputs', os.path.join(tmp, 'bench2p_out')],
         # the in-loop J step with the DENSE (17,6890) all-reduce payload instead of the regressor's support (default): same J
         'w2d': _torchrun(2, 29546, [worker, os.path.join(tmp, 'w2d')] + DP_FLAGS + ['--dist_backend', 'gloo', '--single_device', '--j_allreduce', 'dense']),
         'w8d': _torchrun(8, 29547, [worker, os.path.join(tmp, 'w8d')] + DP_FLAGS + ['--dist_backend', 'gloo', '--single_device', '--j_allreduce', 'dense']),
@@ -101,7 +107,7 @@ def pytest_collection_finish(session):
         # a box with two or more GPUs: the SAME runs with one rank per GPU over RCCL (backend nccl), no --single_device
         runs['w2n'] = _torchrun(2, 29545, [worker, os.path.join(tmp, 'w2n')] + DP_FLAGS[:-2] + ['--dist_backend', 'nccl'])
         runs['bench2n'] = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--j_step_every', '2', '--batch', '256',
-                           '--no_cpu_baseline', '--no_folded', '--no_skin_variants', '--no_config5', '--min_timed_ms', '50']
+                           '--full', '--no_cpu_baseline', '--no_folded', '--no_skin_variants', '--no_config5', '--min_timed_ms', '50']
     DP_RUNS['dir'] = tmp
     for name, cmd in runs.items():
         try:

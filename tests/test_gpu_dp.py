@@ -218,6 +218,7 @@ def test_bench_n_ranks(name, world, batch):
     assert j['unit'] == f"it/s (x{world * batch if strong else batch} poses)"
     assert j['provenance']['in_tree_lib'] is True and len(j['provenance']['lib_sha16']) == 16
     assert j['config']['j_steps_in_timed_regions'] >= 1
+    assert j['full'] is True and j['config']['timed_steps'] == 4 and j['config']['repeated_regions']['timed_regions'] >= 1
     assert j['j_step']['allreduce_bytes'] == 17 * 128 * 4          # the regressor's support, not the dense (17,6890) gradient
     assert np.isfinite(j['config']['joint_loss_last'])
     c = j['collective']
@@ -238,6 +239,44 @@ def test_bench_n_ranks(name, world, batch):
         assert rec['median_us_synchronised'] > 0 and rec['us_back_to_back'] > 0
     assert cc['cadence1_ms_per_step'] > 0 and cc['cadence1_noop_collective_ms_per_step'] > 0
     assert abs(cc['collective_us_per_step'] - (cc['cadence1_ms_per_step'] - cc['cadence1_noop_collective_ms_per_step']) * 1e3) < 0.2
+
+
+@pytest.mark.parametrize('name,world', [('bench1p', 1), ('bench2p', 2)])
+def test_bench_plain_run_times_exactly_steps_and_dumps_outputs(name, world):
+    """a plain `bench.py` (no --full): ONE line with the headline alone, from exactly --steps timed iterations (7 at a J step every
+    5th: one J step inside), and --dump-outputs writes what those iterations computed, float32 / float64, within 64 MB"""
+    r = _run(name)
+    lines = [l for l in r['out'].splitlines() if l.startswith('{')]
+    assert len(lines) == 1, r['out'][-2000:]
+    j = json.loads(lines[0])
+    assert j['full'] is False and j['steps'] == 7 and j['warmup'] == 2 and j['n_gpus'] == world
+    assert j['config']['timed_regions'] == 1 and j['config']['timed_steps'] == 7 and j['config']['j_steps_in_timed_regions'] == 1
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in j, k
+    assert j['dtype'] == 'f32' and j['higher_is_better'] is True and j['value'] > 0
+    assert abs(j['value'] - 1e3 / j['ms_per_step'] * world) < 1e-2 * j['value']
+    for k in ('roofline', 'kernels_ms', 'cadence1', 'outer_step', 'support_tiles', 'config5', 'cpu_baseline', 'driver_outer_batch'):
+        assert k not in j, k
+    assert 'repeated_regions' not in j['config']
+    d = os.path.join(conftest.DP_RUNS['dir'], name + '_out')
+    assert j['outputs']['dir'] == d
+    names = sorted(f[:-4] for f in os.listdir(d))
+    assert names == sorted(j['outputs']['arrays'])
+    assert {'pose6d', 'betas', 'sqerr', 'adam_m', 'adam_v', 'adam_step', 'j_regressor', 'j_adam_m', 'j_adam_v', 'j_adam_step'} <= set(names)
+    arr = {n: np.load(os.path.join(d, n + '.npy')) for n in names}
+    assert sum(a.nbytes for a in arr.values()) <= 64 << 20
+    for n, a in arr.items():
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        assert list(a.shape) == j['outputs']['arrays'][n], n
+    B = 256 * world
+    assert arr['pose6d'].shape == (B, 24, 6) and arr['betas'].shape == (B, 10) and arr['sqerr'].shape == (B,)
+    assert arr['j_regressor'].shape == (17, 6890)
+    # Adam steps: warm-up (2) + the untimed stretch that ends in a J step (min(j_step_every, 100) = 5) + the timed steps (7);
+    # J steps: the one after the warm-up, the untimed stretch's, the timed region's
+    assert arr['adam_step'][0] == 2 + 5 + 7 and arr['j_adam_step'][0] == 3
+    assert (arr['sqerr'] > 0).all()
+    if world == 2:       # the ranks' own seeded batches, in rank order
+        assert not np.allclose(arr['pose6d'][:256], arr['pose6d'][256:])
 
 
 def test_bench_rejects_a_world_that_contradicts_gpus():

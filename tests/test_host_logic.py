@@ -263,8 +263,44 @@ def test_bench_provenance_and_experiment_library_guard(monkeypatch):
     assert bench.provenance(True)['jrr_env']['JRR_LIB'] == lib
     # the separately reported blocks are functions of their own, and the line is assembled in one place
     for name in ('block_folded', 'block_bf16x3', 'block_support_tiles', 'block_config5', 'block_config2', 'block_skin_variants', 'block_driver',
-                 'build_line', 'cpu_baseline', 'provenance', 'self_launch'):
+                 'build_line', 'cpu_baseline', 'provenance', 'self_launch', 'dump_outputs'):
         assert callable(getattr(bench, name)), name
+
+
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """a plain `bench.py` run measures the headline only (--full is off by default); --dump-outputs writes float32 / float64 .npy files
+    within the byte limit, cutting the per-pose arrays to ONE fixed, seeded sample of poses (the same rows in every array) when needed"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_under_test', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '5', '--warmup', '2'])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (5, 2)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--dump-outputs', str(tmp_path / 'o')])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path / 'o')
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+    n = 1000
+    rows = np.arange(n, dtype=np.float32)
+    per_pose = {'pose6d': np.repeat(rows, 144).reshape(n, 24, 6), 'sqerr': rows.copy()}
+    shared = {'j_regressor': np.ones((17, 6890), np.float32), 'adam_step': np.array([3.0])}
+    small = bench.dump_outputs(str(tmp_path / 'all'), per_pose, shared)
+    assert small['pose6d'] == [n, 24, 6] and 'pose_index' not in small
+    assert np.array_equal(np.load(tmp_path / 'all' / 'pose6d.npy'), per_pose['pose6d'])
+    limit = 17 * 6890 * 4 + 8 + 300 * (145 * 4 + 8)
+    cut = [bench.dump_outputs(str(tmp_path / d), per_pose, shared, limit=limit) for d in ('s1', 's2')]
+    assert cut[0] == cut[1] and 0 < cut[0]['pose6d'][0] < n
+    total = 0
+    for name in cut[0]:
+        x1, x2 = np.load(tmp_path / 's1' / f'{name}.npy'), np.load(tmp_path / 's2' / f'{name}.npy')
+        assert x1.dtype in (np.float32, np.float64) and np.array_equal(x1, x2), name
+        total += x1.nbytes
+    assert total <= limit
+    idx = np.load(tmp_path / 's1' / 'pose_index.npy')
+    assert np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / 's1' / 'sqerr.npy'), idx.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / 's1' / 'pose6d.npy')[:, 3, 2], idx.astype(np.float32))
 
 
 @pytest.mark.parametrize('protocol', [0, 2])

@@ -3,7 +3,7 @@
 # one short bench per environment SETTING (each argument is a space-separated list of assignments; "-" = none), two rounds interleaved
 TAG=$1; BF=$2; shift; shift
 mkdir -p gpurun_out/$TAG
-FLAGS="--no_cpu_baseline --no_folded --no_config5 --no_skin_variants --no_config2 --no_rccl_one_rank --no_driver_blocks --min_timed_ms 1000 $BF"
+FLAGS="--full --no_cpu_baseline --no_folded --no_config5 --no_skin_variants --no_config2 --no_rccl_one_rank --no_driver_blocks --min_timed_ms 1000 $BF"
 for round in 1 2; do
   i=0
   for setting in "$@"; do

@@ -1,5 +1,5 @@
 mkdir -p gpurun_out/r5k
-F="--no_cpu_baseline --no_folded --no_config5 --no_skin_variants --no_config2 --no_rccl_one_rank --no_support_tiles --no_driver_blocks --min_timed_ms 1000 --steps 20 --warmup 5"
+F="--full --no_cpu_baseline --no_folded --no_config5 --no_skin_variants --no_config2 --no_rccl_one_rank --no_support_tiles --no_driver_blocks --min_timed_ms 1000 --steps 20 --warmup 5"
 run() { tag=$1; shift; env "$@" python bench.py $F > gpurun_out/r5k/$tag.json 2>/dev/null; python - <<PY
 import json
 j=json.load(open('gpurun_out/r5k/$tag.json')); k=j['kernels_ms']

@@ -4,7 +4,7 @@ import ctypes, os, sys
 root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, root)
 extra = sys.argv[1:]      # e.g. --batch 256
-sys.argv = ['bench.py', '--config', '5', '--steps', '3', '--warmup', '1', '--no_cpu_baseline', '--no_folded', '--no_driver_blocks', '--no_rccl_one_rank', '--min_timed_ms', '100',
+sys.argv = ['bench.py', '--full', '--config', '5', '--steps', '3', '--warmup', '1', '--no_cpu_baseline', '--no_folded', '--no_driver_blocks', '--no_rccl_one_rank', '--min_timed_ms', '100',
             '--no_skin_variants', '--no_support_tiles', '--no_config2', '--allow_experiment_lib'] + extra
 import bench
 bench.main()

@@ -25,10 +25,10 @@ if [ "$2" = variants ]; then
 fi
 bash tools/prof.sh $TAG > $OUT/prof.log 2>&1
 bash tools/prof_c5.sh ${TAG}c5 > $OUT/prof_c5.log 2>&1
-python bench.py --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err; echo "rc $?" >> $OUT/bench_steps20.err
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "rc $?" >> $OUT/bench_default.err
-python bench.py --config 2 --batch 1024 --steps 20 --warmup 5 --no_driver_blocks > $OUT/bench_config2.json 2>/dev/null
-python bench.py --config 5 --steps 20 --warmup 5 --no_driver_blocks > $OUT/bench_config5.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_steps20.json 2> $OUT/bench_steps20.err; echo "rc $?" >> $OUT/bench_steps20.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; echo "rc $?" >> $OUT/bench_default.err
+python bench.py --full --config 2 --batch 1024 --steps 20 --warmup 5 --no_driver_blocks > $OUT/bench_config2.json 2>/dev/null
+python bench.py --full --config 5 --steps 20 --warmup 5 --no_driver_blocks > $OUT/bench_config5.json 2>/dev/null
 python -m pytest tests -m gpu -q 2>&1 | tail -3 > $OUT/gpu_suite.txt
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" >> $OUT/gpu_suite.txt 2>&1
 tail -3 $OUT/prof.log; tail -2 $OUT/prof_c5.log | cut -c1-400; cat $OUT/gpu_suite.txt; tail -1 $OUT/bench_default.err

@@ -5,7 +5,7 @@ OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $OLDPWD/bench.py --config 2 --batch 1024 --steps 100 --warmup 10 --no_cpu_baseline --min_timed_ms 300 --no_folded --no_config5 --no_config2 --no_skin_variants --no_support_tiles --no_driver_blocks --no_rccl_one_rank > $OUT/trace.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $OLDPWD/bench.py --full --config 2 --batch 1024 --steps 100 --warmup 10 --no_cpu_baseline --min_timed_ms 300 --no_folded --no_config5 --no_config2 --no_skin_variants --no_support_tiles --no_driver_blocks --no_rccl_one_rank > $OUT/trace.log 2>&1
 cd $OUT
 python3 - <<'PY'
 import csv, glob

@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 ROOT=$PWD
 cd /tmp
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $OUT -o pmc -- python3 $ROOT/bench.py --config 5 --steps 3 --warmup 1 --no_cpu_baseline --no_folded --no_skin_variants --no_driver_blocks --no_rccl_one_rank --min_timed_ms 1 > $OUT/bench.log 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d $OUT -o pmc -- python3 $ROOT/bench.py --full --config 5 --steps 3 --warmup 1 --no_cpu_baseline --no_folded --no_skin_variants --no_driver_blocks --no_rccl_one_rank --min_timed_ms 1 > $OUT/bench.log 2>&1
 cd $OUT
 python3 - <<'PY'
 import csv, glob, collections, json

@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 ROOT=$PWD
 cd /tmp
-rocprofv3 --pmc $CTRS --output-format csv -d $OUT -o pmc -- python3 $ROOT/bench.py --steps 5 --warmup 2 --no_cpu_baseline --no_folded --no_config5 --min_timed_ms 1 "$@" > $OUT/bench.log 2>&1
+rocprofv3 --pmc $CTRS --output-format csv -d $OUT -o pmc -- python3 $ROOT/bench.py --full --steps 5 --warmup 2 --no_cpu_baseline --no_folded --no_config5 --min_timed_ms 1 "$@" > $OUT/bench.log 2>&1
 cd $OUT
 python3 - <<'PY'
 import csv, glob, collections

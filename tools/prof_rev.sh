@@ -7,7 +7,7 @@ TAG=${1:-rev}
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python3 $PWD/bench.py --steps 5 --warmup 2 --no_cpu_baseline --min_timed_ms 1 --no_skin_variants --no_folded --no_config2 --no_config5 --no_bf16x3 --no_rccl_one_rank --no_support_tiles --no_driver_blocks"
+CMD="python3 $PWD/bench.py --full --steps 5 --warmup 2 --no_cpu_baseline --min_timed_ms 1 --no_skin_variants --no_folded --no_config2 --no_config5 --no_bf16x3 --no_rccl_one_rank --no_support_tiles --no_driver_blocks"
 cd /tmp
 for mode in fwd_order reversed; do
   if [ $mode = reversed ]; then export JRR_BWD16_REV=1; else unset JRR_BWD16_REV; fi

@@ -3,7 +3,7 @@
 OUT=$PWD/gpurun_out/prof_small
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python3 $PWD/bench.py --steps 30 --warmup 5 --no_cpu_baseline --no_folded"
+CMD="python3 $PWD/bench.py --full --steps 30 --warmup 5 --no_cpu_baseline --no_folded"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- $CMD > $OUT/trace.log 2>&1
 python3 - <<PY

@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 ROOT=$PWD
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no_cpu_baseline --no_folded --no_config5 "$@" > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no_cpu_baseline --no_folded --no_config5 "$@" > $OUT/bench.log 2>&1
 cd $OUT
 python3 - <<'PY'
 import csv, glob
