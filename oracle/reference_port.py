@@ -407,6 +407,23 @@ def refine_poses(smpl, J_regressor, orient6d, pose6d, betas, gt_j3d_mm_centred, 
     return orient.detach(), pose.detach(), b.detach(), hist
 
 
+def inner_grad(smpl, J_regressor, x6d, betas, gt_j3d_mm_centred, disc_sd=None, shape_disc_sd=None, mask=None,
+               batch_norm: Optional[int] = None, gt_j2d=None, cam=None, sil_mask=None, faces=None):
+    """The gradient of the inner objective at a given state: one `inner_losses` evaluation (scripts/optimize.py:222-253) and
+    its backward, what `refine_poses` hands to Adam at that state.  x6d (B,24,6) = [orient | 23 body joints].
+    Returns (terms, d/dx6d (B,24,6), d/dbetas (B,10), d/dcam (B,3) or None when no term reads the camera)."""
+    x = x6d.clone().detach().requires_grad_(True)
+    b = betas.clone().detach().requires_grad_(True)
+    c = cam.clone().detach().requires_grad_(True) if (gt_j2d is not None or sil_mask is not None) else None
+    if mask is None:
+        mask = find_j_reg_mask(J_regressor)
+    loss, terms, _ = inner_losses(smpl, J_regressor.detach(), mask, x[:, :1], x[:, 1:], b, gt_j3d_mm_centred, disc_sd,
+                                  shape_disc_sd, batch_norm, 1, gt_j2d, c, sil_mask, faces)
+    loss.backward()
+    return ({k: v.detach() for k, v in terms.items()}, x.grad.detach(), b.grad.detach(),
+            c.grad.detach() if c is not None else None)
+
+
 def j_regressor_loss_and_grad(smpl, J_regressor, orient6d, pose6d, betas, gt_j3d_mm_centred,
                               mask=None, batch_norm: Optional[int] = None):
     """scripts/optimize.py:300-309: joint MSE (weight 1, no 10000 factor) of detached poses
