@@ -812,11 +812,9 @@ int launch_disc_gemm_q(const GemmArgs& g, int epi, int btr, hipStream_t s, int* 
   if (ndot) *ndot = t96 ? g.M / 96 : (g.M / 128) * 2;
   if (t96) {
     // the 96-row tile on four waves, two per (row block, column half), splitting K inside the workgroup: two waves per SIMD instead of
-    // one (round 5: the four launches 0.2685 -> 0.2646 ms); JRR_DISC_KS=1 (experiments): two waves, as in rounds 2-4
-    static const bool ks2 = [] { const char* e = getenv("JRR_DISC_KS"); return !(e && atoi(e) == 1); }();
-    dim3 grid((g.M / 96) * (g.N / 64)), block(ks2 ? 256 : 128);
-    if (epi == EPI_STORE && !btr && ks2) hipLaunchKernelGGL((k_disc_gemm<3, 1, 2, EPI_STORE, 0, 2>), grid, block, 0, s, g);
-    else if (epi == EPI_STORE && !btr) hipLaunchKernelGGL((k_disc_gemm<3, 1, 2, EPI_STORE, 0>), grid, block, 0, s, g);
+    // one (round 5, against the two-wave tile of rounds 2-4: the four launches 0.2685 -> 0.2646 ms)
+    dim3 grid((g.M / 96) * (g.N / 64)), block(256);
+    if (epi == EPI_STORE && !btr) hipLaunchKernelGGL((k_disc_gemm<3, 1, 2, EPI_STORE, 0, 2>), grid, block, 0, s, g);
     else { jrr_set_error("disc_gemm_q: 96-row tiles serve the plain store epilogue only"); return JRR_ERR_ARG; }
     return 0;
   }
@@ -853,18 +851,6 @@ int launch_disc_gemm_q(const GemmArgs& g, int epi, int btr, hipStream_t s, int* 
     return 0;
   }
   dim3 grid((g.M / 128) * (g.N / 64)), block(256);
-  // JRR_DISC_KS128=2 (experiment, round 6): the full-size 128 x 64 tile on EIGHT waves, two K halves per position like the 96-row tile
-  // (same tile, same order of the sums: bit-identical) -- four waves per SIMD instead of two
-  static const bool ks128 = [] { const char* e = getenv("JRR_DISC_KS128"); return e && e[0] == '2'; }();
-  if (ks128) {
-    dim3 block8(512);
-    if (epi == EPI_BIAS_RELU && !btr) hipLaunchKernelGGL((k_disc_gemm<2, 2, 2, EPI_BIAS_RELU, 0, 2>), grid, block8, 0, s, g);
-    else if (epi == EPI_BIAS_RELU_DOT && !btr) hipLaunchKernelGGL((k_disc_gemm<2, 2, 2, EPI_BIAS_RELU_DOT, 0, 2>), grid, block8, 0, s, g);
-    else if (epi == EPI_STORE && !btr) hipLaunchKernelGGL((k_disc_gemm<2, 2, 2, EPI_STORE, 0, 2>), grid, block8, 0, s, g);
-    else if (epi == EPI_MASK && btr == 2) hipLaunchKernelGGL((k_disc_gemm<2, 2, 2, EPI_MASK, 2, 2>), grid, block8, 0, s, g);
-    else { jrr_set_error("disc_gemm_q: unsupported epilogue %d / transform %d", epi, btr); return JRR_ERR_ARG; }
-    return 0;
-  }
   if (epi == EPI_BIAS_RELU && !btr) hipLaunchKernelGGL((k_disc_gemm<2, 2, 2, EPI_BIAS_RELU, 0>), grid, block, 0, s, g);
   else if (epi == EPI_BIAS_RELU_DOT && !btr) hipLaunchKernelGGL((k_disc_gemm<2, 2, 2, EPI_BIAS_RELU_DOT, 0>), grid, block, 0, s, g);
   else if (epi == EPI_STORE && !btr) hipLaunchKernelGGL((k_disc_gemm<2, 2, 2, EPI_STORE, 0>), grid, block, 0, s, g);

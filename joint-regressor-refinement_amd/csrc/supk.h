@@ -70,9 +70,7 @@ struct SupArgs {
   const float* conv_img; const float* x6d; const float* dH2T; float dscale; float* gx; float* dsq;
 };
 
-// stamps (nullable; experiments): phase boundaries on the 100 MHz counter, written by thread 0
-__device__ __forceinline__ void sup_body(float* __restrict__ lds, int blk, const SupArgs& a, long long* stamps = nullptr) {
-  auto stamp = [&](int i) { if (stamps && threadIdx.x == 0) stamps[i] = wall_clock64(); };
+__device__ __forceinline__ void sup_body(float* __restrict__ lds, int blk, const SupArgs& a) {
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p = tid & 31, jt = tid >> 5;               // pose column; SMPL joint / vertex slot / H36M joint of this thread
@@ -108,7 +106,6 @@ __device__ __forceinline__ void sup_body(float* __restrict__ lds, int blk, const
   float* const convL = lds + SUPL_CONV;
   if (a.conv_img) conv_stage_params(a.conv_img, convL);
   __syncthreads();
-  stamp(0);
 
   // ---- v_posed = Ds . F : wave w < 6 owns row tile w; two accumulator chains (even / odd K groups), added at the end ----
   if (wv < SUP_RT) {
@@ -141,7 +138,6 @@ __device__ __forceinline__ void sup_body(float* __restrict__ lds, int blk, const
     }
   }
   __syncthreads();
-  stamp(1);
 
   // ---- skinning: T = sum_j W[v,j] A_j over the vertex's own joints, verts = T [v_posed; 1] ----
   for (int s = jt; s < nsv; s += NJ) {
@@ -160,7 +156,6 @@ __device__ __forceinline__ void sup_body(float* __restrict__ lds, int blk, const
     for (int r = 0; r < 3; ++r) vL[(3 * s + r) * 32 + p] = fmaf(T[r * 4 + 2], vz, fmaf(T[r * 4 + 1], vy, fmaf(T[r * 4], vx, T[r * 4 + 3])));
   }
   __syncthreads();
-  stamp(2);
 
   // ---- joints (ascending vertex row), pelvis-centred squared error and its adjoint (k_joints_loss, prep.hip) ----
   float j3[3] = {0.f, 0.f, 0.f}, g3[3] = {0.f, 0.f, 0.f};
@@ -229,7 +224,6 @@ __device__ __forceinline__ void sup_body(float* __restrict__ lds, int blk, const
     for (int c = 0; c < 3; ++c) djL[(c * NH + jt) * 32 + p] = ok ? g3[c] + g2[c] : 0.f;
   }
   __syncthreads();
-  stamp(3);
 
   // ---- vertex adjoint dverts = Jn^T dj, dvp = T^T dverts (T recomputed) ----
   float* const dvL = Fq;       // [192][32]
@@ -266,7 +260,6 @@ __device__ __forceinline__ void sup_body(float* __restrict__ lds, int blk, const
     dvq[((rho >> 2) * 32 + (i & 31)) * 4 + (rho & 3)] = 0.f;
   }
   __syncthreads();
-  stamp(4);
 
   // ---- dA_j = sum_v W[v,j] dverts_v (x) [v_posed_v; 1]: one thread per (pose, joint), the joint's vertices in ascending order ----
   {
@@ -290,7 +283,6 @@ __device__ __forceinline__ void sup_body(float* __restrict__ lds, int blk, const
 #pragma unroll
     for (int e = 0; e < 12; ++e) a.dA[(size_t)(e * NJ + jt) * BP + b] = acc[e];
   }
-  stamp(5);
 
   // ---- dF = Ds^T . dvp : wave w < 7 owns feature tile w ----
   if (wv < SUP_MT) {
