@@ -165,6 +165,30 @@ int jrr_engine_set_shape_disc(jrr_engine_t* e, const float* params_dev, void* st
 int jrr_rot6d_forward(const float* x6d_dev, float* R_dev, int n, void* stream);
 int jrr_rot6d_backward(const float* x6d_dev, const float* dR_dev, float* dx6d_dev, int n, void* stream);
 
+/* ---- dataset images ------------------------------------------------
+ * find_crop, scripts/data.py:220-271 (called twice per sample at :123-127): the square crop around a bounding box through the
+ * similarity warp of scripts/perturbation_helper.py:185-210 with theta = 0, the sampling grid of scripts/sampling_helper.py:42-69
+ * and grid_sample (bilinear, zero padding, align_corners=False), for a whole batch of uint8 frames in ONE launch.
+ *   pixels_dev   uint8, interleaved RGB (H,W,3) rows; 16-byte aligned, pixels_bytes a non-zero multiple of 16
+ *   desc_dev     [batch][8] int64 per sample {byte offset, row pitch in bytes, roi_y0, roi_x0, roi_h, roi_w, frame_H, frame_W}: the
+ *                buffer holds the block [roi_y0, roi_y0 + roi_h) x [roi_x0, roi_x0 + roi_w) of a frame_H x frame_W frame (roi_w <= 1024;
+ *                the whole frame is the block (0, 0, H, W)).  The caller hands over at least the rows and columns the crops read.
+ *   bboxes_dev   [batch][4] (min_y, min_x, max_y, max_x) in the reference's 1000-unit frame convention whatever the frame's size
+ *   mean_dev / std_dev   [3] each or both NULL: (x - mean) / std per channel on the size0 crop (transforms.Normalize,
+ *                scripts/optimize.py:141-142,164)
+ *   size0 / out0_dev, size1 / out1_dev   crop sizes (multiples of 4, at most 256; size1 = 0: one crop) and their outputs
+ *                (batch,3,size,size) float32 in [0, 1]: uint8 / 255 (scripts/data.py:113) interpolated
+ *   status_dev   one int32 the CALLER zeroes and reads when it next synchronises.  Bit 0: a bilinear tap of non-zero weight inside the
+ *                frame lies outside the sample's block (nothing is read there; the value is wrong); bit 1: a descriptor does not fit
+ *                the pixel buffer (that sample reads nothing).  Never cleared by the library.
+ * A bounding box of zero size gives non-finite sampling positions and an all-zero crop (scripts/sampling_helper.py:36-38).    */
+int jrr_image_crop(const uint8_t* pixels_dev, size_t pixels_bytes, const int64_t* desc_dev, const float* bboxes_dev, int batch,
+                   const float* mean_dev, const float* std_dev, int size0, float* out0_dev, int size1, float* out1_dev,
+                   int32_t* status_dev, void* stream);
+/* mask_rcnn of scripts/data.py:117-121,130-132: masks_dev uint8 (batch,h,w) -> out_dev float32 (batch,1,h,w) = mask / 255 with
+ * the 2 x 2 corner [:2, :2] zeroed, valid_dev int32 (batch) = (mask[0, 0] != 0) read BEFORE the corner is zeroed.             */
+int jrr_mask_prepare(const uint8_t* masks_dev, int batch, int h, int w, float* out_dev, int32_t* valid_dev, void* stream);
+
 /* Axis-angle -> rotation matrix, smplx 0.1.26 lbs.batch_rodrigues: the pose2rot=True branch of the SMPL operator
  * (smplx.SMPL.forward default; the reference's wrapper inherits it, scripts/smpl.py:61-85, base class :7-9).
  * aa (n,3) -> R (n,3,3) with theta = |aa + 1e-8|, R = I + sin(theta) K + (1-cos(theta)) K^2; and its adjoint

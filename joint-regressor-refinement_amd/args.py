@@ -50,6 +50,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help='camera pre-fit (optimize.py:187-199) + 2-D joint term (optimize.py:231-233) on synthetic gt_j2d')
     parser.add_argument('--silhouette', action='store_true',
                         help='soft-silhouette term (optimize.py:234-237, x100) against synthetic masks (BASELINE configs[4])')
+    parser.add_argument('--image_masks', action='store_true',
+                        help='with --data_root and --silhouette: fit the dataset\'s own Mask-RCNN masks (data.py:115-121,130-132; 224 x 224) '
+                             'instead of synthetic ones; frames and masks go through the device image pipeline (data.crop_batch)')
     parser.add_argument('--camera_iters', type=int, default=1000, help='camera pre-fit Adam steps (optimize.py:190)')
     parser.add_argument('--save_j_regressor', type=str, default=None,
                         help='write the trained regressor in the models/retrained_J_Regressor.pt format')

@@ -884,6 +884,38 @@ extern "C" int jrr_rot6d_backward(const float* x, const float* dR, float* dx, in
   return JRR_OK;
 }
 
+/* find_crop on uint8 frames (scripts/data.py:220-271) and the mask preparation (scripts/data.py:121,130-132) */
+extern "C" int jrr_image_crop(const uint8_t* pix, size_t pix_bytes, const int64_t* desc, const float* bboxes, int batch, const float* mean,
+                              const float* stdv, int size0, float* out0, int size1, float* out1, int32_t* status, void* stream) {
+  if (!pix || !desc || !bboxes || !out0 || !status || batch < 0 || batch > 65535 || (size1 != 0 && !out1) || ((mean == nullptr) != (stdv == nullptr))) {
+    jrr_set_error("jrr_image_crop: bad argument");
+    return JRR_ERR_ARG;
+  }
+  auto bad_size = [](int n) { return n < 4 || n > IC_MAX_SIZE || n % 4 != 0; };
+  if (bad_size(size0) || (size1 != 0 && bad_size(size1))) {
+    jrr_set_error("jrr_image_crop: crop sizes %d, %d: one or two sizes, multiples of 4, at most %d", size0, size1, IC_MAX_SIZE);
+    return JRR_ERR_ARG;
+  }
+  if (((uintptr_t)pix & 15) != 0 || pix_bytes % 16 != 0 || pix_bytes == 0) {
+    jrr_set_error("jrr_image_crop: the pixel buffer must be 16-byte aligned and a non-zero multiple of 16 bytes long");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_image_crop(pix, pix_bytes, desc, bboxes, batch, mean, stdv, size0, out0, size1, out1, status, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_mask_prepare(const uint8_t* masks, int batch, int h, int w, float* out, int32_t* valid, void* stream) {
+  if (!masks || !out || !valid || batch < 0 || h <= 0 || w <= 0 || (((uintptr_t)masks | (uintptr_t)out) & 15) != 0) {
+    jrr_set_error("jrr_mask_prepare: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_mask_prepare(masks, batch, h, w, out, valid, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
 /* smplx batch_rodrigues (pose2rot=True branch of the SMPL operator) */
 extern "C" int jrr_rodrigues_forward(const float* aa, float* R, int n, void* stream) {
   if (!aa || !R || n < 0) return JRR_ERR_ARG;

@@ -214,6 +214,16 @@ int launch_fold_bwd(const float* dJT, const float* AT, const float* MT, const fl
 // eval.hip
 int launch_evaluate(const float* pred, const float* target_mm, float* err, float* err_pa, int B, hipStream_t s);
 
+// image.hip
+constexpr int IC_MAX_SIZE = 256;       // largest crop (pixels per side; sizes are multiples of 4)
+constexpr int IC_MAX_ROI_W = 1024;     // widest block of a frame a sample may hand over (pixels; frames are cut to 1000 x 1000)
+// status bits of k_image_crop (ORed into *status, never cleared by the kernel): 1 = a tap of non-zero weight inside the frame but
+// outside the sample's block (nothing is read there), 2 = a descriptor that does not fit the pixel buffer (the sample reads nothing)
+// desc [B][8] = {byte offset, row pitch, roi_y0, roi_x0, roi_h, roi_w, frame_H, frame_W}; pix 16-byte aligned, pix_bytes % 16 == 0
+int launch_image_crop(const uint8_t* pix, size_t pix_bytes, const int64_t* desc, const float* bbox, int B, const float* mean,
+                      const float* stdv, int n0, float* out0, int n1, float* out1, int* status, hipStream_t s);
+int launch_mask_prepare(const uint8_t* masks, int B, int h, int w, float* out, int* valid, hipStream_t s);
+
 // disc.hip
 int launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t s, int ldin = 0, int ldout = 0);
 constexpr int CONV_IMAGE_FLOATS = 4224;     // LDS parameter image of the per-joint MLP kernels (disc.hip CL_*), rounded up

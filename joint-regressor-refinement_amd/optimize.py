@@ -8,6 +8,8 @@ Per outer batch (reference line numbers):
   :164-185  SPIN initial pose (B,24,6) / betas / camera     -> the dataset's pose / orient / betas tensors stand in for
             the SPIN network's prediction (the network and its checkpoint are absent)
   :187-199  camera pre-fit on the 2-D loss                 -> row f1 (`--reprojection`)
+  :234-237  silhouette term                                 -> row f2 (`--silhouette`): synthetic target masks, or with `--image_masks` the
+            dataset's own (batch['mask_rcnn'], scripts/data.py:115-132) through the device image pipeline (data.crop_batch)
   :201-202  fresh Adam over [pose, orient, betas, cam], lr 1e-2
   :220-265  100 inner iterations                            -> ONE C-ABI call, jrr_refine_run
   :276-284  pose-discriminator update, Adam(lr=args.opt_disc_learning_rate)
@@ -85,11 +87,14 @@ def _synthetic_batches(model_np, J_np, B_global: int, n: int, seed: int) -> Iter
                'gt_j3d': torch.from_numpy(full['gt_j3d']), 'cam': torch.from_numpy(full['cam']), 'seed': seed * 1000 + it}
 
 
-def _dataset_batches(root: str, B_global: int, seed: int, device, drop_last: bool = False) -> Iterator[Dict[str, torch.Tensor]]:
+def _dataset_batches(root: str, B_global: int, seed: int, device, drop_last: bool = False,
+                     image_masks: bool = False) -> Iterator[Dict[str, torch.Tensor]]:
     """scripts/optimize.py:132-137: DataLoader(data_set("validation"), batch_size, shuffle=True, drop_last=False)
-    (scripts/test.py:59-63 uses drop_last=True)."""
+    (scripts/test.py:59-63 uses drop_last=True).  image_masks: the samples also carry their index, bounding box and intrinsics, and
+    the batch its frame source: the caller crops its shard on the device (data.crop_batch)."""
     from . import data as jdata
-    ds = jdata.data_set('validation', root=root)
+    frames = jdata.frame_source_for(jdata.split_location('validation', root)) if image_masks else None
+    ds = jdata.data_set('validation', root=root, frames=frames, device_crops=image_masks, compute_canada=image_masks and args.compute_canada)
     g = torch.Generator().manual_seed(seed)          # every rank shuffles identically
     loader = torch.utils.data.DataLoader(ds, batch_size=B_global, num_workers=0, shuffle=True, drop_last=drop_last, generator=g)
     iterator = iter(loader)
@@ -110,8 +115,25 @@ def _dataset_batches(root: str, B_global: int, seed: int, device, drop_last: boo
         if failed:
             continue
         x6 = pose_to_rot6d(batch['orient'].to(device), batch['pose'].to(device)).cpu()
-        yield {'pose6d': x6, 'betas': batch['betas'].float(), 'gt_j3d': batch['gt_j3d'].float(), 'cam': batch['cam'].float(),
+        out = {'pose6d': x6, 'betas': batch['betas'].float(), 'gt_j3d': batch['gt_j3d'].float(), 'cam': batch['cam'].float(),
                'gt_j2d': batch['gt_j2d'].float(), 'seed': seed * 1000 + it}
+        if image_masks:
+            out.update(index=batch['index'], bboxes=batch['bboxes'].float(), intrinsics=batch['intrinsics'].float(), frames=frames)
+        yield out
+
+
+def _dataset_images(full, lo: int, hi: int, device, size: int) -> Dict[str, torch.Tensor]:
+    """scripts/data.py:110-132 for rows [lo, hi) of a dataset batch, on the device: the two crops (the 224 one normalised for the SPIN
+    network, scripts/optimize.py:141-142,164), the prepared masks and `valid`.  The loop's rasteriser renders size x size: a mask of
+    another size is an error that names the sample."""
+    from . import data as jdata
+    index = [int(i) for i in full['index'][lo:hi]]
+    pairs = [full['frames'].read(i) for i in index]
+    for i, (_, mask) in zip(index, pairs):
+        if mask.shape != (size, size):
+            raise ValueError(f'--image_masks: the mask of sample {i} is {mask.shape[0]} x {mask.shape[1]}, the silhouette term renders {size} x {size}')
+    return jdata.crop_batch([p[0] for p in pairs], [p[1] for p in pairs], full['bboxes'][lo:hi], full['intrinsics'][lo:hi], device,
+                            normalize=jdata.SPIN_NORMALIZE)
 
 
 N_J = _engine.NUM_H36M * _engine.NUM_VERTS
@@ -194,8 +216,11 @@ def optimize_pose_refiner(log=print) -> Dict:
             eng.set_shape_disc(sdisc_flat)
         return eng
 
+    image_masks = bool(args.image_masks and args.data_root and args.silhouette)
+    if args.image_masks and not image_masks:
+        raise ValueError('--image_masks needs --data_root and --silhouette')
     if args.data_root:
-        source = _dataset_batches(args.data_root, args.batch_size, args.seed, device)
+        source = _dataset_batches(args.data_root, args.batch_size, args.seed, device, image_masks=image_masks)
     else:
         source = _synthetic_batches(smpl.model_np, J_np, args.batch_size, args.synthetic_batches, args.seed)
 
@@ -249,7 +274,14 @@ def optimize_pose_refiner(log=print) -> Dict:
                 gt_j2d = _synthetic_gt_j2d(eng, x6d, betas, cam, full['seed'], lo, hi, B_global)
             eng.camera_prefit(x6d, betas, gt_j2d, cam, n_steps=args.camera_iters, lr=1e-2)   # :187-199
             eng.set_reprojection(gt_j2d, cam, cam_m, cam_v)
-        if args.silhouette:                                                                # :234-237 (row f2)
+        invalid = None
+        if image_masks:                                                                    # :234-237 on batch['mask_rcnn'] (scripts/data.py:115-132)
+            images = _dataset_images(full, lo, hi, device, eng.sil)
+            sil_mask = images['mask_rcnn'][:, 0].contiguous()
+            invalid = (~images['valid']).sum().float().reshape(1)     # (`valid` is loaded and never used, :159; counted for the record)
+            jdist.all_reduce_sum_(invalid)
+            eng.set_silhouette(sil_mask, cam, cam_m, cam_v)
+        elif args.silhouette:                                                              # :234-237 (row f2)
             sil_mask = _synthetic_mask(eng, x6d, betas, cam, full['seed'], lo, hi, B_global)
             eng.set_silhouette(sil_mask, cam, cam_m, cam_v)
 
@@ -335,6 +367,9 @@ def optimize_pose_refiner(log=print) -> Dict:
                'vertex_tiles_run': tiles_run,     # 216, or the tiles of the regressor's support (FLAG_SUPPORT_TILES engaged)
                'support_vertices_run': sv_n if sv_on else None,      # the vertices the per-vertex iteration ran on (None: tile kernels)
                'body_model': smpl.provenance, 'data': 'dataset' if args.data_root else 'synthetic'}
+        if args.silhouette:
+            rec['masks'] = 'dataset' if image_masks else 'synthetic'
+            rec['masks_invalid'] = int(invalid.item()) if invalid is not None else None
         rec = {k: (float(x) if isinstance(x, np.floating) else x) for k, x in rec.items()}
         pending = (rec, B_global)
 
