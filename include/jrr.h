@@ -189,6 +189,31 @@ int jrr_image_crop(const uint8_t* pixels_dev, size_t pixels_bytes, const int64_t
  * the 2 x 2 corner [:2, :2] zeroed, valid_dev int32 (batch) = (mask[0, 0] != 0) read BEFORE the corner is zeroed.             */
 int jrr_mask_prepare(const uint8_t* masks_dev, int batch, int h, int w, float* out_dev, int32_t* valid_dev, void* stream);
 
+/* ---- fit report: how well a rendered silhouette covers its mask, and a picture of it -----------------------------------
+ * viz() of scripts/optimize.py:35-48 as the reference calls it around its inner loop (:204-218 before, :268-274 after the 100
+ * iterations): r = render > thr_render (0.5 there), m = mask_rcnn > thr_mask (0.8), both STRICT and compared in fp32 as torch.where
+ * on float32 tensors does (mask byte 204 / 255 = 0.800000012 is not above float32(0.8); byte 205 is); NaN compares false.
+ *   alpha_dev, mask_dev   (batch,h,w) float32, 16-byte aligned, h * w a multiple of 4 (every pose is read as float4)
+ *   counts_dev            [batch][4] int32 {r & m, r | m, r, m} summed over the pose's pixels; zeroed by the call itself.  Integer sums:
+ *                         bit-reproducible.  IoU = counts[0] / counts[1] (both empty: the silhouettes agree).                          */
+int jrr_silhouette_compare(const float* alpha_dev, const float* mask_dev, int batch, int h, int w, float thr_render, float thr_mask,
+                           int32_t* counts_dev, void* stream);
+/* The picture: rgb_dev (batch,size,size,3) uint8, interleaved (what a PNG encoder takes); size a multiple of 4, at most 256.
+ *   image_dev     (batch,3,size,size) float32 or NULL (background 0); mean_dev / std_dev [3] each or both NULL: the image is the
+ *                 normalised SPIN crop (scripts/optimize.py:141-142,164) and x * std + mean undoes it (product rounded, then the sum)
+ *   joints2d_dev  (n_sets,batch,17,2) in the crop's pixel frame, 0 <= n_sets <= 3 (NULL with 0)
+ * Arithmetic, every step rounded once in fp32, so that a host restatement reproduces every byte:
+ *   1. background byte = (uint8) floorf(fminf(fmaxf(x, 0), 1) * 255.0f + 0.5f)
+ *   2. where r or m, per channel out = (bg + tint + 1) >> 1 with tint (255,0,0) render only, (0,0,255) mask only, (0,255,0) both
+ *      (the reference shows render + mask == 1, scripts/optimize.py:47-48); elsewhere out = bg
+ *   3. joint discs last, a later set over an earlier one: set 0 (0,255,0) -- the target joints, green in the reference's scatter
+ *      (:63-64) --, set 1 (255,255,0), set 2 (255,0,255).  Pixel (x, y) has its centre at the integer coordinate (imshow); it is
+ *      inside a disc iff dx * dx + dy * dy <= radius * radius with dx = (float)x - jx.  A joint with a non-finite coordinate draws
+ *      nothing; discs are clipped to the image.                                                                                    */
+int jrr_fit_overlay(const float* alpha_dev, const float* mask_dev, const float* image_dev, const float* mean_dev, const float* std_dev,
+                    const float* joints2d_dev, int n_sets, int batch, int size, float thr_render, float thr_mask, float radius,
+                    uint8_t* rgb_dev, void* stream);
+
 /* Axis-angle -> rotation matrix, smplx 0.1.26 lbs.batch_rodrigues: the pose2rot=True branch of the SMPL operator
  * (smplx.SMPL.forward default; the reference's wrapper inherits it, scripts/smpl.py:61-85, base class :7-9).
  * aa (n,3) -> R (n,3,3) with theta = |aa + 1e-8|, R = I + sin(theta) K + (1-cos(theta)) K^2; and its adjoint

@@ -41,6 +41,8 @@ SIGNATURES = {
     'jrr_rot6d_backward': (c_int, [_P, _P, _P, c_int, _P]),
     'jrr_image_crop': (c_int, [_P, c_size_t, _P, _P, c_int, _P, _P, c_int, _P, c_int, _P, _P, _P]),
     'jrr_mask_prepare': (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
+    'jrr_silhouette_compare': (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_float, _P, _P]),
+    'jrr_fit_overlay': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P]),
     'jrr_rodrigues_forward': (c_int, [_P, _P, c_int, _P]),
     'jrr_rodrigues_backward': (c_int, [_P, _P, _P, c_int, _P]),
     'jrr_find_joints_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P]),

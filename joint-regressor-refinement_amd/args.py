@@ -53,6 +53,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--image_masks', action='store_true',
                         help='with --data_root and --silhouette: fit the dataset\'s own Mask-RCNN masks (data.py:115-121,130-132; 224 x 224) '
                              'instead of synthetic ones; frames and masks go through the device image pipeline (data.crop_batch)')
+    parser.add_argument('--fit_report', type=str, default=None, metavar='DIR',
+                        help='with --silhouette: render the mesh before and after the inner loop (optimize.py:204-218,268-274), put the '
+                             'silhouette IoU and the 2-D joint error of both into the record and write overlay PNGs (viz(), :28-74) to DIR')
+    parser.add_argument('--fit_report_images', type=int, default=8,
+                        help='overlay PNG pairs per outer batch and rank (the first poses of the shard)')
     parser.add_argument('--camera_iters', type=int, default=1000, help='camera pre-fit Adam steps (optimize.py:190)')
     parser.add_argument('--save_j_regressor', type=str, default=None,
                         help='write the trained regressor in the models/retrained_J_Regressor.pt format')

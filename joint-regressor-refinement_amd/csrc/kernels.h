@@ -224,6 +224,13 @@ int launch_image_crop(const uint8_t* pix, size_t pix_bytes, const int64_t* desc,
                       const float* stdv, int n0, float* out0, int n1, float* out1, int* status, hipStream_t s);
 int launch_mask_prepare(const uint8_t* masks, int B, int h, int w, float* out, int* valid, hipStream_t s);
 
+// report.hip
+// counts [B][4] = {render & mask, render | mask, render, mask} pixel counts, ADDED to what counts holds; h * w % 4 == 0
+int launch_sil_compare(const float* alpha, const float* mask, int B, int h, int w, float thr_r, float thr_m, int32_t* counts, hipStream_t s);
+// rgb (B,size,size,3) uint8; image / mean + stdv / j2d nullable (j2d with n_sets = 0); size % 4 == 0, at most 256
+int launch_fit_overlay(const float* alpha, const float* mask, const float* image, const float* mean, const float* stdv, const float* j2d,
+                       int n_sets, int B, int size, float thr_r, float thr_m, float radius, uint8_t* rgb, hipStream_t s);
+
 // disc.hip
 int launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t s, int ldin = 0, int ldout = 0);
 constexpr int CONV_IMAGE_FLOATS = 4224;     // LDS parameter image of the per-joint MLP kernels (disc.hip CL_*), rounded up

@@ -16,6 +16,8 @@ Per outer batch (reference line numbers):
   :286-293  shape-discriminator update
   :300-312  J_regressor step, Adam(lr=args.j_reg_lr)        -> + one RCCL all-reduce under data parallelism
   :314-337  MPJPE / PA-MPJPE before and after the J step, logging (all ten scalars of the reference's record)
+  :204-218, :268-274 + viz() :28-74  render before / after the loop -> `--fit_report DIR` (off by default): silhouette IoU and
+            2-D joint error of both renders in the record, overlay PNGs of the first poses (report.py)
 
 Data parallelism (new): one process per GPU, the batch is sharded contiguously, per-pose state is
 rank-local, the MSE means are normalised by the GLOBAL batch.  The inner loop has no collective.  The
@@ -164,7 +166,55 @@ class SharedBucket:
         self.scalars[k:k + 1].copy_(per_pose.sum().reshape(1))
 
 
+class FitReport:
+    """`--fit_report DIR` for one outer batch and shard (scripts/optimize.py:204-218 before the loop, :268-274 after it, viz() at
+    :28-74): the mesh is rendered with the poses as they stand, compared with the batch's mask, the regressed joints are projected.
+    Both calls run a forward of their own on the engine, so each sits where no later call reads the engine's most recent forward."""
+
+    def __init__(self, eng, mask, gt_j2d, n_images: int):
+        self.eng, self.mask, self.gt_j2d = eng, mask, gt_j2d
+        self.n = max(0, min(int(n_images), eng.batch))
+        self.sums = torch.zeros(4, dtype=torch.float64, device=mask.device)     # IoU before / after, pixel error before / after
+        self.iou, self.kept = {}, {}
+
+    def render(self, when: str, x6d, betas, cam):
+        from . import report
+        k = ('before', 'after').index(when)
+        joints, verts = self.eng.find_joints_forward(betas, x6d=x6d, return_verts=True)
+        alpha = self.eng.silhouette_forward(verts, cam)
+        j2d = _engine.project_joints(joints, cam)
+        self.iou[when] = report.iou_from_counts(report.silhouette_compare(alpha, self.mask))
+        self.sums[k] = self.iou[when].sum()
+        if self.gt_j2d is not None:
+            self.sums[2 + k] = (j2d - self.gt_j2d).norm(dim=-1).mean(-1).sum().double()
+        self.kept[when] = (alpha[:self.n].clone(), j2d[:self.n].clone())
+
+    def write(self, directory: str, batch: int, lo: int, image=None, normalize=None):
+        """overlays of the shard's first poses: target joints green, initial yellow, refined magenta (the last on `after` only)"""
+        import os
+        from . import report
+        if self.n == 0:
+            return
+        os.makedirs(directory, exist_ok=True)
+        n = self.n
+        target = self.gt_j2d[:n] if self.gt_j2d is not None else torch.full_like(self.kept['before'][1], float('nan'))
+        sets = {'before': [target, self.kept['before'][1]], 'after': [target, self.kept['before'][1], self.kept['after'][1]]}
+        for when in ('before', 'after'):
+            rgb = report.fit_overlay(self.kept[when][0], self.mask[:n], image=image[:n] if image is not None else None,
+                                     normalize=normalize if image is not None else None, joints2d=sets[when]).cpu().numpy()
+            for i in range(n):
+                report.write_png(os.path.join(directory, f'b{batch:04d}_p{lo + i:05d}_{when}.png'), rgb[i])
+
+
+def _fit_report_flags():
+    """(directory or None, overlays per outer batch and rank); the engine must own a rasteriser and the batch a mask"""
+    if args.fit_report and not args.silhouette:
+        raise ValueError('--fit_report needs --silhouette')
+    return args.fit_report or None, int(args.fit_report_images)
+
+
 def optimize_pose_refiner(log=print) -> Dict:
+    report_dir, report_images = _fit_report_flags()
     dist = jdist.init(args.dist_backend)
     rank, local_rank, world = jdist.env_rank_world()
     device = torch.device(args.device if (world == 1 or args.single_device) else f'cuda:{local_rank}')
@@ -228,6 +278,7 @@ def optimize_pose_refiner(log=print) -> Dict:
     pending = None             # the previous batch's record, waiting for its after-the-J-step metrics
     x6d = betas = cam = None
     lo = hi = 0
+    last_fit = None            # --fit_report: per-pose IoU of the last batch's shard
 
     def finish(rec, B_global, after):
         """complete a record with the all-reduced MPJPE / PA-MPJPE of the stepped regressor and log it (:323-337)"""
@@ -280,9 +331,18 @@ def optimize_pose_refiner(log=print) -> Dict:
             sil_mask = images['mask_rcnn'][:, 0].contiguous()
             invalid = (~images['valid']).sum().float().reshape(1)     # (`valid` is loaded and never used, :159; counted for the record)
             jdist.all_reduce_sum_(invalid)
-            eng.set_silhouette(sil_mask, cam, cam_m, cam_v)
         elif args.silhouette:                                                              # :234-237 (row f2)
             sil_mask = _synthetic_mask(eng, x6d, betas, cam, full['seed'], lo, hi, B_global)
+        fit = None
+        if report_dir:                                                                     # :204-218, ahead of the loop's own forwards
+            gt2d = None
+            if args.reprojection:
+                gt2d = gt_j2d
+            elif 'gt_j2d' in full:
+                gt2d = full['gt_j2d'][lo:hi].to(device).float().contiguous()
+            fit = FitReport(eng, sil_mask, gt2d, report_images)
+            fit.render('before', x6d, betas, cam)
+        if args.silhouette:
             eng.set_silhouette(sil_mask, cam, cam_m, cam_v)
 
         t0 = time.perf_counter()
@@ -343,6 +403,14 @@ def optimize_pose_refiner(log=print) -> Dict:
         joints_after = eng.find_joints_after_j_step(betas, x6d)                            # :317-321 with the stepped regressor (re-regressed from the J step's vertices)
         e_a, epa_a = utils.evaluate_sums(joints_after, gt_mm)
         after_sums = torch.stack([e_a, epa_a])
+        if fit is not None:                                                                 # :268-274; nothing below reads the engine's last forward
+            fit.render('after', x6d, betas, cam)
+            jdist.all_reduce_sum_(fit.sums)                                                 # the one extra (32-byte) collective of --fit_report
+            if image_masks:                                                                 # the 224 crop the SPIN network saw, de-normalised
+                from . import data as jdata
+                fit.write(report_dir, it, lo, image=images['spin_image'], normalize=jdata.SPIN_NORMALIZE)
+            else:
+                fit.write(report_dir, it, lo)
         if use_pd:
             disc_opt.apply(disc_flat, bucket.dD)
             eng.set_pose_disc(disc_flat)
@@ -370,6 +438,11 @@ def optimize_pose_refiner(log=print) -> Dict:
         if args.silhouette:
             rec['masks'] = 'dataset' if image_masks else 'synthetic'
             rec['masks_invalid'] = int(invalid.item()) if invalid is not None else None
+        if fit is not None:
+            fs = fit.sums.cpu().numpy() / B_global
+            rec['silhouette_iou_before'], rec['silhouette_iou_after'] = fs[0], fs[1]
+            rec['j2d_error_px_before'], rec['j2d_error_px_after'] = (fs[2], fs[3]) if fit.gt_j2d is not None else (None, None)
+            last_fit = {'iou_before': fit.iou['before'].cpu().numpy(), 'iou_after': fit.iou['after'].cpu().numpy(), 'shard': (lo, hi)}
         rec = {k: (float(x) if isinstance(x, np.floating) else x) for k, x in rec.items()}
         pending = (rec, B_global)
 
@@ -378,8 +451,11 @@ def optimize_pose_refiner(log=print) -> Dict:
         finish(pending[0], pending[1], after_sums.cpu().double().numpy())
     if args.save_j_regressor and rank == 0:
         checkpoint.save_j_regressor(J_regressor, args.save_j_regressor)
-    return {'history': history, 'J_regressor': J_regressor, 'disc_flat': disc_flat, 'sdisc_flat': sdisc_flat,
-            'x6d': x6d, 'betas': betas, 'cam': cam, 'shard': (lo, hi)}
+    out = {'history': history, 'J_regressor': J_regressor, 'disc_flat': disc_flat, 'sdisc_flat': sdisc_flat,
+           'x6d': x6d, 'betas': betas, 'cam': cam, 'shard': (lo, hi)}
+    if report_dir:
+        out['fit_report'] = last_fit
+    return out
 
 
 def _synthetic_gt_j2d(eng, x6d, betas, cam, seed, lo, hi, B_global):
