@@ -83,6 +83,21 @@ enum {
                                labelled block (`bf16x3_mode`); it is never the headline. */
 };
 
+/* row of the refined-pose table (jrr_pose_export): JRR_EXPORT_ROW floats per sample, offsets in floats.  Layout version 1. */
+enum {
+  JRR_EXPORT_LAYOUT_VERSION = 1,
+  JRR_EXPORT_ROW = 240,        /* 960 bytes: every row of a 16-byte aligned table is 16-byte aligned */
+  JRR_EXPORT_POSE = 0,         /* 72: axis-angle of the 24 joints, orient first (SMPL's `pose`) */
+  JRR_EXPORT_POSE6D = 72,      /* 144: the 6-D values, copied unchanged */
+  JRR_EXPORT_BETAS = 216,      /* 10 */
+  JRR_EXPORT_CAM = 226,        /* 3 */
+  JRR_EXPORT_MARKER = 229,     /* 1.0f in a written row, 0 in a row nobody wrote */
+  JRR_EXPORT_EXTRA = 230,      /* 10: the caller's per-sample values, zeros beyond n_extra */
+  JRR_EXPORT_MAX_EXTRA = 10,
+  JRR_EXPORT_STATUS_INDEX = 1, /* status bit 0: an index outside [0, n_rows); that row is not written */
+  JRR_EXPORT_STATUS_TWICE = 2  /* status bit 1: the target row's marker was already set (a sample exported twice); overwritten */
+};
+
 #define JRR_FLAG_SIL_SIZE(size) ((((size) / 32) & 15) << 16)
 
 typedef struct jrr_model jrr_model_t;   /* device-resident, re-laid-out SMPL constants */
@@ -220,6 +235,30 @@ int jrr_fit_overlay(const float* alpha_dev, const float* mask_dev, const float* 
  * dR (n,3,3) -> daa (n,3), finite at aa = 0.                                                               */
 int jrr_rodrigues_forward(const float* aa_dev, float* R_dev, int n, void* stream);
 int jrr_rodrigues_backward(const float* aa_dev, const float* dR_dev, float* daa_dev, int n, void* stream);
+
+/* Rotation matrix -> axis-angle: R (n,3,3) row-major, assumed rotations -> aa (n,3).  Inverts jrr_rodrigues_forward up to that
+ * kernel's own `+1e-8` quirk (its theta is |aa + 1e-8|).  Canonical form: the angle |aa| lies in [0, pi]; a rotation by exactly pi,
+ * where aa and -aa denote the same matrix, gives the vector whose first non-zero component is positive (diag(-1,-1,1) -> (0,0,pi)).
+ * The exact identity gives exactly 0.  No acos and no division by sin(theta): an unnormalised quaternion by Shepperd's choice
+ * (the largest of tr, R00, R11, R22, ties in that order), then aa = (x,y,z) * 2 atan2(s, w) / s with s = |(x,y,z)| (a two-term
+ * series when s <= 1e-4 w): fp32-accurate at every angle, pi included.  Non-finite input gives non-finite output for that
+ * rotation only.  Not differentiable (no adjoint is provided).  No reference counterpart: the reference's (dead)
+ * scripts/create_smpl_gt.py is the pseudo-ground-truth creator this serves.                                                  */
+int jrr_rotmat_to_axis_angle(const float* R_dev, float* aa_dev, int n, void* stream);
+/* The refined poses of one outer batch as per-sample records (`--save_refined`), ONE launch: per pose b the row
+ *   [ axis-angle of rot6d_to_rotmat(x6d[b]) (72) | x6d[b] (144) | betas[b] (10) | cam[b] (3) | 1.0f | extra[b], zero-padded (10) ]
+ * (JRR_EXPORT_* above) is written to row index_dev[b] of table_dev (n_rows, JRR_EXPORT_ROW), 16-byte aligned.  The axis-angle is
+ * jrr_rotmat_to_axis_angle of the matrices the loop's own 6-D map gives (scripts/utils.py:190-204): canonical form as there --
+ * angle in [0, pi], at pi the first non-zero component positive --, it inverts jrr_rodrigues_forward up to that kernel's own
+ * `+1e-8` quirk.  Everything else is copied bit for bit.
+ *   extra_dev    (batch,n_extra) or NULL (then n_extra values of zero), 0 <= n_extra <= JRR_EXPORT_MAX_EXTRA
+ *   index_dev    (batch) int64
+ *   status_dev   one int32 the CALLER zeroes and reads when it next synchronises, never cleared by the library: bit 0
+ *                (JRR_EXPORT_STATUS_INDEX) an index outside [0, n_rows) -- that row is not written, nothing else is affected; bit 1
+ *                (JRR_EXPORT_STATUS_TWICE) the target row's marker was already non-zero -- the row is overwritten.
+ * The caller zero-fills the table once; rows nobody wrote keep marker 0.  Touches no engine.                                  */
+int jrr_pose_export(const float* x6d_dev, const float* betas_dev, const float* cam_dev, const float* extra_dev, int n_extra,
+                    const int64_t* index_dev, float* table_dev, int64_t n_rows, int32_t* status_dev, int batch, void* stream);
 
 /* find_joints, scripts/utils.py:85-103 (SMPL forward + J_regressor contraction).
  * Exactly one of x6d_dev (B,24,6) / R_dev (B,24,3,3) is non-NULL.  joints_dev (B,17,3).

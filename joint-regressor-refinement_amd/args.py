@@ -58,6 +58,12 @@ def build_parser() -> argparse.ArgumentParser:
                              'silhouette IoU and the 2-D joint error of both into the record and write overlay PNGs (viz(), :28-74) to DIR')
     parser.add_argument('--fit_report_images', type=int, default=8,
                         help='overlay PNG pairs per outer batch and rank (the first poses of the shard)')
+    parser.add_argument('--save_refined', type=str, default=None, metavar='DIR',
+                        help='keep the refined poses: DIR/refined.npz with per-sample pose (72, axis-angle) / pose6d / shape / cam / '
+                             'has_refined and the per-sample errors, rows at their dataset indices, and DIR/meta.json (refined.py)')
+    parser.add_argument('--init_refined', type=str, default=None, metavar='DIR',
+                        help='with --data_root: samples that a --save_refined table in DIR holds start from its pose6d / shape / cam '
+                             'instead of the dataset\'s initial values')
     parser.add_argument('--camera_iters', type=int, default=1000, help='camera pre-fit Adam steps (optimize.py:190)')
     parser.add_argument('--save_j_regressor', type=str, default=None,
                         help='write the trained regressor in the models/retrained_J_Regressor.pt format')

@@ -971,6 +971,37 @@ extern "C" int jrr_rodrigues_backward(const float* aa, const float* dR, float* d
   return JRR_OK;
 }
 
+/* the log map and the refined-pose table (--save_refined) */
+extern "C" int jrr_rotmat_to_axis_angle(const float* R, float* aa, int n, void* stream) {
+  if (!R || !aa || n < 0) {
+    jrr_set_error("jrr_rotmat_to_axis_angle: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (n == 0) return JRR_OK;
+  launch_rotmat_log(R, aa, n, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_pose_export(const float* x6d, const float* betas, const float* cam, const float* extra, int n_extra, const int64_t* index,
+                               float* table, int64_t n_rows, int32_t* status, int batch, void* stream) {
+  if (!x6d || !betas || !cam || !index || !table || !status || batch < 0 || n_rows < 0) {
+    jrr_set_error("jrr_pose_export: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (n_extra < 0 || n_extra > JRR_EXPORT_MAX_EXTRA) {
+    jrr_set_error("jrr_pose_export: n_extra %d: 0 .. %d", n_extra, (int)JRR_EXPORT_MAX_EXTRA);
+    return JRR_ERR_ARG;
+  }
+  if (((uintptr_t)table & 15) != 0 || ((uintptr_t)x6d & 7) != 0 || ((uintptr_t)index & 7) != 0 || ((uintptr_t)status & 3) != 0) {
+    jrr_set_error("jrr_pose_export: the table must be 16-byte aligned (x6d and index 8-byte, status 4-byte)");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_pose_export(x6d, betas, cam, n_extra > 0 ? extra : nullptr, n_extra, index, table, n_rows, status, batch, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
 // The per-vertex-chunk joint partials JP [nvc][3][17][BP] and skinning-adjoint partials dATp [nvcb][12][24][BP] are summed
 // by their consumers (k_joints_loss, k_chain_bwd: a few pose-contiguous loads per thread); the 16 split-K slabs of
 // dF^T (58 MB at 4096 poses) keep a wide reduction kernel of their own -- and so do the dA slabs when there are many of

@@ -231,6 +231,13 @@ int launch_sil_compare(const float* alpha, const float* mask, int B, int h, int 
 int launch_fit_overlay(const float* alpha, const float* mask, const float* image, const float* mean, const float* stdv, const float* j2d,
                        int n_sets, int B, int size, float thr_r, float thr_m, float radius, uint8_t* rgb, hipStream_t s);
 
+// export.hip
+// the log map R (n,3,3) -> axis-angle (n,3), angle in [0, pi] (include/jrr.h, jrr_rotmat_to_axis_angle)
+int launch_rotmat_log(const float* R, float* aa, int n, hipStream_t s);
+// rows of JRR_EXPORT_ROW floats scattered into table (n_rows rows, 16-byte aligned) by index; extra nullable, 0 <= n_extra <= 10
+int launch_pose_export(const float* x6d, const float* betas, const float* cam, const float* extra, int n_extra, const int64_t* index,
+                       float* table, int64_t n_rows, int32_t* status, int B, hipStream_t s);
+
 // disc.hip
 int launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t s, int ldin = 0, int ldout = 0);
 constexpr int CONV_IMAGE_FLOATS = 4224;     // LDS parameter image of the per-joint MLP kernels (disc.hip CL_*), rounded up

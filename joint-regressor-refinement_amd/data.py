@@ -255,9 +255,11 @@ def frame_source_for(location: str):
 class data_set(Dataset):
     """data_set("train" | "validation"): samples of the reference's dataset.  frames=None: the nine tensor-valued keys.  With a frame
     source: the reference's thirteen keys, crops made on the host by find_crop (device_crops=False), or the nine keys plus 'index'
-    for a caller that crops whole batches on the device with crop_batch (device_crops=True)."""
+    for a caller that crops whole batches on the device with crop_batch (device_crops=True).  with_index=True adds 'index' to any of
+    them (the refined-pose table is keyed by it)."""
 
-    def __init__(self, set: str, root: str = 'data/human3.6m', frames=None, device_crops: bool = False, compute_canada: bool = False):
+    def __init__(self, set: str, root: str = 'data/human3.6m', frames=None, device_crops: bool = False, compute_canada: bool = False,
+                 with_index: bool = False):
         if compute_canada:
             raise NotImplementedError('the HDF5 branch of the reference (--compute_canada, scripts/data.py:92-107) needs h5py and is not built')
         location = split_location(set, root)
@@ -273,7 +275,7 @@ class data_set(Dataset):
                 raise ValueError(f'{f}.pt has {getattr(self, f).shape[0]} rows, gt_j3d.pt has {n}')
         self.inc_gt = torch.ones(n, dtype=torch.bool)
         self.gt_j2d_crop = reposition_j2d(self.gt_j2d, self.bboxes)
-        self.frames, self.device_crops = frames, device_crops
+        self.frames, self.device_crops, self.with_index = frames, device_crops, with_index
 
     def __len__(self):
         return self.gt_j3d.shape[0]
@@ -282,6 +284,8 @@ class data_set(Dataset):
         out = {'bboxes': self.bboxes[index], 'betas': self.betas[index], 'cam': self.estimated_translation[index],
                'gt_j2d': self.gt_j2d_crop[index], 'gt_j3d': self.gt_j3d[index], 'intrinsics': self.intrinsics[index],
                'orient': self.orient[index], 'pose': self.pose[index], 'inc_gt': self.inc_gt[index]}
+        if self.with_index:                                                                  # where the sample sits in the split
+            out['index'] = torch.tensor(int(index))
         if self.frames is None:
             return out
         if self.device_crops:

@@ -556,6 +556,34 @@ def rodrigues_backward(aa: torch.Tensor, dR: torch.Tensor) -> torch.Tensor:
     return daa
 
 
+def rotmat_to_axis_angle(R: torch.Tensor) -> torch.Tensor:
+    """the log map: rotation matrices (N,3,3) -> axis-angle (N,3), angle in [0, pi] (jrr_rotmat_to_axis_angle); inverts
+    rodrigues_forward"""
+    lib = _lib.load()
+    R = R.contiguous().view(-1, 3, 3).float()
+    aa = torch.empty(R.shape[0], 3, device=R.device)
+    check(lib.jrr_rotmat_to_axis_angle(ptr(R), ptr(aa), R.shape[0], stream_ptr(R.device)), 'rotmat_to_axis_angle')
+    return aa
+
+
+def pose_export(x6d, betas, cam, index, table, status, extra=None) -> None:
+    """jrr_pose_export: one launch writes the records of poses x6d (B,24,6) / betas (B,10) / cam (B,3) / extra (B,n_extra) or None
+    into rows `index` (B, int64) of `table` (n_rows,240); `status` (1,) int32 collects the error bits"""
+    lib = _lib.load()
+    B = x6d.shape[0]
+    x6d, betas, cam, index = x6d.contiguous(), betas.contiguous(), cam.contiguous(), index.contiguous()
+    extra = None if extra is None else extra.contiguous()
+    assert x6d.shape == (B, NUM_JOINTS, 6) and betas.shape == (B, 10) and cam.shape == (B, 3) and index.shape == (B,)
+    assert table.is_contiguous() and status.is_contiguous()
+    assert all(t.device == x6d.device for t in (betas, cam, index, table, status) + (() if extra is None else (extra,)))
+    assert index.dtype == torch.int64 and status.dtype == torch.int32 and table.dim() == 2 and table.shape[1] == 240
+    assert all(t.dtype == torch.float32 for t in (x6d, betas, cam, table))
+    n_extra = 0 if extra is None else int(extra.shape[1])
+    assert extra is None or (extra.shape[0] == B and extra.dtype == torch.float32)
+    check(lib.jrr_pose_export(ptr(x6d), ptr(betas), ptr(cam), ptr(extra), n_extra, ptr(index), ptr(table), table.shape[0], ptr(status), B,
+                              stream_ptr(x6d.device)), 'pose_export')
+
+
 def project_joints(joints: torch.Tensor, cam: torch.Tensor) -> torch.Tensor:
     """return_2d_joints core (scripts/renderer.py:35-49): (B,17,3), (B,3) -> screen xy (B,17,2)"""
     lib = _lib.load()

@@ -18,6 +18,9 @@ Per outer batch (reference line numbers):
   :314-337  MPJPE / PA-MPJPE before and after the J step, logging (all ten scalars of the reference's record)
   :204-218, :268-274 + viz() :28-74  render before / after the loop -> `--fit_report DIR` (off by default): silhouette IoU and
             2-D joint error of both renders in the record, overlay PNGs of the first poses (report.py)
+  (scripts/create_smpl_gt.py, dead in the reference)    -> `--save_refined DIR` (off by default): the refined poses as per-sample
+            SMPL records, one k_pose_export launch per outer batch, ONE all-reduce and read-back at the end (refined.py);
+            `--init_refined DIR` starts the samples such a table holds from it
 
 Data parallelism (new): one process per GPU, the batch is sharded contiguously, per-pose state is
 rank-local, the MSE means are normalised by the GLOBAL batch.  The inner loop has no collective.  The
@@ -90,13 +93,22 @@ def _synthetic_batches(model_np, J_np, B_global: int, n: int, seed: int) -> Iter
 
 
 def _dataset_batches(root: str, B_global: int, seed: int, device, drop_last: bool = False,
-                     image_masks: bool = False) -> Iterator[Dict[str, torch.Tensor]]:
+                     image_masks: bool = False, with_index: bool = False, init_refined=None) -> Iterator[Dict[str, torch.Tensor]]:
     """scripts/optimize.py:132-137: DataLoader(data_set("validation"), batch_size, shuffle=True, drop_last=False)
     (scripts/test.py:59-63 uses drop_last=True).  image_masks: the samples also carry their index, bounding box and intrinsics, and
-    the batch its frame source: the caller crops its shard on the device (data.crop_batch)."""
+    the batch its frame source: the caller crops its shard on the device (data.crop_batch).  with_index: the batch carries its samples' dataset
+    indices and the split's length (`--save_refined`).  init_refined: the arrays of a refined-pose table (refined.load): samples it
+    holds start from ITS pose6d / shape / cam, copied exactly; the others keep the dataset's values (`--init_refined`)."""
     from . import data as jdata
+    with_index = with_index or init_refined is not None
     frames = jdata.frame_source_for(jdata.split_location('validation', root)) if image_masks else None
-    ds = jdata.data_set('validation', root=root, frames=frames, device_crops=image_masks, compute_canada=image_masks and args.compute_canada)
+    ds = jdata.data_set('validation', root=root, frames=frames, device_crops=image_masks, compute_canada=image_masks and args.compute_canada,
+                        with_index=with_index)
+    if init_refined is not None:
+        if init_refined['has_refined'].shape[0] != len(ds):
+            raise ValueError(f'--init_refined: the table holds {init_refined["has_refined"].shape[0]} samples, the dataset {len(ds)}')
+        init_has = torch.from_numpy(init_refined['has_refined'].astype(bool))
+        init_rows = {key: torch.from_numpy(init_refined[name]).float() for key, name in (('pose6d', 'pose6d'), ('betas', 'shape'), ('cam', 'cam'))}
     g = torch.Generator().manual_seed(seed)          # every rank shuffles identically
     loader = torch.utils.data.DataLoader(ds, batch_size=B_global, num_workers=0, shuffle=True, drop_last=drop_last, generator=g)
     iterator = iter(loader)
@@ -119,6 +131,13 @@ def _dataset_batches(root: str, B_global: int, seed: int, device, drop_last: boo
         x6 = pose_to_rot6d(batch['orient'].to(device), batch['pose'].to(device)).cpu()
         out = {'pose6d': x6, 'betas': batch['betas'].float(), 'gt_j3d': batch['gt_j3d'].float(), 'cam': batch['cam'].float(),
                'gt_j2d': batch['gt_j2d'].float(), 'seed': seed * 1000 + it}
+        if with_index:
+            out.update(index=batch['index'], n_samples=len(ds))
+        if init_refined is not None:
+            idx = batch['index'].long()
+            has = init_has[idx]
+            for key, rows in init_rows.items():
+                out[key][has] = rows[idx[has]]
         if image_masks:
             out.update(index=batch['index'], bboxes=batch['bboxes'].float(), intrinsics=batch['intrinsics'].float(), frames=frames)
         yield out
@@ -213,8 +232,16 @@ def _fit_report_flags():
     return args.fit_report or None, int(args.fit_report_images)
 
 
+def _refined_flags():
+    """(--save_refined directory or None, --init_refined directory or None)"""
+    if args.init_refined and not args.data_root:
+        raise ValueError('--init_refined needs --data_root (the table is keyed by dataset index)')
+    return args.save_refined or None, args.init_refined or None
+
+
 def optimize_pose_refiner(log=print) -> Dict:
     report_dir, report_images = _fit_report_flags()
+    save_dir, init_dir = _refined_flags()
     dist = jdist.init(args.dist_backend)
     rank, local_rank, world = jdist.env_rank_world()
     device = torch.device(args.device if (world == 1 or args.single_device) else f'cuda:{local_rank}')
@@ -270,7 +297,12 @@ def optimize_pose_refiner(log=print) -> Dict:
     if args.image_masks and not image_masks:
         raise ValueError('--image_masks needs --data_root and --silhouette')
     if args.data_root:
-        source = _dataset_batches(args.data_root, args.batch_size, args.seed, device, image_masks=image_masks)
+        init_refined = None
+        if init_dir:
+            from . import refined as jrefined
+            init_refined = jrefined.load(init_dir)
+        source = _dataset_batches(args.data_root, args.batch_size, args.seed, device, image_masks=image_masks,
+                                  with_index=bool(save_dir), init_refined=init_refined)
     else:
         source = _synthetic_batches(smpl.model_np, J_np, args.batch_size, args.synthetic_batches, args.seed)
 
@@ -279,6 +311,11 @@ def optimize_pose_refiner(log=print) -> Dict:
     x6d = betas = cam = None
     lo = hi = 0
     last_fit = None            # --fit_report: per-pose IoU of the last batch's shard
+    refined = None             # --save_refined: the per-sample table (refined.py), allocated with the first batch
+    j_hash = None
+    if save_dir:
+        import hashlib
+        j_hash = hashlib.sha256(np.ascontiguousarray(J_np, dtype=np.float32).tobytes()).hexdigest()[:16]
 
     def finish(rec, B_global, after):
         """complete a record with the all-reduced MPJPE / PA-MPJPE of the stepped regressor and log it (:323-337)"""
@@ -308,6 +345,10 @@ def optimize_pose_refiner(log=print) -> Dict:
         spin_betas = full['betas'][lo:hi].to(device).float().contiguous()
         gt_mm = full['gt_j3d'][lo:hi].to(device).float().contiguous()
         gt_j3d = utils.move_pelvis(gt_mm).contiguous()                                     # :162
+        index_dev = None
+        if save_dir:               # the shard's rows of the refined-pose table: uploaded here, with the batch, while the stream is idle
+            index_dev = (full['index'][lo:hi].to(device, torch.int64) if args.data_root else
+                         torch.arange(it * B_global + lo, it * B_global + hi, dtype=torch.int64, device=device)).contiguous()
         x6d = spin_pose.clone()                                                            # :177-179 pose + orient
         betas = spin_betas.clone()
         m = torch.zeros(B, 154, device=device)                                             # :201-202 fresh optimizer
@@ -391,7 +432,12 @@ def optimize_pose_refiner(log=print) -> Dict:
         joints_before = torch.empty(B, 17, 3, device=device)
         eng.j_regressor_grad(x6d, betas, gt_j3d, sqerr=jsq, out=bucket.dJ, joints=joints_before)
         bucket.put(5, jsq)
-        e_b, epa_b = utils.evaluate_sums(joints_before, gt_mm)                             # :314-315 joints of the old regressor
+        if save_dir:                # the same k_evaluate launch, its per-pose output kept; the sums formed as evaluate_sums forms them
+            with torch.no_grad():
+                err_b, err_pa_b = _engine.evaluate(joints_before.detach().float(), gt_mm.detach().float())
+                e_b, epa_b = err_b.sum(), err_pa_b.sum()
+        else:
+            e_b, epa_b = utils.evaluate_sums(joints_before, gt_mm)                         # :314-315 joints of the old regressor
         bucket.scalars[6:7].copy_(e_b.reshape(1)); bucket.scalars[7:8].copy_(epa_b.reshape(1))
         bucket.scalars[8:10].copy_(after_sums)                                              # previous batch, after its J step
 
@@ -411,6 +457,14 @@ def optimize_pose_refiner(log=print) -> Dict:
                 fit.write(report_dir, it, lo, image=images['spin_image'], normalize=jdata.SPIN_NORMALIZE)
             else:
                 fit.write(report_dir, it, lo)
+        if save_dir:                                                                        # one launch, device tensors only; read back once, after the last batch
+            from . import refined as jrefined
+            if refined is None:
+                refined = jrefined.RefinedTable(full['n_samples'] if args.data_root else args.synthetic_batches * args.batch_size, device)
+            refined.add(index_dev, x6d, betas, cam,
+                        {'joint_err_m': err_b, 'joint_err_pa_m': err_pa_b, 'joint_sqerr': sq, 'pose_disc_sq': pose_disc_sq,
+                         'shape_disc_sq': shape_disc_sq, 'iou_before': fit.iou['before'] if fit is not None else None,
+                         'iou_after': fit.iou['after'] if fit is not None else None})
         if use_pd:
             disc_opt.apply(disc_flat, bucket.dD)
             eng.set_pose_disc(disc_flat)
@@ -451,10 +505,18 @@ def optimize_pose_refiner(log=print) -> Dict:
         finish(pending[0], pending[1], after_sums.cpu().double().numpy())
     if args.save_j_regressor and rank == 0:
         checkpoint.save_j_regressor(J_regressor, args.save_j_regressor)
+    if save_dir:
+        if refined is None:
+            raise RuntimeError('--save_refined: no batch was refined, there is nothing to save')
+        flags_doc = {k: v for k, v in vars(args._get()).items() if isinstance(v, (bool, int, float, str, type(None)))}
+        refined.finish(save_dir, {'flags': flags_doc, 'body_model': smpl.provenance, 'j_regressor_sha256_16': j_hash,
+                                  'inner_iters': int(args.inner_iters), 'data': 'dataset' if args.data_root else 'synthetic'})
     out = {'history': history, 'J_regressor': J_regressor, 'disc_flat': disc_flat, 'sdisc_flat': sdisc_flat,
            'x6d': x6d, 'betas': betas, 'cam': cam, 'shard': (lo, hi)}
     if report_dir:
         out['fit_report'] = last_fit
+    if save_dir or init_dir:
+        out['index'] = full['index'][lo:hi] if args.data_root and x6d is not None else None     # dataset indices of the last shard
     return out
 
 

@@ -6,6 +6,7 @@
   evaluate          scripts/utils.py:117-145  (k_evaluate: on-device Procrustes, row f3 of SURVEY.md)
   find_j_reg_mask   scripts/utils.py:182-187  (reproduces the reference's all-ones mask)
   rot6d_to_rotmat   scripts/utils.py:190-204  (row-wise cross product for every N)
+  rotmat_to_axis_angle / rot6d_to_axis_angle   no counterpart: the way back to SMPL's `pose` vector (k_rotmat_log)
   set_seed          scripts/utils.py:207-215
 """
 from __future__ import annotations
@@ -34,6 +35,19 @@ class _Rot6dFn(torch.autograd.Function):
 def rot6d_to_rotmat(x: torch.Tensor) -> torch.Tensor:
     """(N*6,) / (N,6) / (...,6) -> (N,3,3); columns of R are b1, b2, b3."""
     return _Rot6dFn.apply(x.reshape(-1, 6))
+
+
+def rotmat_to_axis_angle(R: torch.Tensor) -> torch.Tensor:
+    """(...,3,3) rotation matrices -> (N,3) axis-angle, the inverse of smplx batch_rodrigues: angle in [0, pi], at pi the first
+    non-zero component positive (k_rotmat_log).  Not differentiable."""
+    with torch.no_grad():
+        return _engine.rotmat_to_axis_angle(R.detach().reshape(-1, 3, 3))
+
+
+def rot6d_to_axis_angle(x: torch.Tensor) -> torch.Tensor:
+    """(...,6) -> (N,3): rot6d_to_rotmat followed by the log map (what SMPL consumers store as `pose`).  Not differentiable."""
+    with torch.no_grad():
+        return _engine.rotmat_to_axis_angle(_engine.rot6d_forward(x.detach().reshape(-1, 6).float()))
 
 
 class _FindJointsFn(torch.autograd.Function):

@@ -26,6 +26,8 @@ if __name__ == '__main__':
             print('wandb is not installed; logging to stdout')
     utils.set_seed(0)
     res = optimize.optimize_pose_refiner()                                   # main.py:23
+    if args.save_refined and int(os.environ.get('RANK', '0')) == 0:
+        print(f'refined poses: {os.path.join(args.save_refined, "refined.npz")}')
     if not args.skip_eval and int(os.environ.get('RANK', '0')) == 0:
         # main.py:25.  The reference reads models/retrained_J_Regressor.pt; when this run did not write a checkpoint
         # (--save_j_regressor unset) and that file is absent, the regressor just trained is evaluated through a
