@@ -98,6 +98,25 @@ enum {
   JRR_EXPORT_STATUS_TWICE = 2  /* status bit 1: the target row's marker was already set (a sample exported twice); overwritten */
 };
 
+/* row of the evaluation-report table (jrr_eval_accumulate): JRR_EVAL_ACC_ROW int64 per group, offsets in int64, then a trailer of
+ * JRR_EVAL_ACC_TRAILER int64 behind the last row.  Layout version 1. */
+enum {
+  JRR_EVAL_ACC_LAYOUT_VERSION = 1,
+  JRR_EVAL_ACC_ROW = 338,
+  JRR_EVAL_ACC_COUNT = 0,       /* poses counted */
+  JRR_EVAL_ACC_BAD = 1,         /* poses of this group left out: one of their 34 values fails e < 1.0e3f (NaN, inf, absurd) */
+  JRR_EVAL_ACC_SUM = 2,         /* 17: sum over the poses of rn(err_j * 2^24), per joint (units of 2^-24 m) */
+  JRR_EVAL_ACC_SUM_PA = 19,     /* 17: the same for err_pa_j */
+  JRR_EVAL_ACC_HIST = 36,       /* 151: histogram of err_j over all 17 joints, bin min((int)floorf(e * 1000.f), 150) */
+  JRR_EVAL_ACC_HIST_PA = 187,   /* 151: the same for err_pa_j */
+  JRR_EVAL_ACC_BINS = 151,      /* 1-mm bins 0 .. 149, bin 150 = everything >= 150 mm */
+  JRR_EVAL_ACC_TRAILER = 2,
+  JRR_EVAL_ACC_TRAILER_IGNORED = 0,    /* poses with group < 0 (ignored on purpose) */
+  JRR_EVAL_ACC_TRAILER_BAD_GROUP = 1,  /* poses with group >= n_groups (skipped; the caller treats non-zero as an error) */
+  JRR_EVAL_ACC_MAX_GROUPS = 1024,
+  JRR_REGRESS_MAX_REG = 4       /* regressors one jrr_regress_joints call applies to one read of the vertices */
+};
+
 #define JRR_FLAG_SIL_SIZE(size) ((((size) / 32) & 15) << 16)
 
 typedef struct jrr_model jrr_model_t;   /* device-resident, re-laid-out SMPL constants */
@@ -349,6 +368,37 @@ int jrr_adam_step(float* p_dev, const float* g_dev, float* m_dev, float* v_dev, 
  * MPJPE / PA-MPJPE in mm = 1000 * mean over poses.                                                    */
 int jrr_evaluate(const float* pred_j3d_dev, const float* target_j3d_mm_dev, float* err_dev, float* err_pa_dev,
                  int batch, void* stream);
+
+/* evaluate WITHOUT its mean over the joints (scripts/utils.py:127-138 + scripts/eval_utils.py:7-58): err_j_dev / err_pa_j_dev
+ * (batch,17), the per-joint distance and Procrustes-aligned distance in METRES of which jrr_evaluate returns the means (same
+ * arithmetic: one shared body).  pred in m, target in mm, both pelvis-centred inside.  Both outputs 16-byte aligned.          */
+int jrr_evaluate_joints(const float* pred_j3d_dev, const float* target_j3d_mm_dev, float* err_j_dev, float* err_pa_j_dev,
+                        int batch, void* stream);
+
+/* Joints of meshes that need not come from this library: what scripts/test.py:206-212,255-283 (test_pose_refiner_model_VIBE_MEVA)
+ * and :362-373 (METRO) do with another model's vertices, with the arithmetic of find_joints (scripts/utils.py:87-98).
+ * jrr_regress_joints_prepare, once per set of regressors: J_dev (n_reg,17,6890) raw, 1 <= n_reg <= JRR_REGRESS_MAX_REG; mask_dev
+ * (17,6890) or NULL.  J*mask, ReLU, division of each row by its sum, and each row's list of positive columns in ascending order,
+ * into workspace_dev (caller-owned, 16-byte aligned, jrr_regress_joints_workspace_bytes(n_reg) bytes).  One table serves any
+ * number of batches.
+ * jrr_regress_joints: verts_dev (batch,6890,3) pose-major fp32, 8-byte aligned; joints_dev (n_reg,batch,17,3).  The vertices are
+ * read once for all n_reg regressors.  Every output is summed over its row's list in ONE fixed order (double accumulation, one
+ * rounding): it does not depend on batch, on n_reg or on the launch.  A row whose sum is zero gives NaN for that joint of that
+ * regressor (the reference's 0/0) and disturbs nothing else.  n_reg must be the prepared one.                                  */
+size_t jrr_regress_joints_workspace_bytes(int n_reg);
+int jrr_regress_joints_prepare(const float* J_dev, int n_reg, const float* mask_dev, void* workspace_dev, size_t workspace_bytes,
+                               void* stream);
+int jrr_regress_joints(const float* verts_dev, int batch, const void* workspace_dev, int n_reg, float* joints_dev, void* stream);
+
+/* The evaluation report's accumulator (no reference counterpart: scripts/test.py:125-138 prints four means; the per-joint,
+ * per-action and PCK / AUC numbers are read from this table).  ADDS the poses of err_j_dev / err_pa_j_dev (batch,17) to rows
+ * group_dev[b] of acc_dev: int64 [n_groups][JRR_EVAL_ACC_ROW] + JRR_EVAL_ACC_TRAILER words, layout above; the caller zeroes it
+ * once per report.  1 <= n_groups <= JRR_EVAL_ACC_MAX_GROUPS.  A pose with a value that fails e < 1.0e3f counts in word 1 of its
+ * row only (the cap keeps int64 from overflowing below ~5e8 poses; it is no tolerance); group < 0 counts in trailer word 0 only,
+ * group >= n_groups in trailer word 1 only.  Integer atomics only: the table does not depend on the order, on the split into
+ * calls or on the sharding over ranks (sum the ranks' tables).                                                              */
+int jrr_eval_accumulate(const float* err_j_dev, const float* err_pa_j_dev, const int32_t* group_dev, int batch, int n_groups,
+                        int64_t* acc_dev, void* stream);
 
 /* ---- 2-D reprojection --------------------------------------------
  * return_2d_joints core, scripts/renderer.py:35-49 (pytorch3d 0.3.0 PerspectiveCameras, R = I,

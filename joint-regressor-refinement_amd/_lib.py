@@ -66,6 +66,11 @@ SIGNATURES = {
     'jrr_refine_aux_losses': (c_int, [_P, _P, _P, _P]),
     'jrr_adam_step': (c_int, [_P, _P, _P, _P, c_size_t, _P, c_float, c_float, c_float, c_float, _P]),
     'jrr_evaluate': (c_int, [_P, _P, _P, _P, c_int, _P]),
+    'jrr_evaluate_joints': (c_int, [_P, _P, _P, _P, c_int, _P]),
+    'jrr_regress_joints_workspace_bytes': (c_size_t, [c_int]),
+    'jrr_regress_joints_prepare': (c_int, [_P, c_int, _P, _P, c_size_t, _P]),
+    'jrr_regress_joints': (c_int, [_P, c_int, _P, c_int, _P, _P]),
+    'jrr_eval_accumulate': (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     'jrr_project_joints': (c_int, [_P, _P, _P, c_int, _P]),
     'jrr_engine_set_reprojection': (c_int, [_P, _P, _P, _P, _P]),
     'jrr_camera_prefit': (c_int, [_P, _P, _P, _P, _P, c_int, c_float, _P, _P]),

@@ -64,6 +64,19 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--init_refined', type=str, default=None, metavar='DIR',
                         help='with --data_root: samples that a --save_refined table in DIR holds start from its pose6d / shape / cam '
                              'instead of the dataset\'s initial values')
+    parser.add_argument('--eval_report', type=str, default=None, metavar='DIR',
+                        help='evaluation report: DIR/eval.json and DIR/eval.md with MPJPE / PA-MPJPE per group and per joint, PCK and AUC, '
+                             'initial against retrained regressor (eval_report.py); the printed lines of scripts/test.py:125-138 stay as they are')
+    parser.add_argument('--eval_groups', type=str, default='action', choices=['action', 'subject', 'none'],
+                        help='groups of the evaluation report, from the frame path (scripts/data.py:301): the component before '
+                             'imageSequence without its trailing take number, or the one before that; samples without such a path form '
+                             'the single group `all`')
+    parser.add_argument('--eval_vertices', type=str, default=None, metavar='DIR',
+                        help='with --eval_report: evaluate both regressors on the meshes of DIR (vertices.npy (N,6890,3) float32 m in SMPL '
+                             'vertex order, gt_j3d.npy (N,17,3) mm, optional paths.txt or group.npy + group_names.txt) and exit -- what '
+                             'scripts/test.py:141-301 does with the vertices of other models; no SMPL model file is read.  The regressors '
+                             'are multiplied by find_j_reg_mask of the initial one as at scripts/test.py:108 (the convention of '
+                             'test_pose_refiner_model; :206-212 applies no mask -- the reference\'s mask is all ones, so the two agree)')
     parser.add_argument('--camera_iters', type=int, default=1000, help='camera pre-fit Adam steps (optimize.py:190)')
     parser.add_argument('--save_j_regressor', type=str, default=None,
                         help='write the trained regressor in the models/retrained_J_Regressor.pt format')

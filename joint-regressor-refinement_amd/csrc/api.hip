@@ -1386,6 +1386,69 @@ extern "C" int jrr_evaluate(const float* pred, const float* target_mm, float* er
   return JRR_OK;
 }
 
+/* the evaluation report (--eval_report / --eval_vertices): per-joint errors, joints of foreign meshes, the int64 accumulator */
+extern "C" int jrr_evaluate_joints(const float* pred, const float* target_mm, float* err_j, float* err_pa_j, int batch, void* stream) {
+  if (!pred || !target_mm || !err_j || !err_pa_j || batch < 0) {
+    jrr_set_error("jrr_evaluate_joints: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if ((((uintptr_t)err_j | (uintptr_t)err_pa_j) & 15) != 0) {
+    jrr_set_error("jrr_evaluate_joints: err_j and err_pa_j must be 16-byte aligned");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_evaluate_joints(pred, target_mm, err_j, err_pa_j, batch, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" size_t jrr_regress_joints_workspace_bytes(int n_reg) {
+  return (n_reg < 1 || n_reg > JRR_REGRESS_MAX_REG) ? 0 : regress_workspace_bytes(n_reg);
+}
+extern "C" int jrr_regress_joints_prepare(const float* J, int n_reg, const float* mask, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  if (!J || !workspace || n_reg < 1 || n_reg > JRR_REGRESS_MAX_REG || ((uintptr_t)workspace & 15) != 0) {
+    jrr_set_error("jrr_regress_joints_prepare: bad argument (1 <= n_reg <= %d, workspace 16-byte aligned)", (int)JRR_REGRESS_MAX_REG);
+    return JRR_ERR_ARG;
+  }
+  if (workspace_bytes < regress_workspace_bytes(n_reg)) {
+    jrr_set_error("jrr_regress_joints_prepare: the workspace needs jrr_regress_joints_workspace_bytes(%d) = %zu bytes", n_reg,
+                  regress_workspace_bytes(n_reg));
+    return JRR_ERR_WORKSPACE;
+  }
+  launch_regress_prepare(J, mask, n_reg, workspace, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_regress_joints(const float* verts, int batch, const void* workspace, int n_reg, float* joints, void* stream) {
+  if (!verts || !workspace || !joints || batch < 0 || n_reg < 1 || n_reg > JRR_REGRESS_MAX_REG || ((uintptr_t)verts & 7) != 0 ||
+      ((uintptr_t)workspace & 15) != 0) {
+    jrr_set_error("jrr_regress_joints: bad argument (1 <= n_reg <= %d, verts 8-byte aligned)", (int)JRR_REGRESS_MAX_REG);
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  if (launch_regress_joints(verts, workspace, n_reg, joints, batch, (hipStream_t)stream) != 0) {
+    jrr_set_error("jrr_regress_joints: the device refuses %d bytes of LDS per workgroup", V * 3 * 4);
+    return JRR_ERR_HIP;
+  }
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_eval_accumulate(const float* err_j, const float* err_pa_j, const int32_t* group, int batch, int n_groups, int64_t* acc,
+                                   void* stream) {
+  if (!err_j || !err_pa_j || !group || !acc || batch < 0 || ((uintptr_t)acc & 7) != 0) {
+    jrr_set_error("jrr_eval_accumulate: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS) {
+    jrr_set_error("jrr_eval_accumulate: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_eval_accumulate(err_j, err_pa_j, group, n_groups, acc, batch, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
 // =============================================================================================
 // 2-D reprojection (row f1)
 // =============================================================================================

@@ -214,6 +214,16 @@ int launch_fold_bwd(const float* dJT, const float* AT, const float* MT, const fl
 // eval.hip
 int launch_evaluate(const float* pred, const float* target_mm, float* err, float* err_pa, int B, hipStream_t s);
 
+// evalrep.hip
+// the per-joint distances behind launch_evaluate's means; err_j / err_pa_j (B,17), 16-byte aligned
+int launch_evaluate_joints(const float* pred, const float* target_mm, float* err_j, float* err_pa_j, int B, hipStream_t s);
+size_t regress_workspace_bytes(int n_reg);
+int launch_regress_prepare(const float* J, const float* mask, int n_reg, void* ws, hipStream_t s);
+// joints (n_reg,B,17,3) <- normalised regressors of ws x verts (B,6890,3); -1 when the device refuses the LDS the dense path needs
+int launch_regress_joints(const float* verts, const void* ws, int n_reg, float* joints, int B, hipStream_t s);
+int launch_eval_accumulate(const float* err_j, const float* err_pa_j, const int32_t* group, int n_groups, int64_t* acc, int B,
+                           hipStream_t s);
+
 // image.hip
 constexpr int IC_MAX_SIZE = 256;       // largest crop (pixels per side; sizes are multiples of 4)
 constexpr int IC_MAX_ROI_W = 1024;     // widest block of a frame a sample may hand over (pixels; frames are cut to 1000 x 1000)

@@ -247,6 +247,16 @@ def split_location(set: str, root: str) -> str:
     return os.path.join(root, 'precomputed_train' if set == 'train' else 'precomputed_val')
 
 
+def split_image_paths(location: str):
+    """the frame paths of images.pkl (data.py:60-61), one per sample, or None when the split directory has no such file: what the
+    evaluation report groups by (eval_report.group_of)"""
+    p = os.path.join(location, 'images.pkl')
+    if not os.path.isfile(p):
+        return None
+    with open(p, 'rb') as f:
+        return [str(x) for x in pickle.load(f)]
+
+
 def frame_source_for(location: str):
     """the .npy source when the split directory holds one, else the image files of images.pkl"""
     return ArrayFrameSource(directory=location) if ArrayFrameSource.present(location) else FileFrameSource(location)

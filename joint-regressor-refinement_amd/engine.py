@@ -584,6 +584,66 @@ def pose_export(x6d, betas, cam, index, table, status, extra=None) -> None:
                               stream_ptr(x6d.device)), 'pose_export')
 
 
+def evaluate_joints(pred_j3d: torch.Tensor, target_j3d_mm: torch.Tensor):
+    """the per-joint distances behind `evaluate`: err_j, err_pa_j (B,17) in metres (jrr_evaluate_joints)"""
+    lib = _lib.load()
+    B = pred_j3d.shape[0]
+    pred_j3d, target_j3d_mm = pred_j3d.contiguous(), target_j3d_mm.contiguous()
+    assert pred_j3d.shape == (B, 17, 3) and target_j3d_mm.shape == (B, 17, 3) and target_j3d_mm.device == pred_j3d.device
+    assert pred_j3d.dtype == torch.float32 and target_j3d_mm.dtype == torch.float32
+    err_j = torch.empty(B, 17, device=pred_j3d.device)
+    err_pa_j = torch.empty(B, 17, device=pred_j3d.device)
+    check(lib.jrr_evaluate_joints(ptr(pred_j3d), ptr(target_j3d_mm), ptr(err_j), ptr(err_pa_j), B, stream_ptr(pred_j3d.device)),
+          'evaluate_joints')
+    return err_j, err_pa_j
+
+
+class JointRegressorTable:
+    """jrr_regress_joints_prepare: 1 .. 4 raw regressors (n_reg,17,6890) (+ mask (17,6890)) normalised on the device into a workspace
+    this object owns; `regress(verts)` is jrr_regress_joints: verts (B,6890,3) -> joints (n_reg,B,17,3).  No engine, no body model."""
+
+    def __init__(self, J: torch.Tensor, mask: Optional[torch.Tensor] = None):
+        lib = _lib.load()
+        J = J.detach().float().contiguous()
+        if J.dim() == 2:
+            J = J[None]
+        assert J.dim() == 3 and J.shape[1:] == (17, 6890) and 1 <= J.shape[0] <= 4, tuple(J.shape)
+        self.n_reg, self.device = int(J.shape[0]), J.device
+        if mask is not None:
+            mask = mask.detach().float().contiguous()
+            assert mask.shape == (17, 6890) and mask.device == J.device
+        nbytes = int(lib.jrr_regress_joints_workspace_bytes(self.n_reg))
+        self.workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=J.device)
+        check(lib.jrr_regress_joints_prepare(ptr(J), self.n_reg, ptr(mask), ptr(self.workspace), self.workspace.numel() * 8,
+                                             stream_ptr(J.device)), 'regress_joints_prepare')
+
+    def regress(self, verts: torch.Tensor) -> torch.Tensor:
+        lib = _lib.load()
+        verts = verts.contiguous()
+        B = verts.shape[0]
+        assert verts.shape == (B, 6890, 3) and verts.dtype == torch.float32 and verts.device == self.device
+        joints = torch.empty(self.n_reg, B, 17, 3, device=self.device)
+        check(lib.jrr_regress_joints(ptr(verts), B, ptr(self.workspace), self.n_reg, ptr(joints), stream_ptr(self.device)), 'regress_joints')
+        return joints
+
+
+EVAL_ACC_ROW, EVAL_ACC_TRAILER = 338, 2         # include/jrr.h: JRR_EVAL_ACC_ROW, JRR_EVAL_ACC_TRAILER
+
+
+def eval_accumulate(err_j: torch.Tensor, err_pa_j: torch.Tensor, group: torch.Tensor, n_groups: int, acc: torch.Tensor) -> None:
+    """jrr_eval_accumulate: ADD the poses' per-joint errors (B,17) to rows `group` (B, int32) of the int64 table `acc`
+    (n_groups * 338 + 2 words, include/jrr.h JRR_EVAL_ACC_*)"""
+    lib = _lib.load()
+    B = err_j.shape[0]
+    err_j, err_pa_j, group = err_j.contiguous(), err_pa_j.contiguous(), group.contiguous()
+    assert err_j.shape == (B, 17) and err_pa_j.shape == (B, 17) and group.shape == (B,)
+    assert err_j.dtype == torch.float32 and err_pa_j.dtype == torch.float32 and group.dtype == torch.int32 and acc.dtype == torch.int64
+    assert acc.is_contiguous() and acc.numel() == n_groups * EVAL_ACC_ROW + EVAL_ACC_TRAILER
+    assert all(t.device == err_j.device for t in (err_pa_j, group, acc))
+    check(lib.jrr_eval_accumulate(ptr(err_j), ptr(err_pa_j), ptr(group), B, int(n_groups), ptr(acc), stream_ptr(err_j.device)),
+          'eval_accumulate')
+
+
 def project_joints(joints: torch.Tensor, cam: torch.Tensor) -> torch.Tensor:
     """return_2d_joints core (scripts/renderer.py:35-49): (B,17,3), (B,3) -> screen xy (B,17,2)"""
     lib = _lib.load()

@@ -1,0 +1,325 @@
+"""The evaluation report (`--eval_report DIR`, `--eval_vertices DIR`): where the error is.
+
+The reference prints four means (/root/reference/scripts/test.py:125-138).  This module keeps, per group (Human3.6M action or
+subject, from the frame's path as /root/reference/scripts/data.py:301 builds it) and for `all`: MPJPE / PA-MPJPE, their 17 per-joint
+means, PCK at integer-millimetre thresholds and the AUC of PCK over 0, 5, ..., 150 mm (31 thresholds, the 3DHP convention).
+
+`EvalReport` owns an int64 device table (include/jrr.h, JRR_EVAL_ACC_*: `n_groups` rows of 338 words + a 2-word trailer).  `add()`
+is two launches -- jrr_evaluate_joints (the per-joint distances k_evaluate forms before it averages) and jrr_eval_accumulate (integer
+atomics) -- and reads nothing back.  `finish()` makes ONE sum-all-reduce under data parallelism (exact: integers of disjoint shards),
+then the only read-back, raises on the trailer's status word and derives the numbers in float64.  `finish`, `derive` and `write` work
+on a CPU tensor table with a gloo group as well.
+
+`evaluate_vertices()` is `--eval_vertices DIR`: meshes that did not come from this library's SMPL forward
+(/root/reference/scripts/test.py:141-301 test_pose_refiner_model_VIBE_MEVA and the METRO block :362-373 do `relu(J) / rowsum`,
+`J @ pred_vertices`, `evaluate` on another model's vertices) -- `vertices.npy` (N,6890,3) float32 metres, `gt_j3d.npy` (N,17,3) mm,
+optionally `paths.txt` or `group.npy` + `group_names.txt` -- through jrr_regress_joints with both regressors on one read of the
+vertices.  No SMPL model file, no engine.
+"""
+from __future__ import annotations
+
+import hashlib
+import json
+import os
+import re
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import dist as jdist
+
+LAYOUT_VERSION = 1            # include/jrr.h: JRR_EVAL_ACC_LAYOUT_VERSION and the offsets below
+ROW, TRAILER = 338, 2
+COUNT, BAD, SUM, SUM_PA, HIST, HIST_PA, BINS = 0, 1, 2, 19, 36, 187, 151
+NJ = 17
+FIXED = float(1 << 24)        # the sums are in units of 2^-24 m
+MAX_GROUPS = 1024
+PCK_THRESHOLDS_MM = (50, 100, 150)
+AUC_THRESHOLDS_MM = tuple(range(0, 151, 5))     # 31 thresholds
+JOINT_NAMES = ('Pelvis', 'R_Hip', 'R_Knee', 'R_Ankle', 'L_Hip', 'L_Knee', 'L_Ankle', 'Torso', 'Neck', 'Nose', 'Head',
+               'L_Shoulder', 'L_Elbow', 'L_Wrist', 'R_Shoulder', 'R_Elbow', 'R_Wrist')
+GROUP_KINDS = ('action', 'subject', 'none')
+ALL = 'all'
+
+
+# ---- groups ----------------------------------------------------------------------------------------------------------------
+def group_of(path: Optional[str], kind: str = 'action') -> str:
+    """the group of a frame path `.../<subject>/<action>/imageSequence/<camera>/img_%06d.jpg` (scripts/data.py:301): the action is the
+    component directly before `imageSequence` with ONE trailing `-N`, `_N`, ` N` or `.N` removed, the subject the component before
+    that.  No `imageSequence` component, no path, or kind 'none': the single group `all`."""
+    if kind not in GROUP_KINDS:
+        raise ValueError(f'group kind {kind!r}: one of {GROUP_KINDS}')
+    if kind == 'none' or not path:
+        return ALL
+    parts = [p for p in re.split(r'[\\/]+', str(path)) if p]
+    if 'imageSequence' not in parts:
+        return ALL
+    at = parts.index('imageSequence')
+    want = at - 1 if kind == 'action' else at - 2
+    if want < 0:
+        return ALL
+    name = parts[want]
+    if kind == 'action':
+        name = re.sub(r'[-_ .]\d+$', '', name, count=1) or name
+    return name
+
+
+def assign_groups(paths: Optional[Sequence[str]], kind: str, n: Optional[int] = None) -> Tuple[List[str], np.ndarray]:
+    """(sorted group names, int32 id per sample) of a whole split's paths: every rank computes the same from the same list, so the
+    ranks agree without communication.  paths None: the single group `all` for n samples."""
+    if paths is None or kind == 'none':
+        return [ALL], np.zeros(len(paths) if paths is not None else int(n or 0), dtype=np.int32)
+    per = [group_of(p, kind) for p in paths]
+    names = sorted(set(per)) or [ALL]
+    if len(names) > MAX_GROUPS:
+        raise ValueError(f'{len(names)} groups: the accumulator holds at most {MAX_GROUPS}')
+    lut = {g: i for i, g in enumerate(names)}
+    return names, np.array([lut[g] for g in per], dtype=np.int32)
+
+
+# ---- the table -------------------------------------------------------------------------------------------------------------
+class EvalReport:
+    def __init__(self, group_names: Sequence[str], device):
+        self.names = [str(g) for g in group_names]
+        if not 1 <= len(self.names) <= MAX_GROUPS:
+            raise ValueError(f'{len(self.names)} groups: 1 .. {MAX_GROUPS}')
+        self.device = torch.device(device)
+        self.acc = torch.zeros(len(self.names) * ROW + TRAILER, dtype=torch.int64, device=self.device)
+
+    def add(self, pred_joints: torch.Tensor, gt_j3d_mm: torch.Tensor, group_ids: Optional[torch.Tensor] = None) -> None:
+        """pred (B,17,3) m, gt (B,17,3) mm, group_ids (B,) int32 on the same device (None: group 0); < 0 = do not score.  Two
+        launches, nothing read back."""
+        from . import engine as _engine
+        B = pred_joints.shape[0]
+        if group_ids is None:
+            group_ids = torch.zeros(B, dtype=torch.int32, device=pred_joints.device)
+        if group_ids.device != pred_joints.device or group_ids.dtype != torch.int32:
+            raise ValueError(f'EvalReport.add: group_ids must be an int32 tensor on {pred_joints.device}, got {group_ids.dtype} on '
+                             f'{group_ids.device}')
+        err_j, err_pa_j = _engine.evaluate_joints(pred_joints.detach().float(), gt_j3d_mm.detach().float())
+        _engine.eval_accumulate(err_j, err_pa_j, group_ids, len(self.names), self.acc)
+
+    def finish(self, reduce: bool = True) -> dict:
+        """the ONE all-reduce (reduce=False: this process evaluated everything alone), the one read-back, the derivation"""
+        import torch.distributed as dist
+        table = self.acc
+        if reduce and dist.is_available() and dist.is_initialized():
+            if table.is_cuda and dist.get_backend() == 'gloo':
+                table = table.cpu()
+            dist.all_reduce(table, op=dist.ReduceOp.SUM)
+        return derive(table.cpu().numpy(), self.names)
+
+
+def _stats(row: np.ndarray) -> dict:
+    n, n_bad = int(row[COUNT]), int(row[BAD])
+    out = {'n': n, 'n_bad': n_bad, 'raw': [int(x) for x in row]}
+    for key, s0, h0 in (('mpjpe', SUM, HIST), ('pampjpe', SUM_PA, HIST_PA)):
+        sums = row[s0:s0 + NJ].astype(np.float64)
+        hist = row[h0:h0 + BINS].astype(np.float64)
+        if n == 0:
+            out.update({f'{key}_mm': None, f'{key}_per_joint_mm': None, f'pck_{key}': None, f'auc_{key}': None})
+            continue
+        out[f'{key}_mm'] = float(sums.sum() / FIXED / (NJ * n) * 1000.0)
+        out[f'{key}_per_joint_mm'] = [float(s / FIXED / n * 1000.0) for s in sums]
+        below = np.concatenate([[0.0], np.cumsum(hist)])                      # below[t] = values < t mm, t = 0 .. 151
+        pck = lambda t: float(below[t] / (NJ * n))
+        out[f'pck_{key}'] = {str(t): pck(t) for t in PCK_THRESHOLDS_MM}
+        out[f'auc_{key}'] = float(np.mean([pck(t) for t in AUC_THRESHOLDS_MM]))
+    return out
+
+
+def derive(table: np.ndarray, names: Sequence[str]) -> dict:
+    """the numbers of one regressor's report from the int64 table (n_groups * 338 + 2 words): per group and for `all`
+    n, n_bad, MPJPE / PA-MPJPE in mm = sum / 2^24 / (17 n) * 1000 in float64, the 17 per-joint means, PCK@t = (values in bins below t)
+    / (17 n), AUC = mean of PCK over t = 0, 5, ..., 150.  Raises when a pose carried a group id >= n_groups."""
+    table = np.asarray(table)
+    G = len(names)
+    if table.dtype != np.int64 or table.shape != (G * ROW + TRAILER,):
+        raise ValueError(f'evaluation table: {G * ROW + TRAILER} int64 expected for {G} groups, got {table.dtype} {table.shape}')
+    ignored, bad_group = int(table[G * ROW]), int(table[G * ROW + 1])
+    if bad_group:
+        raise RuntimeError(f'evaluation table: {bad_group} poses carried a group id outside [0, {G}); they were not scored')
+    rows = table[:G * ROW].reshape(G, ROW)
+    return {'groups': {name: _stats(rows[i]) for i, name in enumerate(names)}, ALL: _stats(rows.sum(0)), 'ignored': ignored}
+
+
+# ---- the files -------------------------------------------------------------------------------------------------------------
+def sha16(path: Optional[str], fallback: Optional[np.ndarray] = None) -> Optional[str]:
+    if path and os.path.isfile(path):
+        with open(path, 'rb') as f:
+            return hashlib.sha256(f.read()).hexdigest()[:16]
+    if fallback is not None:
+        return hashlib.sha256(np.ascontiguousarray(fallback).tobytes()).hexdigest()[:16]
+    return None
+
+
+def _fmt(x, spec='.2f') -> str:
+    return '-' if x is None else format(x, spec)
+
+
+def _arrow(b, a, spec='.2f') -> str:
+    return f'{_fmt(b, spec)} → {_fmt(a, spec)}'
+
+
+def markdown(doc: dict) -> str:
+    reg = doc['regressors']
+    first = 'before' if 'before' in reg else sorted(reg)[0]
+    last = 'after' if 'after' in reg else sorted(reg)[-1]
+    b, a = reg[first], reg[last]
+    lines = [f'# Evaluation report ({doc["source"]}, groups by {doc["group_kind"]})', '',
+             f'`{first}`: {doc["j_regressor_initial"]["path"]} ({doc["j_regressor_initial"]["sha256_16"]})  ',
+             f'`{last}`: {doc["j_regressor_retrained"]["path"]} ({doc["j_regressor_retrained"]["sha256_16"]})', '',
+             f'Errors in mm, {first} → {last}.  PCK@150 and AUC (PCK over 0, 5, ..., 150 mm) of the unaligned error.', '',
+             '| group | n | bad | MPJPE | PA-MPJPE | PCK@150 | AUC |', '|---|---|---|---|---|---|---|']
+    for name in list(doc['groups']) + [ALL]:
+        rb = b[ALL] if name == ALL else b['groups'][name]
+        ra = a[ALL] if name == ALL else a['groups'][name]
+        pb = None if rb['pck_mpjpe'] is None else rb['pck_mpjpe']['150']
+        pa = None if ra['pck_mpjpe'] is None else ra['pck_mpjpe']['150']
+        lines.append(f'| {name} | {ra["n"]} | {ra["n_bad"]} | {_arrow(rb["mpjpe_mm"], ra["mpjpe_mm"])} | '
+                     f'{_arrow(rb["pampjpe_mm"], ra["pampjpe_mm"])} | {_arrow(pb, pa, ".4f")} | {_arrow(rb["auc_mpjpe"], ra["auc_mpjpe"], ".4f")} |')
+    lines += ['', f'Per joint, all groups ({first} → {last} → difference; negative = the retrained regressor is better):', '',
+              '| joint | MPJPE | PA-MPJPE |', '|---|---|---|']
+    for i, jn in enumerate(doc['joints']):
+        cells = []
+        for key in ('mpjpe_per_joint_mm', 'pampjpe_per_joint_mm'):
+            vb = None if b[ALL][key] is None else b[ALL][key][i]
+            va = None if a[ALL][key] is None else a[ALL][key][i]
+            diff = None if vb is None or va is None else va - vb
+            cells.append(f'{_arrow(vb, va)} → {_fmt(diff, "+.2f")}')
+        lines.append(f'| {jn} | {cells[0]} | {cells[1]} |')
+    if a.get('ignored'):
+        lines += ['', f'{a["ignored"]} samples were not scored (marked invalid by the dataset).']
+    return '\n'.join(lines) + '\n'
+
+
+def write(directory: str, results: Dict[str, dict], group_names: Sequence[str], group_kind: str, source: str, flags: dict,
+          initial: Tuple[Optional[str], Optional[str]], retrained: Tuple[Optional[str], Optional[str]]) -> Optional[dict]:
+    """DIR/eval.json and DIR/eval.md; rank 0 alone writes (the others return None).  `results`: name ('before', 'after') -> what
+    finish() returned; initial / retrained: (path, sha256[:16])."""
+    if _rank() != 0:
+        return None
+    doc = {'layout_version': LAYOUT_VERSION, 'source': source, 'group_kind': group_kind, 'groups': list(group_names),
+           'joints': list(JOINT_NAMES), 'pck_thresholds_mm': list(PCK_THRESHOLDS_MM), 'auc_thresholds_mm': list(AUC_THRESHOLDS_MM),
+           'regressors': results, 'flags': flags,
+           'j_regressor_initial': {'path': initial[0], 'sha256_16': initial[1]},
+           'j_regressor_retrained': {'path': retrained[0], 'sha256_16': retrained[1]}}
+    os.makedirs(directory, exist_ok=True)
+    with open(os.path.join(directory, 'eval.json'), 'w') as f:
+        json.dump(doc, f, indent=1, sort_keys=True, default=str)
+    with open(os.path.join(directory, 'eval.md'), 'w', encoding='utf-8') as f:
+        f.write(markdown(doc))
+    return doc
+
+
+def load(directory: str) -> dict:
+    with open(os.path.join(directory, 'eval.json')) as f:
+        doc = json.load(f)
+    if doc.get('layout_version') != LAYOUT_VERSION:
+        raise ValueError(f'{directory}: table layout version {doc.get("layout_version")!r}, this build reads version {LAYOUT_VERSION}')
+    return doc
+
+
+def _rank() -> int:
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank()
+    return jdist.env_rank_world()[0]
+
+
+# ---- --eval_vertices -------------------------------------------------------------------------------------------------------
+def open_vertices_dir(directory: str, kind: str = 'action'):
+    """(vertices memmap (N,6890,3) float32, gt_j3d memmap (N,17,3) float32, group names, int32 ids (N,)) of an --eval_vertices
+    directory.  Refuses -- with the file's name -- a wrong shape or dtype, a vertex count other than 6890 and NaN ground truth."""
+    vp, gp = os.path.join(directory, 'vertices.npy'), os.path.join(directory, 'gt_j3d.npy')
+    for p in (vp, gp):
+        if not os.path.isfile(p):
+            raise FileNotFoundError(f'--eval_vertices: {p} is missing')
+    verts, gt = np.load(vp, mmap_mode='r'), np.load(gp, mmap_mode='r')
+    if verts.ndim != 3 or verts.shape[2] != 3:
+        raise ValueError(f'{vp}: (N,6890,3) expected, got {verts.shape}')
+    if verts.shape[1] != 6890:
+        raise ValueError(f'{vp}: {verts.shape[1]} vertices per mesh; the regressors are defined on the 6890 SMPL vertices')
+    if verts.dtype != np.float32:
+        raise ValueError(f'{vp}: float32 expected, got {verts.dtype}')
+    N = verts.shape[0]
+    if gt.shape != (N, NJ, 3):
+        raise ValueError(f'{gp}: ({N},17,3) expected for {N} meshes, got {gt.shape}')
+    if gt.dtype not in (np.float32, np.float64):
+        raise ValueError(f'{gp}: float32 or float64 expected, got {gt.dtype}')
+    if np.isnan(gt).any():
+        raise ValueError(f'{gp}: NaN in the ground truth of sample {int(np.argwhere(np.isnan(gt).reshape(N, -1).any(1))[0, 0])}')
+    pp, gnp, gip = (os.path.join(directory, f) for f in ('paths.txt', 'group_names.txt', 'group.npy'))
+    if kind != 'none' and os.path.isfile(pp):
+        with open(pp) as f:
+            paths = [line.rstrip('\n') for line in f]
+        if len(paths) != N:
+            raise ValueError(f'{pp}: {len(paths)} lines for {N} meshes')
+        names, ids = assign_groups(paths, kind)
+    elif kind != 'none' and os.path.isfile(gip) and os.path.isfile(gnp):
+        with open(gnp) as f:
+            names = [line.strip() for line in f if line.strip()]
+        ids = np.load(gip)
+        if ids.shape != (N,) or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError(f'{gip}: ({N},) integers expected, got {ids.dtype} {ids.shape}')
+        if ids.size and int(ids.max()) >= len(names):
+            raise ValueError(f'{gip}: group id {int(ids.max())} with {len(names)} names in {gnp}')
+        ids = ids.astype(np.int32)
+    else:
+        names, ids = assign_groups(None, 'none', N)
+    return verts, gt, names, ids
+
+
+def evaluate_vertices(log=print) -> Optional[dict]:
+    """`--eval_vertices DIR --eval_report OUT`: rank r takes shard_bounds(N, r, world) of the meshes in chunks of --batch_size
+    (pinned uploads), both regressors on one read of the vertices, one all-reduce per report at the end."""
+    from . import checkpoint, engine as _engine, smpl_model, utils
+    from .args import args
+    if not args.eval_report:
+        raise ValueError('--eval_vertices needs --eval_report DIR (where eval.json / eval.md go)')
+    verts, gt, names, ids = open_vertices_dir(args.eval_vertices, args.eval_groups)          # before any launch
+    jdist.init(args.dist_backend)
+    rank, local_rank, world = jdist.env_rank_world()
+    device = torch.device(args.device if (world == 1 or args.single_device) else f'cuda:{local_rank}')
+    torch.cuda.set_device(device)
+    path = args.eval_j_regressor or args.save_j_regressor or 'models/retrained_J_Regressor.pt'
+    J_after = checkpoint.load_j_regressor(path).float()
+    J_np = smpl_model.default_h36m_regressor(args.j_regressor_init,
+                                             allow_default=args.synthetic or args.j_regressor_init == 'SPIN/data/J_regressor_h36m.npy')
+    J_before = torch.from_numpy(J_np).float()
+    Js = torch.stack([J_before, J_after.cpu()]).to(device)
+    table = _engine.JointRegressorTable(Js, utils.find_j_reg_mask(Js[0]))     # the mask of scripts/test.py:51-53,108
+    reports = {'before': EvalReport(names, device), 'after': EvalReport(names, device)}
+    N = verts.shape[0]
+    lo, hi = jdist.shard_bounds(N, rank, world)
+    bs = max(1, int(args.batch_size))
+    stage = [(torch.empty((bs, 6890, 3), dtype=torch.float32).pin_memory(), torch.empty((bs, NJ, 3), dtype=torch.float32).pin_memory(),
+              torch.empty((bs,), dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+    used = [False, False]
+    with torch.no_grad():
+        for k, a in enumerate(range(lo, hi, bs)):
+            b = min(a + bs, hi)
+            n = b - a
+            pv, pg, pi, ev = stage[k % 2]
+            if used[k % 2]:
+                ev.synchronize()                                              # the upload that last read this buffer is done
+            pv.numpy()[:n] = verts[a:b]
+            pg.numpy()[:n] = gt[a:b]
+            pi.numpy()[:n] = ids[a:b]
+            dv, dg, di = (t[:n].to(device, non_blocking=True) for t in (pv, pg, pi))
+            ev.record()
+            used[k % 2] = True
+            joints = table.regress(dv)
+            gtc = utils.move_pelvis(dg)                                       # scripts/test.py:87
+            reports['before'].add(joints[0], gtc, di)
+            reports['after'].add(joints[1], gtc, di)
+    results = {k: r.finish() for k, r in reports.items()}
+    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', dict(vars(args._get())),
+                (args.j_regressor_init, sha16(args.j_regressor_init, J_np)), (path, sha16(path)))
+    if rank == 0:
+        for k in ('before', 'after'):
+            r = results[k][ALL]
+            log(f'{k}: n {r["n"]} (bad {r["n_bad"]})  MPJPE {_fmt(r["mpjpe_mm"], ".4f")}  PAMPJPE {_fmt(r["pampjpe_mm"], ".4f")}')
+        log(f'evaluation report: {os.path.join(args.eval_report, "eval.md")}')
+    return doc

@@ -17,9 +17,41 @@ from typing import Dict, Optional
 
 import torch
 
-from . import checkpoint, engine as _engine, smpl_model, utils
+from . import checkpoint, engine as _engine, eval_report, smpl_model, utils
 from .args import args
 from .smpl import SMPL
+
+
+def validation_batches(model_np, J_np, device, with_index: bool = False):
+    """the batches the report is computed on (:59-63): the dataset's validation split, shuffled, drop_last=True -- or synthetic
+    validation batches with seeds disjoint from the optimiser's.  with_index: dataset batches carry their samples' indices (the same
+    batches either way)."""
+    from . import optimize as _opt
+    if args.data_root:
+        return _opt._dataset_batches(args.data_root, args.batch_size, args.seed, device, drop_last=True, with_index=with_index)
+    return _opt._synthetic_batches(model_np, J_np, args.batch_size, args.synthetic_batches, args.seed + 7919)
+
+
+def _groups():
+    """(group names, int32 id per dataset sample or None): from the whole split's frame paths; synthetic batches and a split without
+    images.pkl form the single group `all`"""
+    paths = None
+    if args.data_root:
+        from . import data as jdata
+        paths = jdata.split_image_paths(jdata.split_location('validation', args.data_root))
+    if paths is None:
+        return [eval_report.ALL], None
+    return eval_report.assign_groups(paths, args.eval_groups)
+
+
+def _batch_groups(batch, group_ids, B: int, device) -> torch.Tensor:
+    """the batch's group ids on the device; samples the batch marks `valid == 0` get -1 (not scored)"""
+    gid = torch.zeros(B, dtype=torch.int32)
+    if group_ids is not None:
+        gid = torch.from_numpy(group_ids[batch['index'].long().numpy()])
+    if 'valid' in batch:
+        gid = torch.where(batch['valid'].cpu().bool(), gid, torch.full_like(gid, -1))
+    return gid.to(device)
 
 
 def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> Dict[str, float]:
@@ -33,11 +65,11 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     J_regressor_initial = torch.from_numpy(J_np).float().to(device)                                      # :48-49
     j_reg_mask = utils.find_j_reg_mask(J_regressor_initial)                                              # :51-53
 
-    from . import optimize as _opt
-    if args.data_root:
-        source = _opt._dataset_batches(args.data_root, args.batch_size, args.seed, device, drop_last=True)       # :59-63
-    else:        # synthetic validation batches: seeds disjoint from the optimiser's
-        source = _opt._synthetic_batches(smpl.model_np, J_np, args.batch_size, args.synthetic_batches, args.seed + 7919)
+    source = validation_batches(smpl.model_np, J_np, device, with_index=bool(args.eval_report))
+    reports, group_ids = None, None
+    if args.eval_report:       # per group / per joint / PCK next to the four printed means: two more launches per evaluate, no read-back
+        names, group_ids = _groups()
+        reports = {'before': eval_report.EvalReport(names, device), 'after': eval_report.EvalReport(names, device)}
 
     mpjpe_before, pampjpe_before, mpjpe_after, pampjpe_after = [], [], [], []
     engines: Dict[int, _engine.RefineEngine] = {}
@@ -53,16 +85,26 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
             eng.set_j_regressor(J_regressor_initial, j_reg_mask)
             joints = eng.find_joints_forward(betas, x6d=x6d)                                             # :107-108
             mb, pb = utils.evaluate(joints, gt)                                                         # :110-111
+            if reports is not None:
+                gid = _batch_groups(batch, group_ids, B, device)
+                reports['before'].add(joints, gt, gid)
             eng.set_j_regressor(J_regressor, j_reg_mask)
             joints = eng.find_joints_forward(betas, x6d=x6d)                                             # :116-117
             ma, pa = utils.evaluate(joints, gt)                                                         # :119-120
             mpjpe_before.append(mb); pampjpe_before.append(pb); mpjpe_after.append(ma); pampjpe_after.append(pa)
+            if reports is not None:
+                reports['after'].add(joints, gt, gid)
     if not mpjpe_before:
         raise RuntimeError('no validation batch (drop_last=True needs at least --batch_size samples)')
     mean = lambda xs: float(torch.tensor(xs, dtype=torch.float64).mean())
     rep = {'mpjpe_before': mean(mpjpe_before), 'pampjpe_before': mean(pampjpe_before), 'mpjpe_after': mean(mpjpe_after),
            'pampjpe_after': mean(pampjpe_after), 'batches': len(mpjpe_before), 'retrained_j_regressor': path,
            'body_model': smpl.provenance}
+    if reports is not None:    # this function runs in ONE process (main.py: rank 0) on whole batches: nothing to reduce
+        results = {k: r.finish(reduce=False) for k, r in reports.items()}
+        rep['eval_report'] = eval_report.write(args.eval_report, results, names, args.eval_groups if group_ids is not None else 'none', 'parameters',
+                                               dict(vars(args._get())), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
+                                               (path, eval_report.sha16(path)))
     log('MPJPE')                                                                                         # :125-138
     log(f"{rep['mpjpe_before']:.4f}")
     log('PAMPJPE')

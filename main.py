@@ -3,7 +3,8 @@
     torchrun --nproc-per-node N main.py [flags]   (data parallel, one process per GPU over RCCL)
 Runs set_seed(0), optimize_pose_refiner() and then the evaluation report test_pose_refiner_model()
 (/root/reference/main.py:21-25).  The reference's two further evaluations (test_pose_refiner_model_VIBE_MEVA,
-main.py:26-27) need the external VIBE / MEVA checkouts and are out of scope."""
+main.py:26-27) need the external VIBE / MEVA checkouts: the networks are out of scope, what those functions do with the
+networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evaluate_vertices), which runs alone and exits."""
 import importlib
 import os
 import sys
@@ -25,6 +26,13 @@ if __name__ == '__main__':
         except ImportError:
             print('wandb is not installed; logging to stdout')
     utils.set_seed(0)
+    if args.eval_vertices:                                                   # scripts/test.py:141-301 on the meshes of a directory
+        importlib.import_module(PKG + '.eval_report').evaluate_vertices()
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            dist.barrier()
+            dist.destroy_process_group()
+        sys.exit(0)
     res = optimize.optimize_pose_refiner()                                   # main.py:23
     if args.save_refined and int(os.environ.get('RANK', '0')) == 0:
         print(f'refined poses: {os.path.join(args.save_refined, "refined.npz")}')

@@ -1,0 +1,333 @@
+"""The evaluation report without a GPU: the host restatement (tests/eval_report_cases.py) against the reference's stored values (G6,
+g10) and the float64 yardstick, the accumulator's integers, PCK / AUC from a hand-made histogram, the groups, EvalReport.finish on
+CPU tensors (one process and two gloo ranks), the files, and what `--eval_vertices` refuses.
+
+Bound of every comparison with float64: 3 x (the reference's float32 distance from float64 on that test's inputs) + 1e-7."""
+import importlib
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import eval_report_cases as ec
+import oracle
+from conftest import PKG_NAME, ROOT, load_golden
+
+F = np.float32
+T = torch.from_numpy
+
+
+def _mod(name):
+    return importlib.import_module(f'{PKG_NAME}.{name}')
+
+
+# ---- 1. the restatement against the reference's values and float64 ----
+def test_procrustes_restatement_on_g6():
+    g = load_golden('g6_evaluate.npz')
+    pred, tgt = T(g['pred']), T(g['target_mm']) / 1000
+    s64 = oracle.batch_compute_similarity_transform_torch(pred.double(), tgt.double()).numpy()
+    d = np.abs(g['s1hat'].astype(np.float64) - s64).max()                  # the reference's own fp32 distance on these 4 poses
+    ours32, ours64 = ec.procrustes(pred, tgt).numpy(), ec.procrustes(pred.double(), tgt.double()).numpy()
+    print(f'g6: reference {d:.3e}  restatement fp32 {np.abs(ours32 - s64).max():.3e}  fp64 {np.abs(ours64 - s64).max():.3e}')
+    assert np.abs(ours32 - s64).max() <= ec.bound(d) and np.abs(ours64 - s64).max() <= ec.bound(d)
+    assert np.abs(ours32 - g['s1hat']).max() <= ec.bound(d)
+
+
+def test_evaluate_joints_restatement_on_g10():
+    g = load_golden('g10_eval_joints.npz')
+    pred, tgt = ec.pose_cases(ec.G10_POSES, ec.G10_POSE_SEED)
+    assert np.array_equal(pred, g['pred']) and np.array_equal(tgt, g['target_mm'])          # the seeds regenerate the fixture's inputs
+    s64, e64, pa64 = ec.evaluate_joints(pred, tgt, torch.float64)
+    p64 = T(pred).double() - T(pred).double()[:, [0], :]
+    t64 = T(tgt).double() / 1000
+    t64 = t64 - t64[:, [0], :]
+    assert np.abs(oracle.batch_compute_similarity_transform_torch(p64, t64).numpy() - s64).max() < 1e-12
+    d_plain, d_pa = np.abs(g['err_j'] - e64).max(), np.abs(g['err_pa_j'] - pa64).max()
+    print(f'g10: reference fp32 against float64: plain {d_plain:.3e} m, PA {d_pa:.3e} m')
+    assert d_pa <= 5e-6                                                    # the generator's condition on the fixture
+    s32, e32, pa32 = ec.evaluate_joints(pred, tgt, torch.float32)
+    assert np.abs(e32 - e64).max() <= ec.bound(d_plain) and np.abs(pa32 - pa64).max() <= ec.bound(d_pa)
+    assert np.abs(e32 - g['err_j']).max() <= ec.bound(d_plain) and np.abs(pa32 - g['err_pa_j']).max() <= ec.bound(d_pa)
+    # the fixture's means are the reference's evaluate()
+    np.testing.assert_allclose(g['err_j'].mean(1).mean() * 1000, float(g['mpjpe']), rtol=1e-6)
+    np.testing.assert_allclose(g['err_pa_j'].mean(1).mean() * 1000, float(g['pampjpe']), rtol=1e-6)
+    assert (pa64[:ec.N_MIRRORED].mean() > 5 * pa64[ec.N_MIRRORED:].mean())                 # mirrored poses cannot be aligned away
+
+
+def test_regress_restatement_on_g10():
+    g = load_golden('g10_eval_joints.npz')
+    verts = ec.mesh_cases(ec.G10_MESHES, ec.G10_MESH_SEED)
+    J = _mod('smpl_model').default_h36m_regressor()
+    cases = (('joints_h36m', J, np.ones_like(J)), ('joints_dense', ec.dense_regressor(ec.G10_DENSE_SEED), None),
+             ('joints_dense_zero_row', ec.dense_regressor(ec.G10_DENSE_SEED, ec.G10_ZERO_ROW), None))
+    for key, Jc, mask in cases:
+        j64, j32 = ec.regress(verts, Jc, mask, torch.float64), ec.regress(verts, Jc, mask, torch.float32)
+        nan = np.isnan(g[key])
+        np.testing.assert_array_equal(np.isnan(j32), nan)
+        np.testing.assert_array_equal(np.isnan(j64), nan)
+        assert nan.any() == (key == 'joints_dense_zero_row')
+        d = np.abs(g[key] - j64)[~nan].max()
+        print(f'{key}: reference fp32 against float64 {d:.3e} m')
+        assert np.abs(j32 - j64)[~nan].max() <= ec.bound(d) and np.abs(j32 - g[key])[~nan].max() <= ec.bound(d)
+
+
+# ---- 2. the accumulator's integers ----
+def test_accumulator_integers_by_hand():
+    e0 = np.full((4, 17), 0.01, dtype=F)
+    e1 = np.full((4, 17), 0.002, dtype=F)
+    e0[0, :3] = [0.05, 0.15, 0.1499999]                # bin edges: exactly 50 mm -> bin 50 (or 49: fl(0.05f * 1000f) decides), 150 -> 150
+    e0[1, 5] = np.nan                                   # a bad pose
+    e1[2, 0] = 2e3                                      # another
+    group = np.array([1, 1, 0, 1], dtype=np.int32)
+    t = ec.accumulate(e0, e1, group, 2)
+    rows = t[:2 * ec.ROW].reshape(2, ec.ROW)
+    assert rows[0, ec.COUNT] == 0 and rows[0, ec.BAD] == 1 and not rows[0, 2:].any()       # a bad pose touches word 1 only
+    assert rows[1, ec.COUNT] == 2 and rows[1, ec.BAD] == 1
+    fx = lambda v: int(np.rint(np.float64(F(v)) * 2.0 ** 24))
+    assert rows[1, ec.SUM + 0] == fx(0.05) + fx(0.01) and rows[1, ec.SUM + 1] == fx(0.15) + fx(0.01)
+    assert rows[1, ec.SUM + 4] == 2 * fx(0.01) and rows[1, ec.SUM_PA + 4] == 2 * fx(0.002)
+    hist, hist_pa = rows[1, ec.HIST:ec.HIST + ec.BINS], rows[1, ec.HIST_PA:ec.HIST_PA + ec.BINS]
+    assert hist.sum() == 34 and hist_pa.sum() == 34 and hist_pa[2] + hist_pa[1] == 34
+    b50 = min(int(np.floor(F(0.05) * F(1000))), 150)
+    assert b50 in (49, 50) and hist[b50] == 1
+    assert hist[150] == 1 and hist[149] == 1                                               # 0.15f -> 150, 0.1499999f -> 149
+    assert hist[10] + hist[9] == 31
+    assert t[-2] == 0 and t[-1] == 0
+    # |error| of one fixed-point value: at most 2^-25 m
+    assert abs(fx(0.0123456) / 2.0 ** 24 - np.float64(F(0.0123456))) <= 2.0 ** -25
+
+
+def test_accumulator_groups_and_splits():
+    e0, e1, group = ec.accumulate_case()
+    t = ec.accumulate(e0, e1, group, 3)
+    rows = t[:3 * ec.ROW].reshape(3, ec.ROW)
+    assert not rows[1].any()                                                               # the empty group
+    assert t[-2] == 2 and t[-1] == 0                                                       # group -1 twice
+    assert rows[:, ec.BAD].sum() == 3                                                      # NaN, inf, 2e3
+    assert rows[:, ec.COUNT].sum() == 65 - 2 - 3
+    assert rows[:, ec.HIST:ec.HIST + ec.BINS].sum() == 17 * 60 and rows[:, ec.HIST_PA:].sum() == 17 * 60
+    # two adds equal one over the concatenation; any order
+    two = ec.accumulate(e0[40:], e1[40:], group[40:], 3, ec.accumulate(e0[:40], e1[:40], group[:40], 3))
+    np.testing.assert_array_equal(two, t)
+    perm = np.random.RandomState(0).permutation(65)
+    np.testing.assert_array_equal(ec.accumulate(e0[perm], e1[perm], group[perm], 3), t)
+    # an id >= n_groups: trailer word 1, rows untouched; the derivation refuses the table
+    g2 = group.copy()
+    g2[9] = 3
+    t2 = ec.accumulate(e0, e1, g2, 3)
+    assert t2[-1] == 1 and t2[:3 * ec.ROW].sum() < t[:3 * ec.ROW].sum()
+    with pytest.raises(RuntimeError, match='1 poses carried a group id outside'):
+        _mod('eval_report').derive(t2, ['a', 'b', 'c'])
+
+
+# ---- 3. the derivation ----
+def test_pck_auc_and_means_from_a_hand_made_table():
+    er = _mod('eval_report')
+    assert (er.ROW, er.TRAILER, er.COUNT, er.BAD, er.SUM, er.SUM_PA, er.HIST, er.HIST_PA, er.BINS) == \
+        (ec.ROW, ec.TRAILER, ec.COUNT, ec.BAD, ec.SUM, ec.SUM_PA, ec.HIST, ec.HIST_PA, ec.BINS)
+    hdr = open(os.path.join(ROOT, 'include', 'jrr.h')).read()
+    for name, val in (('ROW', 338), ('COUNT', 0), ('BAD', 1), ('SUM', 2), ('SUM_PA', 19), ('HIST', 36), ('HIST_PA', 187), ('BINS', 151),
+                      ('LAYOUT_VERSION', 1), ('TRAILER', 2)):
+        assert f'JRR_EVAL_ACC_{name} = {val},' in hdr, name
+    t = np.zeros(2 * er.ROW + er.TRAILER, dtype=np.int64)
+    rows = t[:2 * er.ROW].reshape(2, er.ROW)
+    n = 2                                               # group 'a': 2 poses = 34 values
+    rows[0, er.COUNT] = n
+    rows[0, er.SUM:er.SUM + 17] = np.arange(17) * (1 << 24) // 1000 * n                    # joint i: mean i mm (floored to 2^-24 m)
+    rows[0, er.SUM_PA:er.SUM_PA + 17] = (1 << 24) // 100 * n                               # 10 mm each
+    rows[0, er.HIST + 3] = 17                           # 17 values in [3, 4) mm
+    rows[0, er.HIST + 50] = 10                          # 10 in [50, 51)
+    rows[0, er.HIST + 150] = 7                          # 7 at or above 150 mm
+    rows[0, er.HIST_PA + 10] = 34
+    t[-2] = 5
+    out = er.derive(t, ['a', 'b'])
+    a, b, al = out['groups']['a'], out['groups']['b'], out['all']
+    assert out['ignored'] == 5 and b['n'] == 0 and b['mpjpe_mm'] is None and b['pck_mpjpe'] is None and b['auc_pampjpe'] is None
+    assert a['n'] == 2 and a['n_bad'] == 0 and al['n'] == 2 and al['raw'] == a['raw']
+    np.testing.assert_allclose(a['mpjpe_per_joint_mm'], np.arange(17), atol=1e-4)
+    np.testing.assert_allclose(a['mpjpe_mm'], 8.0, atol=1e-4)
+    np.testing.assert_allclose(a['pampjpe_mm'], 10.0, atol=1e-4)
+    assert a['pck_mpjpe'] == {'50': 17 / 34, '100': 27 / 34, '150': 27 / 34}               # bins BELOW t: [50, 51) is not below 50
+    assert a['pck_pampjpe'] == {'50': 1.0, '100': 1.0, '150': 1.0}
+    # AUC over t = 0, 5, ..., 150: PCK is 0 at t = 0, 17/34 for t = 5 .. 50 (10 thresholds), 27/34 for t = 55 .. 150 (20)
+    np.testing.assert_allclose(a['auc_mpjpe'], (10 * 17 / 34 + 20 * 27 / 34) / 31, rtol=1e-12)
+    np.testing.assert_allclose(a['auc_pampjpe'], 28 / 31, rtol=1e-12)                      # 0 at t = 0, 5, 10; 1 from t = 15 on
+    assert len(er.AUC_THRESHOLDS_MM) == 31
+
+
+def test_group_of_and_assignment():
+    er = _mod('eval_report')
+    base = '/data/h36m/S9/%s/imageSequence/54138969/img_000001.jpg'
+    for action in ('Directions-1', 'Directions_1', 'Directions 1', 'Directions.1', 'Directions'):
+        assert er.group_of(base % action) == 'Directions' and er.group_of(base % action, 'subject') == 'S9'
+    assert er.group_of(base % 'WalkDog-2-1') == 'WalkDog-2'                                # ONE suffix
+    assert er.group_of('/data/frames/000123.jpg') == 'all' and er.group_of(None) == 'all' and er.group_of(base % 'Eating', 'none') == 'all'
+    assert er.group_of('imageSequence/1/img.jpg') == 'all'
+    with pytest.raises(ValueError):
+        er.group_of(base % 'Eating', 'camera')
+    paths = [base % 'Walking-1', base % 'Eating', base.replace('S9', 'S11') % 'Walking', '/no/sequence.jpg']
+    names, ids = er.assign_groups(paths, 'action')
+    assert names == ['Eating', 'Walking', 'all'] and ids.tolist() == [1, 0, 1, 2] and ids.dtype == np.int32
+    names, ids = er.assign_groups(paths, 'subject')
+    assert names == ['S11', 'S9', 'all'] and ids.tolist() == [1, 1, 0, 2]
+    assert er.assign_groups(None, 'action', 5)[0] == ['all'] and er.assign_groups(paths, 'none')[1].tolist() == [0, 0, 0, 0]
+
+
+# ---- 4. finish() on CPU tensors, the files ----
+def _filled_report(names, lo=None, hi=None):
+    er = _mod('eval_report')
+    e0, e1, group = ec.accumulate_case()
+    sl = slice(lo, hi)
+    rep = er.EvalReport(names, 'cpu')
+    rep.acc += T(ec.accumulate(e0[sl], e1[sl], group[sl], len(names)))
+    return rep
+
+
+def test_finish_write_and_load_round_trip(tmp_path):
+    er = _mod('eval_report')
+    names = ['Eating', 'Sitting', 'Walking']
+    before = _filled_report(names).finish()
+    after = _filled_report(names, 0, 40).finish()
+    e0, e1, group = ec.accumulate_case()
+    t = ec.accumulate(e0, e1, group, 3)
+    assert before['all']['raw'] == t[:3 * ec.ROW].reshape(3, ec.ROW).sum(0).tolist() and before['ignored'] == 2
+    keep = (group == 0) & np.all(e0 < 1e3, 1) & np.all(e1 < 1e3, 1)
+    np.testing.assert_allclose(before['groups']['Eating']['mpjpe_mm'], e0[keep].astype(np.float64).mean() * 1000, atol=3e-5)
+    np.testing.assert_allclose(before['groups']['Eating']['pampjpe_per_joint_mm'], e1[keep].astype(np.float64).mean(0) * 1000, atol=3e-5)
+    out = str(tmp_path / 'eval')
+    doc = er.write(out, {'before': before, 'after': after}, names, 'action', 'parameters', {'batch_size': 65, 'eval_report': out},
+                   ('init.npy', 'a' * 16), ('retrained.pt', 'b' * 16))
+    assert sorted(os.listdir(out)) == ['eval.json', 'eval.md']
+    back = er.load(out)
+    assert back == json.loads(json.dumps(doc)) and back['regressors']['before'] == json.loads(json.dumps(before))
+    assert back['groups'] == names and back['joints'][0] == 'Pelvis' and len(back['joints']) == 17
+    assert back['j_regressor_retrained'] == {'path': 'retrained.pt', 'sha256_16': 'b' * 16} and back['flags']['batch_size'] == 65
+    md = open(os.path.join(out, 'eval.md'), encoding='utf-8').read()
+    assert '| Sitting | 0 | 0 | - → - |' in md                                              # the empty group
+    assert f"| all | {after['all']['n']} | {after['all']['n_bad']} | {before['all']['mpjpe_mm']:.2f} → {after['all']['mpjpe_mm']:.2f} |" in md
+    assert md.count('\n| ') == 2 + 4 + 17 and '| R_Wrist |' in md                           # two headers, 3 groups + all, 17 joints
+    back['layout_version'] = 2
+    json.dump(back, open(os.path.join(out, 'eval.json'), 'w'))
+    with pytest.raises(ValueError, match='layout version 2'):
+        er.load(out)
+    # sha16: a file's contents, else the array's bytes
+    p = tmp_path / 'x.bin'
+    p.write_bytes(b'abc')
+    assert er.sha16(str(p)) == 'ba7816bf8f01cfea' and er.sha16('missing', np.zeros(2, dtype=F)) is not None and er.sha16(None) is None
+
+
+_RANK_WORKER = r'''
+import importlib, json, os, sys, numpy as np, torch
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import torch.distributed as dist
+import eval_report_cases as ec
+er = importlib.import_module("joint-regressor-refinement_amd.eval_report")
+dist.init_process_group("gloo")
+rank = dist.get_rank()
+e0, e1, group = ec.accumulate_case()
+lo, hi = (0, 31) if rank == 0 else (31, 65)                      # disjoint shards
+names = ["Eating", "Sitting", "Walking"]
+rep = er.EvalReport(names, "cpu")
+rep.acc += torch.from_numpy(ec.accumulate(e0[lo:hi], e1[lo:hi], group[lo:hi], 3))
+res = rep.finish()
+er.write(os.path.join(sys.argv[2], "rank%d" % rank), {"before": res, "after": res}, names, "action", "parameters", {}, (None, None), (None, None))
+json.dump(res, open(os.path.join(sys.argv[2], "res%d.json" % rank), "w"))
+dist.barrier()
+dist.destroy_process_group()
+'''
+
+
+def test_two_gloo_ranks_equal_one_process(tmp_path):
+    one = _filled_report(['Eating', 'Sitting', 'Walking']).finish()
+    script = tmp_path / 'eval_rank_worker.py'
+    script.write_text(_RANK_WORKER)
+    out = str(tmp_path / 'two')
+    os.makedirs(out)
+    env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT='29581', OMP_NUM_THREADS='2')
+    cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr', '127.0.0.1',
+           '--master-port', '29581', str(script), ROOT, out]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert sorted(os.listdir(out)) == ['rank0', 'res0.json', 'res1.json']                  # rank 0 alone wrote the report
+    for k in (0, 1):
+        assert json.load(open(os.path.join(out, f'res{k}.json'))) == json.loads(json.dumps(one))       # every integer, every number
+
+
+# ---- 5. flags and what --eval_vertices refuses ----
+def test_flags_default_to_off():
+    a = _mod('args')
+    ns = a.get_args([])
+    assert ns.eval_report is None and ns.eval_vertices is None and ns.eval_groups == 'action'
+    ns = a.get_args(['--eval_report', 'out', '--eval_vertices', 'in', '--eval_groups', 'subject'])
+    assert (ns.eval_report, ns.eval_vertices, ns.eval_groups) == ('out', 'in', 'subject')
+    for k, v in a.REFERENCE_FLAGS.items():
+        assert getattr(ns, k) == v, k
+
+
+def _vertices_dir(d, n=3, verts=None, gt=None):
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, 'vertices.npy'), np.zeros((n, 6890, 3), dtype=F) if verts is None else verts)
+    np.save(os.path.join(d, 'gt_j3d.npy'), np.ones((n, 17, 3), dtype=F) if gt is None else gt)
+    return d
+
+
+def test_eval_vertices_input_validation(tmp_path):
+    er, a = _mod('eval_report'), _mod('args')
+    good = _vertices_dir(str(tmp_path / 'good'))
+    verts, gt, names, ids = er.open_vertices_dir(good)
+    assert isinstance(verts, np.memmap) and isinstance(gt, np.memmap) and names == ['all'] and ids.tolist() == [0, 0, 0]
+    with open(os.path.join(good, 'paths.txt'), 'w') as f:
+        f.write('/d/S1/Eating-1/imageSequence/1/a.jpg\n/d/S1/Walking/imageSequence/1/a.jpg\n/d/S1/Eating-2/imageSequence/1/a.jpg\n')
+    assert er.open_vertices_dir(good)[2:][0] == ['Eating', 'Walking'] and er.open_vertices_dir(good)[3].tolist() == [0, 1, 0]
+    assert er.open_vertices_dir(good, 'none')[2] == ['all']
+    os.remove(os.path.join(good, 'paths.txt'))
+    np.save(os.path.join(good, 'group.npy'), np.array([1, 0, 1]))
+    with open(os.path.join(good, 'group_names.txt'), 'w') as f:
+        f.write('VIBE\nMEVA\n')
+    assert er.open_vertices_dir(good)[2] == ['VIBE', 'MEVA'] and er.open_vertices_dir(good)[3].tolist() == [1, 0, 1]
+    cases = [(dict(verts=np.zeros((3, 6890, 3), dtype=np.float64)), 'vertices.npy: float32 expected'),
+             (dict(verts=np.zeros((3, 6890, 2), dtype=F)), r'vertices.npy: \(N,6890,3\) expected'),
+             (dict(verts=np.zeros((3, 10475, 3), dtype=F)), 'vertices.npy: 10475 vertices per mesh'),
+             (dict(gt=np.ones((2, 17, 3), dtype=F)), r'gt_j3d.npy: \(3,17,3\) expected'),
+             (dict(gt=np.ones((3, 17, 3), dtype=np.int32)), 'gt_j3d.npy: float32 or float64 expected')]
+    nan_gt = np.ones((3, 17, 3), dtype=F)
+    nan_gt[1, 4, 2] = np.nan
+    cases.append((dict(gt=nan_gt), 'gt_j3d.npy: NaN in the ground truth of sample 1'))
+    for k, (kw, msg) in enumerate(cases):
+        with pytest.raises(ValueError, match=msg):
+            er.open_vertices_dir(_vertices_dir(str(tmp_path / f'bad{k}'), **kw))
+    with pytest.raises(FileNotFoundError, match='vertices.npy is missing'):
+        er.open_vertices_dir(str(tmp_path / 'nothing'))
+    saved = a._LazyArgs._ns
+    try:                                                # --eval_report missing: refused before anything is opened or launched
+        a._LazyArgs._ns = a.get_args(['--eval_vertices', good, '--synthetic'])
+        with pytest.raises(ValueError, match='--eval_vertices needs --eval_report'):
+            er.evaluate_vertices()
+    finally:
+        a._LazyArgs._ns = saved
+
+
+def test_symbols_declared_exported_and_in_the_table():
+    hdr = open(os.path.join(ROOT, 'include', 'jrr.h')).read()
+    doc = open(os.path.join(ROOT, 'INTEGRATION.md')).read()
+    lib_mod = _mod('_lib')
+    _mod('build').build(verbose=False)
+    lib = lib_mod.load()
+    for name in ('jrr_evaluate_joints', 'jrr_regress_joints_workspace_bytes', 'jrr_regress_joints_prepare', 'jrr_regress_joints',
+                 'jrr_eval_accumulate'):
+        assert f'{name}(' in hdr and name in lib_mod.SIGNATURES and hasattr(lib, name) and f'`{name}`' in doc, name
+    assert lib.jrr_regress_joints_workspace_bytes(0) == 0 and lib.jrr_regress_joints_workspace_bytes(5) == 0
+    assert lib.jrr_regress_joints_workspace_bytes(2) == 512 + 2 * 17 * 6890 * 8
+    # argument errors come back as status codes before anything touches the device
+    z = np.zeros(64, dtype=F)
+    p = z.ctypes.data
+    assert lib.jrr_evaluate_joints(None, p, p, p, 4, None) == -1 and lib.jrr_evaluate_joints(p, p, p + 4, p, 4, None) == -1
+    assert lib.jrr_regress_joints_prepare(p, 5, None, p, 1 << 30, None) == -1
+    assert lib.jrr_regress_joints_prepare(p, 1, None, p, 100, None) == -3 and b'workspace_bytes' in lib.jrr_last_error()
+    assert lib.jrr_regress_joints(p + 4, 1, p, 1, p, None) == -1
+    assert lib.jrr_eval_accumulate(p, p, p, 4, 0, p, None) == -1 and lib.jrr_eval_accumulate(p, p, p, 4, 1025, p, None) == -1
+    assert lib.jrr_eval_accumulate(p, p, p, 0, 3, p, None) == 0 and lib.jrr_evaluate_joints(p, p, p, p, 0, None) == 0

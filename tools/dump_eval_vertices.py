@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Write an `--eval_vertices` directory from the batches the evaluation report itself runs on, through this library's SMPL forward:
+
+    python tools/dump_eval_vertices.py OUT_DIR [driver flags: --synthetic, --data_root, --batch_size, --synthetic_batches, --seed ...]
+    python main.py --eval_vertices OUT_DIR --eval_report out/eval [the same flags]
+
+OUT_DIR/vertices.npy (N,6890,3) float32 metres in SMPL vertex order, OUT_DIR/gt_j3d.npy (N,17,3) float32 mm, and OUT_DIR/paths.txt
+(one frame path per mesh) when the dataset split lists its frames.  It is the template for other models: write the same three files
+from their vertices (VIBE, MEVA, METRO: /root/reference/scripts/test.py:141-301,362-373) and the second command evaluates both
+regressors on them.  The arrays are written through numpy's open_memmap, batch by batch."""
+import importlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = 'joint-regressor-refinement_amd'
+
+
+def main(argv):
+    out, flags = argv[0], argv[1:]
+    argsmod = importlib.import_module(PKG + '.args')
+    argsmod._LazyArgs._ns = argsmod.get_args(flags)
+    args = argsmod.args
+    engine = importlib.import_module(PKG + '.engine')
+    evaluation = importlib.import_module(PKG + '.test')
+    sm = importlib.import_module(PKG + '.smpl_model')
+    jdata = importlib.import_module(PKG + '.data')
+    SMPL = importlib.import_module(PKG + '.smpl').SMPL
+    device = torch.device(args.device)
+    torch.cuda.set_device(device)
+    smpl = SMPL(args.smpl_dir, batch_size=1, allow_synthetic=args.synthetic or args.smpl_dir == 'SPIN/data/smpl').to(device)
+    J_np = sm.default_h36m_regressor(args.j_regressor_init,
+                                     allow_default=args.synthetic or args.j_regressor_init == 'SPIN/data/J_regressor_h36m.npy')
+    paths = jdata.split_image_paths(jdata.split_location('validation', args.data_root)) if args.data_root else None
+    verts, gts, kept = [], [], []
+    engines = {}
+    with torch.no_grad():
+        for batch in evaluation.validation_batches(smpl.model_np, J_np, device, with_index=paths is not None):
+            B = int(batch['pose6d'].shape[0])
+            if B not in engines:
+                engines[B] = engine.RefineEngine(smpl.device_model, B, flags=engine.FLAG_KEEP_VERTS)
+                engines[B].set_j_regressor(torch.from_numpy(J_np).float().to(device))
+            _, v = engines[B].find_joints_forward(batch['betas'].to(device).float().contiguous(),
+                                                  x6d=batch['pose6d'].to(device).float().contiguous(), return_verts=True)
+            verts.append(v.cpu().numpy())
+            gts.append(batch['gt_j3d'].float().numpy())
+            if paths is not None:
+                kept += [paths[int(i)] for i in batch['index']]
+    if not verts:
+        raise SystemExit('no validation batch (drop_last=True needs at least --batch_size samples)')
+    N = sum(v.shape[0] for v in verts)
+    os.makedirs(out, exist_ok=True)
+    vm = np.lib.format.open_memmap(os.path.join(out, 'vertices.npy'), mode='w+', dtype=np.float32, shape=(N, 6890, 3))
+    at = 0
+    for v in verts:
+        vm[at:at + v.shape[0]] = v
+        at += v.shape[0]
+    vm.flush()
+    del vm
+    np.save(os.path.join(out, 'gt_j3d.npy'), np.concatenate(gts).astype(np.float32))
+    if paths is not None:
+        with open(os.path.join(out, 'paths.txt'), 'w') as f:
+            f.write(''.join(p + '\n' for p in kept))
+    print(f'wrote {N} meshes to {out}')
+
+
+if __name__ == '__main__':
+    if len(sys.argv) < 2:
+        raise SystemExit(__doc__)
+    main(sys.argv[1:])
