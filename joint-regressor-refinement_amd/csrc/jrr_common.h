@@ -205,7 +205,7 @@ struct jrr_model {
   int* v2p_host;   // host copy of Model::v2p (jrr_model_set_faces), NULL for the identity order
 };
 
-// error plumbing (api.hip)
+// error plumbing (defined in api.hip; used by every translation unit)
 void jrr_set_error(const char* fmt, ...);
 #define JRR_HIP(expr)                                                                 \
   do {                                                                                \

@@ -1,4 +1,4 @@
-// Internal launcher interface between api.hip and the kernel translation units.
+// Internal launcher interface between the host translation units (api.hip, model.hip, refine.hip: engine.h) and the kernel translation units.
 #pragma once
 #include "jrr_common.h"
 
