@@ -8,6 +8,8 @@
 reproduces every row's values; a stored -0.0 comes back as +0.0 there, since -0.0 + 0.0 = +0.0, so two ranks and one can differ in
 the sign bit of a zero -- the only bits `--init_refined` does not get back), then the only read-back, validates, and rank 0 writes `refined.npz` (plain numpy arrays) and `meta.json`.
 `finish`, `load` and the validation work on CPU tensors with a gloo group as well.
+`RefinedExport` is `--save_refined` as the driver sees it: built once, called where a batch is uploaded, where its joints are scored, after
+its J step and at the end of the run.
 """
 from __future__ import annotations
 
@@ -19,6 +21,7 @@ import numpy as np
 import torch
 
 from . import dist as jdist
+from .args import args
 
 LAYOUT_VERSION = 1
 ROW = 240                     # include/jrr.h: JRR_EXPORT_ROW and the offsets below
@@ -68,6 +71,47 @@ class RefinedTable:
             with open(os.path.join(directory, 'meta.json'), 'w') as f:
                 json.dump(doc, f, indent=1, sort_keys=True, default=str)
         return arrays
+
+
+class RefinedExport:
+    """`--save_refined DIR` of one run of the driver.  `b` is the driver's batch object (its batch dict `full`, shard bounds, poses and
+    per-pose loss terms), `fit` the run's FitReport or None."""
+
+    def __init__(self, directory: str, J_np: np.ndarray, body_model: str):
+        import hashlib
+        self.directory, self.body_model = directory, body_model
+        self.j_hash = hashlib.sha256(np.ascontiguousarray(J_np, dtype=np.float32).tobytes()).hexdigest()[:16]
+        self.table = None          # allocated with the first batch: a dataset batch says how many samples the split has
+
+    def upload_index(self, b, device):
+        """the shard's rows of the table -- dataset indices, or `it * B_global + row` for synthetic batches: uploaded with the batch,
+        ahead of the loop, while the stream is idle"""
+        first = b.it * b.B_global
+        self.index = (b.full['index'][b.lo:b.hi].to(device, torch.int64) if args.data_root else
+                      torch.arange(first + b.lo, first + b.hi, dtype=torch.int64, device=device)).contiguous()
+
+    def evaluate_sums(self, joints: torch.Tensor, gt_mm: torch.Tensor):
+        """utils.evaluate_sums -- the same one k_evaluate launch, the sums formed the same way -- with the per-pose output kept"""
+        from . import engine as _engine
+        with torch.no_grad():
+            self.err, self.err_pa = _engine.evaluate(joints.detach().float(), gt_mm.detach().float())
+            return self.err.sum(), self.err_pa.sum()
+
+    def add(self, b, fit):
+        """one launch, device tensors only; read back once, after the last batch"""
+        if self.table is None:
+            self.table = RefinedTable(b.full['n_samples'] if args.data_root else args.synthetic_batches * args.batch_size, b.x6d.device)
+        self.table.add(self.index, b.x6d, b.betas, b.cam,
+                       {'joint_err_m': self.err, 'joint_err_pa_m': self.err_pa, 'joint_sqerr': b.sq, 'pose_disc_sq': b.pose_disc_sq,
+                        'shape_disc_sq': b.shape_disc_sq, 'iou_before': fit.iou['before'] if fit is not None else None,
+                        'iou_after': fit.iou['after'] if fit is not None else None})
+
+    def finish(self):
+        if self.table is None:
+            raise RuntimeError('--save_refined: no batch was refined, there is nothing to save')
+        flags_doc = {k: v for k, v in vars(args._get()).items() if isinstance(v, (bool, int, float, str, type(None)))}
+        self.table.finish(self.directory, {'flags': flags_doc, 'body_model': self.body_model, 'j_regressor_sha256_16': self.j_hash,
+                                           'inner_iters': int(args.inner_iters), 'data': 'dataset' if args.data_root else 'synthetic'})
 
 
 def _rank() -> int:

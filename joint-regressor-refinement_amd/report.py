@@ -14,7 +14,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, dist as jdist, engine as _engine
 
 THR_RENDER, THR_MASK = 0.5, 0.8        # scripts/optimize.py:35,41
 
@@ -117,3 +117,64 @@ def write_png(path: str, rgb) -> None:
            + _chunk(b'IDAT', zlib.compress(rows.tobytes(), 6)) + _chunk(b'IEND', b''))
     with open(path, 'wb') as f:
         f.write(png)
+
+
+class FitReport:
+    """`--fit_report DIR` of one run (scripts/optimize.py:204-218 before the loop, :268-274 after it, viz() at :28-74): per outer batch and
+    shard the mesh is rendered with the poses as they stand, compared with the batch's mask, the regressed joints are projected.
+    `before` and `after` each run a forward of their own on the batch's engine, so each sits where no later call reads the engine's
+    most recent forward.  They take the driver's batch object: its engine, mask, poses, shard bounds and global batch."""
+
+    def __init__(self, directory: str, n_images: int):
+        self.directory, self.n_images = directory, int(n_images)
+        self.last = None           # the run's `fit_report` return value: per-pose IoU of the last batch's shard
+
+    def before(self, b):
+        self.gt_j2d = b.gt_j2d     # the loop's own 2-D target (--reprojection), else the dataset's, else none
+        if self.gt_j2d is None and 'gt_j2d' in b.full:
+            self.gt_j2d = b.full['gt_j2d'][b.lo:b.hi].to(b.sil_mask.device).float().contiguous()
+        self.n = max(0, min(self.n_images, b.eng.batch))
+        self.sums = torch.zeros(4, dtype=torch.float64, device=b.sil_mask.device)     # IoU before / after, pixel error before / after
+        self.iou, self.kept = {}, {}
+        self._render('before', b)
+
+    def after(self, b):
+        self._render('after', b)
+        jdist.all_reduce_sum_(self.sums)                                              # the one extra (32-byte) collective of --fit_report
+        self._write(b)
+
+    def record(self, b) -> dict:
+        """the record's four fields (means over the GLOBAL batch); reads the sums back"""
+        fs = self.sums.cpu().numpy() / b.B_global
+        px = (fs[2], fs[3]) if self.gt_j2d is not None else (None, None)
+        self.last = {'iou_before': self.iou['before'].cpu().numpy(), 'iou_after': self.iou['after'].cpu().numpy(), 'shard': (b.lo, b.hi)}
+        return {'silhouette_iou_before': fs[0], 'silhouette_iou_after': fs[1], 'j2d_error_px_before': px[0], 'j2d_error_px_after': px[1]}
+
+    def _render(self, when: str, b):
+        k = ('before', 'after').index(when)
+        joints, verts = b.eng.find_joints_forward(b.betas, x6d=b.x6d, return_verts=True)
+        alpha = b.eng.silhouette_forward(verts, b.cam)
+        j2d = _engine.project_joints(joints, b.cam)
+        self.iou[when] = iou_from_counts(silhouette_compare(alpha, b.sil_mask))
+        self.sums[k] = self.iou[when].sum()
+        if self.gt_j2d is not None:
+            self.sums[2 + k] = (j2d - self.gt_j2d).norm(dim=-1).mean(-1).sum().double()
+        self.kept[when] = (alpha[:self.n].clone(), j2d[:self.n].clone())
+
+    def _write(self, b):
+        """overlays of the shard's first poses: target joints green, initial yellow, refined magenta (the last on `after` only); under
+        `--image_masks` over the 224 crop the SPIN network saw, de-normalised"""
+        import os
+        from .data import SPIN_NORMALIZE
+        if self.n == 0:
+            return
+        os.makedirs(self.directory, exist_ok=True)
+        n = self.n
+        image = b.images['spin_image'][:n] if b.images is not None else None
+        target = self.gt_j2d[:n] if self.gt_j2d is not None else torch.full_like(self.kept['before'][1], float('nan'))
+        sets = {'before': [target, self.kept['before'][1]], 'after': [target, self.kept['before'][1], self.kept['after'][1]]}
+        for when in ('before', 'after'):
+            rgb = fit_overlay(self.kept[when][0], b.sil_mask[:n], image=image, normalize=SPIN_NORMALIZE if image is not None else None,
+                              joints2d=sets[when]).cpu().numpy()
+            for i in range(n):
+                write_png(os.path.join(self.directory, f'b{b.it:04d}_p{b.lo + i:05d}_{when}.png'), rgb[i])

@@ -17,7 +17,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import checkpoint, engine as _engine, eval_report, smpl_model, utils
+from . import batches, checkpoint, engine as _engine, eval_report, smpl_model, utils
 from .args import args
 from .smpl import SMPL
 
@@ -26,10 +26,9 @@ def validation_batches(model_np, J_np, device, with_index: bool = False):
     """the batches the report is computed on (:59-63): the dataset's validation split, shuffled, drop_last=True -- or synthetic
     validation batches with seeds disjoint from the optimiser's.  with_index: dataset batches carry their samples' indices (the same
     batches either way)."""
-    from . import optimize as _opt
     if args.data_root:
-        return _opt._dataset_batches(args.data_root, args.batch_size, args.seed, device, drop_last=True, with_index=with_index)
-    return _opt._synthetic_batches(model_np, J_np, args.batch_size, args.synthetic_batches, args.seed + 7919)
+        return batches.dataset_batches(args.data_root, args.batch_size, args.seed, device, drop_last=True, with_index=with_index)
+    return batches.synthetic_batches(model_np, J_np, args.batch_size, args.synthetic_batches, args.seed + 7919)
 
 
 def _groups():

@@ -307,7 +307,7 @@ def test_dataset_index_is_opt_in(tmp_path):
 
 
 def test_init_refined_overlays_exactly_the_refined_rows(tmp_path):
-    refined, opt = _mod('refined'), _mod('optimize')
+    refined, opt = _mod('refined'), _mod('batches')
     n, B = 13, 5
     files = _write_6d_dataset(str(tmp_path), n, 1)
     rows_at = [2, 3, 7, 12]
@@ -317,8 +317,8 @@ def test_init_refined_overlays_exactly_the_refined_rows(tmp_path):
     init = refined.load(table_dir, n=n)
     seen = np.zeros(n, dtype=int)
     sizes = []
-    plain = list(opt._dataset_batches(str(tmp_path), B, 0, 'cpu'))
-    for full, ref in zip(opt._dataset_batches(str(tmp_path), B, 0, 'cpu', init_refined=init), plain):
+    plain = list(opt.dataset_batches(str(tmp_path), B, 0, 'cpu'))
+    for full, ref in zip(opt.dataset_batches(str(tmp_path), B, 0, 'cpu', init_refined=init), plain):
         assert 'index' not in ref and 'n_samples' not in ref and full['n_samples'] == n
         idx = full['index'].numpy()
         sizes.append(len(idx))
@@ -334,10 +334,10 @@ def test_init_refined_overlays_exactly_the_refined_rows(tmp_path):
                 assert torch.equal(full['cam'][k], files['estimated_translation'][i])
         assert torch.equal(full['gt_j3d'], ref['gt_j3d'])       # the same shuffled batch as without the table
     assert sizes == [5, 5, 3] and (seen == 1).all()
-    with_index = next(opt._dataset_batches(str(tmp_path), B, 0, 'cpu', with_index=True))
+    with_index = next(opt.dataset_batches(str(tmp_path), B, 0, 'cpu', with_index=True))
     assert torch.equal(with_index['pose6d'], plain[0]['pose6d']) and with_index['index'].shape == (5,)
     # a table of another length is refused
     t2, _ = _filled(n + 1, rows_at, seed=4)
     t2.finish(str(tmp_path / 'longer'))
     with pytest.raises(ValueError, match='the table holds 14 samples, the dataset 13'):
-        next(opt._dataset_batches(str(tmp_path), B, 0, 'cpu', init_refined=refined.load(str(tmp_path / 'longer'))))
+        next(opt.dataset_batches(str(tmp_path), B, 0, 'cpu', init_refined=refined.load(str(tmp_path / 'longer'))))
