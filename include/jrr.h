@@ -248,6 +248,55 @@ int jrr_fit_overlay(const float* alpha_dev, const float* mask_dev, const float* 
                     const float* joints2d_dev, int n_sets, int batch, int size, float thr_render, float thr_mask, float radius,
                     uint8_t* rgb_dev, void* stream);
 
+/* ---- fit report: shaded views of the fitted mesh (`--fit_report_mesh`) ------------------------------------------------------
+ * What the reference had pytorch3d for (scripts/mesh_renderer.py:23-79 builds the silhouette renderer only; a shaded view is what a
+ * person checks before trusting a fit).  Neither operator takes an engine or a body model; vertices and faces are in the API (file)
+ * vertex order; n_verts and n_faces are general.  Every operation below is rounded once in fp32, in the order written; no product is
+ * fused into a sum: the results are functions of the inputs alone (no float atomics) and a host restatement can follow them.  Every index
+ * read from device memory is checked against its array before use: nothing is read outside the arrays whatever the data.
+ *
+ * jrr_vertex_normals: pytorch3d's Meshes.verts_normals_packed.
+ *   verts_dev (batch,n_verts,3), faces_dev (n_faces,3) int32, normals_dev (batch,n_verts,3)
+ *   adj_offset_dev [n_verts + 1], adj_face_dev [3 * n_faces] int32: the faces of vertex v are adj_face[adj_offset[v] .. adj_offset[v + 1]),
+ *   in ascending face index (CSR; a vertex may have any number of them).
+ *   Per (pose, vertex): s = 0; for every face f of the list, in the list's order, with p0, p1, p2 its vertices, e1 = p1 - p0, e2 = p2 - p0:
+ *     s += (e1y * e2z - e1z * e2y, e1z * e2x - e1x * e2z, e1x * e2y - e1y * e2x)      (area-weighted: not normalised per face)
+ *   len = sqrtf((sx * sx + sy * sy) + sz * sz), n = s / (len < 1e-6f ? 1e-6f : len) -- torch's clamp(min = 1e-6), which keeps a NaN.
+ *   A vertex without faces gives exactly (0,0,0).  A non-finite vertex makes the normals of the vertices that share a face with it NaN,
+ *   in its own pose, and nothing else.  A list entry or a vertex index outside its array is skipped.  */
+int jrr_vertex_normals(const float* verts_dev, const int32_t* faces_dev, const int32_t* adj_offset_dev, const int32_t* adj_face_dev,
+                       int batch, int n_verts, int n_faces, float* normals_dev, void* stream);
+/* jrr_mesh_shade: the picture of the mesh behind a pix_to_face map (jrr_silhouette_pix_to_face): rgb_dev (batch,size,size,3) uint8,
+ * interleaved; size a multiple of 4, at most 256.
+ *   verts_dev, normals_dev (batch,n_verts,3); faces_dev (n_faces,3) int32; cam_dev (batch,3); pix_to_face_dev (batch,size,size) int32,
+ *   16-byte aligned
+ *   image_dev / mean_dev / std_dev   the background as in jrr_fit_overlay: (batch,3,size,size) float32 or NULL, x * std + mean (product
+ *                 rounded, then the sum) when mean / std are given; without an image every pixel's x is `background`.  bg = fminf(fmaxf(x, 0), 1)
+ *   colour_host, light_host [3]      base colour c in [0, 1] and the light direction l in view space, used as given (the caller normalises);
+ *                 the headlight is (0, 0, -1)
+ *   depth_dev (batch,size,size), normal_dev (batch,size,size,3)   nullable, 16-byte aligned
+ *   status_dev    nullable; one int32 the CALLER zeroes and reads when it next synchronises, never cleared by the library
+ * Per pixel (row i, column j) with face f = pix_to_face >= 0 and its vertices k = 0, 1, 2 (model-space position p_k, normal n_k):
+ *   1. projection, as the rasteriser's k_sil_project: X = -2 x + cx, Y = -2 y + cy, Z_k = 2 z + cz, (u_k, v_k) = (F * X / Z_k, F * Y / Z_k)
+ *      with F = 5000.0f / (float)size; pixel centre (px, py) = (1 - (float)(2 j + 1) / (float)size, 1 - (float)(2 i + 1) / (float)size)
+ *   2. E(p; a, b) = (px - ax) * (by - ay) - (py - ay) * (bx - ax); area = E((u2,v2); 0, 1);
+ *      w0 = E(p; 1, 2) / area, w1 = E(p; 2, 0) / area, w2 = E(p; 0, 1) / area          (no perspective correction: pytorch3d 0.3.0's default)
+ *   3. pytorch3d's clip_barycentric_coordinates: w_k = fmaxf(w_k, 0), then w_k = w_k / fmaxf((w0 + w1) + w2, 1e-5f) -- a pixel whose centre
+ *      lies just outside its face (the rasteriser's projection is compiled with other contraction choices) still gets a bounded answer
+ *   4. depth = (w0 * Z_0 + w1 * Z_1) + w2 * Z_2
+ *   5. m = (w0 * n_0 + w1 * n_1) + w2 * n_2 per component; view-space n = (-mx, -my, mz) / fmaxf(sqrtf((mx * mx + my * my) + mz * mz), 1e-6f)
+ *   6. I = ambient + (1 - ambient) * |(nx * lx + ny * ly) + nz * lz|: TWO-SIDED -- a mesh whose faces wind inward (the synthetic body) is
+ *      shaded like one that winds outward (the SMPL file)
+ *   7. per channel byte = (uint8) floorf(fminf(fmaxf((opacity * c) * I + (1 - opacity) * bg, 0), 1) * 255.0f + 0.5f)
+ * A pixel with f < 0: byte = floorf(bg * 255.0f + 0.5f), depth -1 (pytorch3d's zbuf convention), normal 0.  f >= n_faces, or a vertex index
+ * of face f outside [0, n_verts): the same, and status bit 0.  A face with !(|area| > 1e-8f), or a non-finite u_k, v_k or Z_k: the same, and
+ * status bit 1.                                                                                                                        */
+enum { JRR_SHADE_STATUS_INDEX = 1, JRR_SHADE_STATUS_DEGENERATE = 2 };
+int jrr_mesh_shade(const float* verts_dev, const float* normals_dev, const int32_t* faces_dev, const float* cam_dev,
+                   const int32_t* pix_to_face_dev, const float* image_dev, const float* mean_dev, const float* std_dev, int batch, int n_verts,
+                   int n_faces, int size, const float* colour_host, float opacity, float ambient, const float* light_host, float background,
+                   uint8_t* rgb_dev, float* depth_dev, float* normal_dev, int32_t* status_dev, void* stream);
+
 /* Axis-angle -> rotation matrix, smplx 0.1.26 lbs.batch_rodrigues: the pose2rot=True branch of the SMPL operator
  * (smplx.SMPL.forward default; the reference's wrapper inherits it, scripts/smpl.py:61-85, base class :7-9).
  * aa (n,3) -> R (n,3,3) with theta = |aa + 1e-8|, R = I + sin(theta) K + (1-cos(theta)) K^2; and its adjoint

@@ -43,6 +43,9 @@ SIGNATURES = {
     'jrr_mask_prepare': (c_int, [_P, c_int, c_int, c_int, _P, _P, _P]),
     'jrr_silhouette_compare': (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_float, _P, _P]),
     'jrr_fit_overlay': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, _P, _P]),
+    'jrr_vertex_normals': (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    'jrr_mesh_shade': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, POINTER(c_float), c_float, c_float, POINTER(c_float), c_float,
+                               _P, _P, _P, _P, _P]),
     'jrr_rodrigues_forward': (c_int, [_P, _P, c_int, _P]),
     'jrr_rodrigues_backward': (c_int, [_P, _P, _P, c_int, _P]),
     'jrr_rotmat_to_axis_angle': (c_int, [_P, _P, c_int, _P]),

@@ -58,6 +58,9 @@ def build_parser() -> argparse.ArgumentParser:
                              'silhouette IoU and the 2-D joint error of both into the record and write overlay PNGs (viz(), :28-74) to DIR')
     parser.add_argument('--fit_report_images', type=int, default=8,
                         help='overlay PNG pairs per outer batch and rank (the first poses of the shard)')
+    parser.add_argument('--fit_report_mesh', action='store_true',
+                        help='with --fit_report: also write b*_p*_{before,after}_mesh.png, the fitted body shaded from the front (over the '
+                             'crop under --image_masks, else over black) and from the side (over grey) in one (S, 2S) picture')
     parser.add_argument('--save_refined', type=str, default=None, metavar='DIR',
                         help='keep the refined poses: DIR/refined.npz with per-sample pose (72, axis-angle) / pose6d / shape / cam / '
                              'has_refined and the per-sample errors, rows at their dataset indices, and DIR/meta.json (refined.py)')

@@ -529,6 +529,49 @@ extern "C" int jrr_fit_overlay(const float* alpha, const float* mask, const floa
   return JRR_OK;
 }
 
+/* the fit report's shaded views (--fit_report_mesh): no engine, no body model */
+extern "C" int jrr_vertex_normals(const float* verts, const int32_t* faces, const int32_t* adj_offset, const int32_t* adj_face, int batch,
+                                  int n_verts, int n_faces, float* normals, void* stream) {
+  if (!verts || !faces || !adj_offset || !adj_face || !normals || batch < 0 || n_verts < 1 || n_faces < 1 || n_faces > (1 << 28) ||
+      (long long)batch * n_verts > (1LL << 30)) {
+    jrr_set_error("jrr_vertex_normals: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if ((((uintptr_t)verts | (uintptr_t)faces | (uintptr_t)adj_offset | (uintptr_t)adj_face | (uintptr_t)normals) & 3) != 0) {
+    jrr_set_error("jrr_vertex_normals: every array must be 4-byte aligned");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_vertex_normals(verts, faces, adj_offset, adj_face, normals, batch, n_verts, n_faces, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_mesh_shade(const float* verts, const float* normals, const int32_t* faces, const float* cam, const int32_t* pix_to_face,
+                              const float* image, const float* mean, const float* stdv, int batch, int n_verts, int n_faces, int size,
+                              const float* colour_host, float opacity, float ambient, const float* light_host, float background,
+                              uint8_t* rgb, float* depth, float* normal, int32_t* status, void* stream) {
+  if (!verts || !normals || !faces || !cam || !pix_to_face || !colour_host || !light_host || !rgb || batch < 0 || batch > (1 << 24) ||
+      n_verts < 1 || n_faces < 1 || n_faces > (1 << 28) || (long long)batch * n_verts > (1LL << 30) ||
+      ((mean == nullptr) != (stdv == nullptr)) || (mean && !image)) {
+    jrr_set_error("jrr_mesh_shade: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (size < 4 || size > 256 || size % 4 != 0) {
+    jrr_set_error("jrr_mesh_shade: size %d: a multiple of 4, at most 256", size);
+    return JRR_ERR_ARG;
+  }
+  if ((((uintptr_t)pix_to_face | (uintptr_t)image | (uintptr_t)depth | (uintptr_t)normal) & 15) != 0 ||
+      (((uintptr_t)verts | (uintptr_t)normals | (uintptr_t)faces | (uintptr_t)cam | (uintptr_t)rgb | (uintptr_t)status) & 3) != 0) {
+    jrr_set_error("jrr_mesh_shade: pix_to_face, image, depth and normal must be 16-byte aligned, everything else 4-byte aligned");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_mesh_shade(verts, normals, faces, cam, pix_to_face, image, mean, stdv, batch, n_verts, n_faces, size, colour_host, opacity, ambient,
+                    light_host, background, rgb, depth, normal, status, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
 /* smplx batch_rodrigues (pose2rot=True branch of the SMPL operator) */
 extern "C" int jrr_rodrigues_forward(const float* aa, float* R, int n, void* stream) {
   if (!aa || !R || n < 0) return JRR_ERR_ARG;

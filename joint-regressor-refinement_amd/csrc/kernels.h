@@ -241,6 +241,16 @@ int launch_sil_compare(const float* alpha, const float* mask, int B, int h, int 
 int launch_fit_overlay(const float* alpha, const float* mask, const float* image, const float* mean, const float* stdv, const float* j2d,
                        int n_sets, int B, int size, float thr_r, float thr_m, float radius, uint8_t* rgb, hipStream_t s);
 
+// shade.hip
+// normals (B,V,3) = the area-weighted sum of the face normals at each vertex over its CSR list adj_offset [V + 1] / adj_face [3 F], unit length
+int launch_vertex_normals(const float* verts, const int32_t* faces, const int32_t* adj_offset, const int32_t* adj_face, float* normals,
+                          int B, int V, int F, hipStream_t s);
+// rgb (B,size,size,3) uint8 of the shaded mesh behind p2f (B,size,size); image / mean + stdv / depth / normal / status nullable;
+// colour and light [3] host values; size % 4 == 0, at most 256
+int launch_mesh_shade(const float* verts, const float* normals, const int32_t* faces, const float* cam, const int32_t* p2f, const float* image,
+                      const float* mean, const float* stdv, int B, int V, int F, int size, const float* colour, float opacity, float ambient,
+                      const float* light, float background, uint8_t* rgb, float* depth, float* normal, int32_t* status, hipStream_t s);
+
 // export.hip
 // the log map R (n,3,3) -> axis-angle (n,3), angle in [0, pi] (include/jrr.h, jrr_rotmat_to_axis_angle)
 int launch_rotmat_log(const float* R, float* aa, int n, hipStream_t s);

@@ -64,6 +64,23 @@ class Mesh_Renderer(nn.Module):
         ones = torch.ones_like(alpha)
         return torch.stack([ones, ones, ones, alpha], dim=1)
 
+    @torch.no_grad()
+    def shaded(self, batch, smpl_verts, image=None, side=False):
+        """The body itself, shaded: uint8 (B, H, W, 3) at every size the class takes.  `smpl_verts` as in forward() (after the flip
+        and scale); `image` (B,3,H,W) in [0, 1] is the background (black without one); side=True turns every body by 90 degrees about
+        the vertical axis through its centroid before it is rendered (report.side_view) and draws it over grey.  What the reference
+        had a pytorch3d shader for: the rasteriser's nearest face per pixel, vertex normals (verts_normals_packed) interpolated with
+        clipped barycentrics, a two-sided headlight (include/jrr.h, jrr_mesh_shade).  Not differentiable."""
+        from . import report as _report
+        world = (smpl_verts.detach() * smpl_verts.new_tensor([-0.5, -0.5, 0.5])).contiguous().float()
+        cam = batch['cam'].detach().contiguous().float()
+        if side:
+            world = _report.side_view(world, cam).contiguous()
+        eng = self._engine(world.shape[0])
+        eng.silhouette_forward(world, cam)
+        return _report.mesh_shade(world, cam, eng.silhouette_pix_to_face(), self.smpl.faces, image=image,
+                                  background=_report.SIDE_GREY if side and image is None else 0.0)
+
 
 def render_mesh(smpl, silhouette_renderer, betas, orient, pose, batch):
     """scripts/optimize.py:77-85: SMPL vertices, x/y flip, x2 scale, alpha channel of the renderer."""

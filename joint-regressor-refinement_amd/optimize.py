@@ -17,7 +17,8 @@ Per outer batch (reference line numbers):
   :300-312  J_regressor step, Adam(lr=args.j_reg_lr)        -> + one RCCL all-reduce under data parallelism
   :314-337  MPJPE / PA-MPJPE before and after the J step, logging (all ten scalars of the reference's record)
   :204-218, :268-274 + viz() :28-74  render before / after the loop -> `--fit_report DIR` (off by default): silhouette IoU and
-            2-D joint error of both renders in the record, overlay PNGs of the first poses (report.py)
+            2-D joint error of both renders in the record, overlay PNGs of the first poses (report.py); with `--fit_report_mesh` also
+            the fitted body itself, shaded, front and side view in one PNG per pose and render (k_vertex_normals, k_mesh_shade)
   (scripts/create_smpl_gt.py, dead in the reference)    -> `--save_refined DIR` (off by default): the refined poses as per-sample
             SMPL records, one k_pose_export launch per outer batch, ONE all-reduce and read-back at the end (refined.py);
             `--init_refined DIR` starts the samples such a table holds from it
@@ -104,6 +105,8 @@ def _check_flags():
     """the flag combinations the driver refuses, before anything is set up"""
     if args.fit_report and not args.silhouette:           # the engine must own a rasteriser and the batch a mask
         raise ValueError('--fit_report needs --silhouette')
+    if args.fit_report_mesh and not args.fit_report:      # the shaded views are pictures of the report's two renders
+        raise ValueError('--fit_report_mesh needs --fit_report')
     if args.init_refined and not args.data_root:
         raise ValueError('--init_refined needs --data_root (the table is keyed by dataset index)')
     if args.image_masks and not (args.data_root and args.silhouette):
@@ -384,7 +387,7 @@ def _record(run: Run, b: Batch, sc, hist_np, fit) -> dict:
 def optimize_pose_refiner(log=print) -> Dict:
     _check_flags()
     run = Run()
-    fit = jreport.FitReport(args.fit_report, args.fit_report_images) if args.fit_report else None
+    fit = jreport.FitReport(args.fit_report, args.fit_report_images, mesh=args.fit_report_mesh) if args.fit_report else None
     export = jrefined.RefinedExport(args.save_refined, run.J_np, run.smpl.provenance) if args.save_refined else None
     records = RecordLog(run.rank, log)
     b = None

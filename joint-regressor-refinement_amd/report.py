@@ -4,9 +4,15 @@ The reference renders the mesh before and after its 100 iterations and hands the
 (/root/reference/scripts/optimize.py:204-218, :268-274, viz at :28-74): `render > 0.5`, `mask_rcnn > 0.8`, the map
 `mask + render == 1` with the 2-D joints scattered over it, one PNG per pose.  Here the comparison (jrr_silhouette_compare) and the
 compositing (jrr_fit_overlay) run on the device over the whole batch; only the PNG encoder is host code, standard library only.
+
+`--fit_report_mesh` adds what the reference had pytorch3d for: the fitted body itself, shaded, from the front and from the side
+(jrr_vertex_normals, jrr_mesh_shade over the rasteriser's pix_to_face; include/jrr.h states the arithmetic).
 """
 from __future__ import annotations
 
+import ctypes
+import hashlib
+import math
 import struct
 import zlib
 from typing import Optional, Sequence
@@ -99,6 +105,155 @@ def fit_overlay(alpha: torch.Tensor, mask: torch.Tensor, image: Optional[torch.T
     return out
 
 
+MESH_COLOUR = (0.65, 0.74, 0.86)       # the light blue SMPL fits are usually shown in
+SIDE_GREY = 0.25                        # background of the side view
+_ADJACENCY, _DEVICE_MESH = {}, {}
+
+
+def _faces_np(faces) -> np.ndarray:
+    if torch.is_tensor(faces):
+        faces = faces.detach().cpu().numpy()
+    faces = np.ascontiguousarray(np.asarray(faces))
+    if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] < 1 or not np.issubdtype(faces.dtype, np.integer):
+        raise ValueError(f'faces: expected an integer array (F,3), got {faces.dtype} {faces.shape}')
+    return faces
+
+
+def vertex_face_adjacency(faces, n_verts: int):
+    """The faces at every vertex in CSR form: (adj_offset int32 [n_verts + 1], adj_face int32 [3 F]); the faces of vertex v are
+    adj_face[adj_offset[v]:adj_offset[v + 1]] in ascending face index; a vertex no face names has an empty list.  Cached per faces
+    array (by content)."""
+    faces = _faces_np(faces)
+    n_verts = int(n_verts)
+    key = (hashlib.sha1(faces.astype(np.int64).tobytes()).hexdigest(), faces.shape[0], n_verts)
+    if key not in _ADJACENCY:
+        if n_verts < 1 or faces.min() < 0 or faces.max() >= n_verts:
+            raise ValueError(f'faces: vertex indices outside [0, {n_verts})')
+        flat = faces.reshape(-1).astype(np.int64)
+        order = np.argsort(flat, kind='stable')                 # stable: within a vertex the corners stay in face order
+        offset = np.zeros(n_verts + 1, dtype=np.int64)
+        np.cumsum(np.bincount(flat, minlength=n_verts), out=offset[1:])
+        _ADJACENCY[key] = (offset.astype(np.int32), (order // 3).astype(np.int32))
+    return _ADJACENCY[key]
+
+
+def _device_mesh(faces, n_verts: int, device):
+    """(faces, adj_offset, adj_face) as int32 tensors on `device`, uploaded once per faces array and device"""
+    faces = _faces_np(faces)
+    offset, adj = vertex_face_adjacency(faces, n_verts)
+    key = (hashlib.sha1(faces.astype(np.int64).tobytes()).hexdigest(), faces.shape[0], int(n_verts), str(torch.device(device)))
+    if key not in _DEVICE_MESH:
+        _DEVICE_MESH[key] = tuple(torch.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(device) for a in (faces, offset, adj))
+    return _DEVICE_MESH[key]
+
+
+def _verts(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dim() != 3 or t.shape[2] != 3 or t.shape[1] < 1 or t.dtype != torch.float32 or not t.is_cuda:
+        raise ValueError(f'{name}: expected a float32 device tensor (B,V,3), got {tuple(t.shape)} {t.dtype} on {t.device}')
+    return t.contiguous()
+
+
+def vertex_normals(verts: torch.Tensor, faces) -> torch.Tensor:
+    """pytorch3d's verts_normals_packed per pose: verts (B,V,3), faces (F,3) -> unit normals (B,V,3), the area-weighted sum of the
+    face normals at each vertex (summed in ascending face index: reproducible); exactly zero at a vertex without faces"""
+    verts = _verts(verts, 'verts')
+    B, V, _ = verts.shape
+    f_dev, off_dev, adj_dev = _device_mesh(faces, V, verts.device)
+    normals = torch.empty_like(verts)
+    _lib.check(_lib.load().jrr_vertex_normals(_lib.ptr(verts), _lib.ptr(f_dev), _lib.ptr(off_dev), _lib.ptr(adj_dev), B, V, f_dev.shape[0],
+                                              _lib.ptr(normals), _lib.stream_ptr(verts.device)), 'vertex_normals')
+    return normals
+
+
+def mesh_shade(verts: torch.Tensor, cam: torch.Tensor, pix_to_face: torch.Tensor, faces, normals: Optional[torch.Tensor] = None,
+               image: Optional[torch.Tensor] = None, normalize=None, colour=MESH_COLOUR, opacity: float = 1.0, ambient: float = 0.3,
+               light=(0.0, 0.0, -1.0), out: Optional[torch.Tensor] = None, want_depth: bool = False, want_normals: bool = False,
+               background: float = 0.0, status: Optional[torch.Tensor] = None):
+    """The shaded mesh behind a pix_to_face map (engine.silhouette_pix_to_face of a render of `verts`, `cam`): uint8 (B,S,S,3).
+    verts (B,V,3) in SMPL space, cam (B,3), pix_to_face (B,S,S) int32, faces (F,3); normals (B,V,3) default to vertex_normals(verts,
+    faces).  image (B,3,S,S) / normalize = (mean, std) are the background as in fit_overlay, `background` the grey without an image.
+    colour: base colour in [0, 1]; light: direction in view space (normalised here; default the headlight), two-sided.
+    `out`: a caller-owned contiguous uint8 (B,S,S,3).  `status`: a caller-zeroed int32 tensor of one element; bit 0 = a face or vertex
+    index outside the mesh, bit 1 = a degenerate face (both draw background).  With want_depth / want_normals the return value is
+    (rgb, depth (B,S,S) or None, normal (B,S,S,3) or None): interpolated view depth (-1 on background) and unit view-space normal."""
+    verts = _verts(verts, 'verts')
+    B, V, _ = verts.shape
+    dev = verts.device
+    if not torch.is_tensor(pix_to_face) or pix_to_face.dim() != 3 or pix_to_face.shape[0] != B or pix_to_face.shape[1] != pix_to_face.shape[2] \
+            or pix_to_face.dtype != torch.int32 or pix_to_face.device != dev:
+        raise ValueError(f'pix_to_face: expected int32 (B,S,S) with B = {B} on {dev}')
+    S = int(pix_to_face.shape[1])
+    if S % 4 or not 4 <= S <= 256:
+        raise ValueError(f'mesh_shade: image size {S}: a multiple of 4, at most 256')
+    pix_to_face = pix_to_face.contiguous()
+    if tuple(cam.shape) != (B, 3) or cam.dtype != torch.float32 or cam.device != dev:
+        raise ValueError(f'cam: expected float32 {(B, 3)} on {dev}, got {tuple(cam.shape)} {cam.dtype} on {cam.device}')
+    cam = cam.contiguous()
+    if normals is None:
+        normals = vertex_normals(verts, faces)
+    elif tuple(normals.shape) != (B, V, 3) or normals.dtype != torch.float32 or normals.device != dev:
+        raise ValueError(f'normals: expected float32 {(B, V, 3)} on {dev}')
+    normals = normals.contiguous()
+    f_dev = _device_mesh(faces, V, dev)[0]
+    if image is not None:
+        if tuple(image.shape) != (B, 3, S, S) or image.dtype != torch.float32 or image.device != dev:
+            raise ValueError(f'image: expected float32 {(B, 3, S, S)} on {dev}, got {tuple(image.shape)} {image.dtype} on {image.device}')
+        image = image.contiguous()
+    mean = std = None
+    if normalize is not None:
+        if image is None:
+            raise ValueError('mesh_shade: normalize without an image')
+        mean = torch.tensor(normalize[0], dtype=torch.float32, device=dev)
+        std = torch.tensor(normalize[1], dtype=torch.float32, device=dev)
+        if mean.shape != (3,) or std.shape != (3,):
+            raise ValueError('mesh_shade: normalize = (mean, std) of 3 values each')
+    colour = [float(c) for c in colour]
+    light = [float(x) for x in light]
+    norm = math.sqrt(sum(x * x for x in light)) if len(light) == 3 else 0.0
+    if len(colour) != 3 or not all(0.0 <= c <= 1.0 for c in colour):
+        raise ValueError('mesh_shade: colour = 3 values in [0, 1]')
+    if not (norm > 0.0 and math.isfinite(norm)):
+        raise ValueError('mesh_shade: light = a non-zero direction of 3 values')
+    if not (0.0 <= opacity <= 1.0 and 0.0 <= ambient <= 1.0):
+        raise ValueError('mesh_shade: opacity and ambient in [0, 1]')
+    if out is None:
+        out = torch.empty(B, S, S, 3, dtype=torch.uint8, device=dev)
+    elif tuple(out.shape) != (B, S, S, 3) or out.dtype != torch.uint8 or out.device != dev or not out.is_contiguous():
+        raise ValueError(f'out: expected a contiguous uint8 {(B, S, S, 3)} on {dev}')
+    if status is not None and (status.dtype != torch.int32 or status.numel() != 1 or status.device != dev):
+        raise ValueError(f'status: expected one int32 on {dev}')
+    depth = torch.empty(B, S, S, device=dev) if want_depth else None
+    nmap = torch.empty(B, S, S, 3, device=dev) if want_normals else None
+    c3, l3 = (ctypes.c_float * 3)(*colour), (ctypes.c_float * 3)(*[x / norm for x in light])
+    _lib.check(_lib.load().jrr_mesh_shade(_lib.ptr(verts), _lib.ptr(normals), _lib.ptr(f_dev), _lib.ptr(cam), _lib.ptr(pix_to_face),
+                                          _lib.ptr(image), _lib.ptr(mean), _lib.ptr(std), B, V, f_dev.shape[0], S, c3, float(opacity),
+                                          float(ambient), l3, float(background), _lib.ptr(out), _lib.ptr(depth), _lib.ptr(nmap),
+                                          _lib.ptr(status), _lib.stream_ptr(dev)), 'mesh_shade')
+    return (out, depth, nmap) if (want_depth or want_normals) else out
+
+
+def side_view(verts: torch.Tensor, cam: torch.Tensor, degrees: float = 90.0) -> torch.Tensor:
+    """The vertices that the SAME `cam` renders as the body seen from the side: verts (B,V,3) in SMPL space -> (B,V,3).  In view space
+    (x, y, z) -> (-2x + cx, -2y + cy, 2z + cz) each pose is turned by `degrees` about the vertical axis through its centroid, so its
+    distance from the camera stays what it was.  The view-space offsets from the centroid are d = (v - mean v) * (-2, -2, 2), exact in
+    floating point; the result is v + ((R - I) d) * (-1/2, -1/2, 1/2), the map back to SMPL space, exact as well -- the camera's
+    translation cancels.  A turn by 0 adds zeros: the identity bit for bit.  A torch op on the tensors' device; not differentiated
+    through by anything here."""
+    if verts.dim() != 3 or verts.shape[2] != 3 or not verts.is_floating_point():
+        raise ValueError(f'verts: expected a floating-point (B,V,3), got {tuple(verts.shape)} {verts.dtype}')
+    if tuple(cam.shape) != (verts.shape[0], 3) or cam.device != verts.device:
+        raise ValueError(f'cam: expected {(verts.shape[0], 3)} on {verts.device}, got {tuple(cam.shape)} on {cam.device}')
+    quarter = float(degrees) / 90.0
+    if quarter == round(quarter):                                 # whole quarter turns: exact cosine and sine
+        c, s = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(round(quarter)) % 4]
+    else:
+        c, s = math.cos(math.radians(degrees)), math.sin(math.radians(degrees))
+    flip = verts.new_tensor([-2.0, -2.0, 2.0])
+    d = (verts - verts.mean(dim=1, keepdim=True)) * flip
+    turned = torch.stack([(c - 1.0) * d[..., 0] + s * d[..., 2], torch.zeros_like(d[..., 1]), (c - 1.0) * d[..., 2] - s * d[..., 0]], dim=-1)
+    return verts + turned * verts.new_tensor([-0.5, -0.5, 0.5])
+
+
 def _chunk(tag: bytes, data: bytes) -> bytes:
     return struct.pack('>I', len(data)) + tag + data + struct.pack('>I', zlib.crc32(tag + data) & 0xffffffff)
 
@@ -123,10 +278,12 @@ class FitReport:
     """`--fit_report DIR` of one run (scripts/optimize.py:204-218 before the loop, :268-274 after it, viz() at :28-74): per outer batch and
     shard the mesh is rendered with the poses as they stand, compared with the batch's mask, the regressed joints are projected.
     `before` and `after` each run a forward of their own on the batch's engine, so each sits where no later call reads the engine's
-    most recent forward.  They take the driver's batch object: its engine, mask, poses, shard bounds and global batch."""
+    most recent forward.  They take the driver's batch object: its engine, mask, poses, shard bounds and global batch.
+    `mesh` (`--fit_report_mesh`): each render also reads the rasteriser's pix_to_face and rasterises the body once more turned by 90
+    degrees (side_view), on the same engine and at the same place; the first poses of both views are written as one shaded picture."""
 
-    def __init__(self, directory: str, n_images: int):
-        self.directory, self.n_images = directory, int(n_images)
+    def __init__(self, directory: str, n_images: int, mesh: bool = False):
+        self.directory, self.n_images, self.mesh = directory, int(n_images), bool(mesh)
         self.last = None           # the run's `fit_report` return value: per-pose IoU of the last batch's shard
 
     def before(self, b):
@@ -135,7 +292,7 @@ class FitReport:
             self.gt_j2d = b.full['gt_j2d'][b.lo:b.hi].to(b.sil_mask.device).float().contiguous()
         self.n = max(0, min(self.n_images, b.eng.batch))
         self.sums = torch.zeros(4, dtype=torch.float64, device=b.sil_mask.device)     # IoU before / after, pixel error before / after
-        self.iou, self.kept = {}, {}
+        self.iou, self.kept, self.kept_mesh = {}, {}, {}
         self._render('before', b)
 
     def after(self, b):
@@ -154,6 +311,13 @@ class FitReport:
         k = ('before', 'after').index(when)
         joints, verts = b.eng.find_joints_forward(b.betas, x6d=b.x6d, return_verts=True)
         alpha = b.eng.silhouette_forward(verts, b.cam)
+        if self.mesh:              # nothing below reads the engine's rasterisation: the second one may overwrite it
+            n = self.n
+            front = b.eng.silhouette_pix_to_face()
+            turned = side_view(verts, b.cam)
+            b.eng.silhouette_forward(turned, b.cam)
+            side = b.eng.silhouette_pix_to_face()
+            self.kept_mesh[when] = (b.cam[:n].clone(), verts[:n].clone(), front[:n].clone(), turned[:n].clone(), side[:n].clone())
         j2d = _engine.project_joints(joints, b.cam)
         self.iou[when] = iou_from_counts(silhouette_compare(alpha, b.sil_mask))
         self.sums[k] = self.iou[when].sum()
@@ -178,3 +342,11 @@ class FitReport:
                               joints2d=sets[when]).cpu().numpy()
             for i in range(n):
                 write_png(os.path.join(self.directory, f'b{b.it:04d}_p{b.lo + i:05d}_{when}.png'), rgb[i])
+            if self.mesh:          # (S, 2S, 3): the front view over the crop (or black), the side view over grey
+                cam, verts, front, turned, side = self.kept_mesh[when]
+                faces = b.eng.model.faces
+                left = mesh_shade(verts, cam, front, faces, image=image, normalize=SPIN_NORMALIZE if image is not None else None)
+                right = mesh_shade(turned, cam, side, faces, background=SIDE_GREY)
+                both = torch.cat([left, right], dim=2).cpu().numpy()
+                for i in range(n):
+                    write_png(os.path.join(self.directory, f'b{b.it:04d}_p{b.lo + i:05d}_{when}_mesh.png'), both[i])
