@@ -98,6 +98,15 @@ enum {
   JRR_EXPORT_STATUS_TWICE = 2  /* status bit 1: the target row's marker was already set (a sample exported twice); overwritten */
 };
 
+/* jrr_pose_smooth / jrr_pose_jitter: the time-axis filter over the refined-pose table. */
+enum {
+  JRR_SMOOTH_MAX_RADIUS = 16,       /* the window is 2 radius + 1 positions; weights has radius + 1 entries */
+  JRR_SMOOTH_TILE = 32,             /* positions per workgroup (a result never depends on where its position falls in a tile) */
+  JRR_SMOOTH_MAX_POSITIONS = 1 << 30,
+  JRR_SMOOTH_STATUS_INDEX = 1,      /* status bit 0: an entry of order outside [0, n_rows); that position is skipped */
+  JRR_SMOOTH_STATUS_MARKER = 2      /* status bit 1: a listed row whose marker is not 1.0f; that position is skipped */
+};
+
 /* row of the evaluation-report table (jrr_eval_accumulate): JRR_EVAL_ACC_ROW int64 per group, offsets in int64, then a trailer of
  * JRR_EVAL_ACC_TRAILER int64 behind the last row.  Layout version 1. */
 enum {
@@ -327,6 +336,43 @@ int jrr_rotmat_to_axis_angle(const float* R_dev, float* aa_dev, int n, void* str
  * The caller zero-fills the table once; rows nobody wrote keep marker 0.  Touches no engine.                                  */
 int jrr_pose_export(const float* x6d_dev, const float* betas_dev, const float* cam_dev, const float* extra_dev, int n_extra,
                     const int64_t* index_dev, float* table_dev, int64_t n_rows, int32_t* status_dev, int batch, void* stream);
+
+/* The refined poses of a table along the time axis (`--smooth_refined`).  table_dev (n_rows, JRR_EXPORT_ROW) is a table
+ * jrr_pose_export wrote; it is only read.  order_dev (m) int32 lists table rows in time order and run_dev (m) int32 gives each
+ * position's run of consecutive frames (the host forms both from the frame paths).  Position p's NEIGHBOURS are the offsets
+ * k in [-radius, radius] with 0 <= p + k < m, run[p + k] == run[p] and position p + k not skipped (below).
+ *   unit quaternion q of a joint of a row: R = rot6d_to_rotmat of the row's six values (scripts/utils.py:190-204, the loop's own map);
+ *     Shepperd's unnormalised quaternion of R -- of tr, R00, R11, R22 the largest (ties in that order) selects
+ *       (w,x,y,z) = (1+tr, R21-R12, R02-R20, R10-R01) | (R21-R12, 1+R00-R11-R22, R01+R10, R02+R20) | the two cyclic analogues,
+ *     as in jrr_rotmat_to_axis_angle --; divided by its norm sqrt(w w + x x + y y + z z).  No canonical sign is chosen.
+ *   jrr_pose_smooth, per position p and joint, with q_0 the centre's own quaternion and weights_dev[k] = (float)exp(-k k / (2 sigma^2))
+ *   (the caller rounds them once; the kernel calls no exp):
+ *     s = sum over the neighbours k, ascending from -radius, of weights[|k|] * (q_k . q_0 < 0 ? -q_k : q_k);
+ *     s . q_0 >= weights[0] > 0, so the sum never degenerates;  q~ = s / |s|;
+ *     x6d_out[p][joint] = the first two columns of R(q~) in the 6-D layout (x[0], x[2], x[4] column 0 =
+ *       (1 - 2(yy + zz), 2(xy + wz), 2(xz - wy));  x[1], x[3], x[5] column 1 = (2(xy - wz), 1 - 2(xx + zz), 2(yz + wx)));
+ *     delta_deg[p] = (sum over the 24 joints, in joint order, of 2 atan2(|e_xyz|, |e_w|) 180 / pi) / 24 with e = conj(q_0) (x) q~,
+ *       conj(a) (x) b = (a.b,  a_w b_v - b_w a_v - a_v x b_v);
+ *     betas_out[p], cam_out[p] = (sum_k weights[|k|] v_k) / (sum_k weights[|k|]) over the same neighbours in the same order, both
+ *       sums starting from their first term.
+ *   Every operation after rot6d_to_rotmat is rounded once, in the order written (no contraction).  With radius 0, or a run of
+ *   length 1, betas_out and cam_out reproduce the row bit for bit and x6d_out holds the orthonormalised columns of the input.
+ *   A non-finite row changes exactly the positions whose window holds it.
+ *   jrr_pose_jitter, per position p whose neighbours p - 1 and p + 1 both exist: per joint d1 = conj(q_{p-1}) (x) q_p,
+ *     d2 = conj(q_p) (x) q_{p+1}, e = conj(d1) (x) d2; jitter_deg[p] = the mean over the joints (summed in joint order) of the angle of
+ *     e as above: degrees per sampled frame^2, zero for a constant angular velocity about a fixed axis.  NaN at every other position.
+ *   begin, count   the positions [begin, begin + count) the call computes; the output arrays are indexed by position (m rows) and the
+ *                  other rows are not touched.  A result depends on its window alone: not on m, the range or the launch's tiling.
+ *   x6d_out_dev (m,24,6) 16-byte aligned, betas_out_dev (m,10), cam_out_dev (m,3), delta_deg_dev (m), jitter_deg_dev (m)
+ *   status_dev     one int32 the CALLER zeroes and reads when it next synchronises: bit 0 (JRR_SMOOTH_STATUS_INDEX) an entry of order
+ *                  outside [0, n_rows); bit 1 (JRR_SMOOTH_STATUS_MARKER) a listed row whose marker is not 1.0f.  Such a position is
+ *                  skipped -- it is nobody's neighbour and its own outputs are NaN --; every other position is unaffected.
+ * 0 <= radius <= JRR_SMOOTH_MAX_RADIUS.  Touches no engine.  No reference counterpart.                                          */
+int jrr_pose_smooth(const float* table_dev, int64_t n_rows, const int32_t* order_dev, const int32_t* run_dev, int m,
+                    const float* weights_dev, int radius, int begin, int count, float* x6d_out_dev, float* betas_out_dev,
+                    float* cam_out_dev, float* delta_deg_dev, int32_t* status_dev, void* stream);
+int jrr_pose_jitter(const float* table_dev, int64_t n_rows, const int32_t* order_dev, const int32_t* run_dev, int m, int begin, int count,
+                    float* jitter_deg_dev, int32_t* status_dev, void* stream);
 
 /* find_joints, scripts/utils.py:85-103 (SMPL forward + J_regressor contraction).
  * Exactly one of x6d_dev (B,24,6) / R_dev (B,24,3,3) is non-NULL.  joints_dev (B,17,3).

@@ -66,7 +66,15 @@ def build_parser() -> argparse.ArgumentParser:
                              'has_refined and the per-sample errors, rows at their dataset indices, and DIR/meta.json (refined.py)')
     parser.add_argument('--init_refined', type=str, default=None, metavar='DIR',
                         help='with --data_root: samples that a --save_refined table in DIR holds start from its pose6d / shape / cam '
-                             'instead of the dataset\'s initial values')
+                             'instead of the dataset\'s initial values; a path that ends in .npz reads that file of its directory '
+                             '(DIR/refined_smooth.npz: the table --smooth_refined wrote)')
+    parser.add_argument('--smooth_refined', type=str, default=None, metavar='DIR',
+                        help='with --data_root: filter the --save_refined table of DIR along time, per run of consecutive frames of one '
+                             'camera (the frame paths of images.pkl), write DIR/refined_smooth.npz with the jitter before and after and the '
+                             'joint error of both, print one line and exit (refined.smooth)')
+    parser.add_argument('--smooth_sigma', type=float, default=2.0, help='--smooth_refined: standard deviation of the Gaussian, in sampled frames')
+    parser.add_argument('--smooth_radius', type=int, default=None,
+                        help='--smooth_refined: the window reaches this many frames to either side, 0 .. 16 (default: min(16, ceil(3 sigma)))')
     parser.add_argument('--eval_report', type=str, default=None, metavar='DIR',
                         help='evaluation report: DIR/eval.json and DIR/eval.md with MPJPE / PA-MPJPE per group and per joint, PCK and AUC, '
                              'initial against retrained regressor (eval_report.py); the printed lines of scripts/test.py:125-138 stay as they are')

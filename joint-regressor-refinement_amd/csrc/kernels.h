@@ -258,6 +258,14 @@ int launch_rotmat_log(const float* R, float* aa, int n, hipStream_t s);
 int launch_pose_export(const float* x6d, const float* betas, const float* cam, const float* extra, int n_extra, const int64_t* index,
                        float* table, int64_t n_rows, int32_t* status, int B, hipStream_t s);
 
+// smooth.hip
+// the time-axis filter over a refined-pose table and the jitter of it (include/jrr.h, jrr_pose_smooth / jrr_pose_jitter); positions
+// [begin, begin + count) of the m listed ones, 0 <= radius <= 16, x6d_out 16-byte aligned
+int launch_pose_smooth(const float* table, int64_t n_rows, const int32_t* order, const int32_t* run, int M, const float* weights, int radius,
+                       int begin, int count, float* x6d_out, float* betas_out, float* cam_out, float* delta_deg, int32_t* status, hipStream_t s);
+int launch_pose_jitter(const float* table, int64_t n_rows, const int32_t* order, const int32_t* run, int M, int begin, int count,
+                       float* jitter_deg, int32_t* status, hipStream_t s);
+
 // disc.hip
 int launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t s, int ldin = 0, int ldout = 0);
 constexpr int CONV_IMAGE_FLOATS = 4224;     // LDS parameter image of the per-joint MLP kernels (disc.hip CL_*), rounded up

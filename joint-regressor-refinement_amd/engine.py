@@ -584,6 +584,53 @@ def pose_export(x6d, betas, cam, index, table, status, extra=None) -> None:
                               stream_ptr(x6d.device)), 'pose_export')
 
 
+SMOOTH_MAX_RADIUS = 16        # include/jrr.h: JRR_SMOOTH_MAX_RADIUS
+
+
+def _smooth_lists(table, order, run, status, begin, count):
+    M = int(order.shape[0])
+    assert table.dim() == 2 and table.shape[1] == 240 and table.dtype == torch.float32 and table.is_contiguous()
+    assert order.shape == (M,) and run.shape == (M,) and order.dtype == torch.int32 and run.dtype == torch.int32
+    assert order.is_contiguous() and run.is_contiguous() and status.is_contiguous() and status.dtype == torch.int32
+    assert all(t.device == table.device for t in (order, run, status))
+    begin = int(begin)
+    count = M - begin if count is None else int(count)
+    return M, begin, count
+
+
+def pose_smooth(table, order, run, weights, status, begin: int = 0, count: Optional[int] = None, out=None):
+    """jrr_pose_smooth: the Gaussian filter along `order` (M, int32: table rows in time order) within the runs `run` (M, int32) of a
+    refined-pose `table` (n_rows,240), which is only read; `weights` (radius+1,) float32 on the device.  Computes positions
+    [begin, begin + count) into `out` = (x6d (M,24,6), betas (M,10), cam (M,3), delta_deg (M,)) -- allocated, NaN-filled, when None --
+    and returns it; `status` (1,) int32 collects the error bits"""
+    lib = _lib.load()
+    M, begin, count = _smooth_lists(table, order, run, status, begin, count)
+    dev = table.device
+    assert weights.dim() == 1 and weights.dtype == torch.float32 and weights.is_contiguous() and weights.device == dev
+    radius = int(weights.shape[0]) - 1
+    if out is None:
+        out = tuple(torch.full(shape, float('nan'), device=dev) for shape in ((M, NUM_JOINTS, 6), (M, 10), (M, 3), (M,)))
+    x6d, betas, cam, delta = out
+    assert x6d.shape == (M, NUM_JOINTS, 6) and betas.shape == (M, 10) and cam.shape == (M, 3) and delta.shape == (M,)
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in out)
+    check(lib.jrr_pose_smooth(ptr(table), table.shape[0], ptr(order), ptr(run), M, ptr(weights), radius, begin, count, ptr(x6d), ptr(betas),
+                              ptr(cam), ptr(delta), ptr(status), stream_ptr(dev)), 'pose_smooth')
+    return out
+
+
+def pose_jitter(table, order, run, status, begin: int = 0, count: Optional[int] = None, out=None) -> torch.Tensor:
+    """jrr_pose_jitter: jitter_deg (M,) of positions [begin, begin + count) of `order` -- the mean over the joints of the angle of the
+    rotations' second difference along the run, NaN where a position lacks a neighbour"""
+    lib = _lib.load()
+    M, begin, count = _smooth_lists(table, order, run, status, begin, count)
+    if out is None:
+        out = torch.full((M,), float('nan'), device=table.device)
+    assert out.shape == (M,) and out.dtype == torch.float32 and out.is_contiguous() and out.device == table.device
+    check(lib.jrr_pose_jitter(ptr(table), table.shape[0], ptr(order), ptr(run), M, begin, count, ptr(out), ptr(status),
+                              stream_ptr(table.device)), 'pose_jitter')
+    return out
+
+
 def evaluate_joints(pred_j3d: torch.Tensor, target_j3d_mm: torch.Tensor):
     """the per-joint distances behind `evaluate`: err_j, err_pa_j (B,17) in metres (jrr_evaluate_joints)"""
     lib = _lib.load()

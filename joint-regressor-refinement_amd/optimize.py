@@ -171,7 +171,7 @@ class Run:
         """:132-139; every rank draws the same global batches"""
         if not args.data_root:
             return batches.synthetic_batches(self.smpl.model_np, self.J_np, args.batch_size, args.synthetic_batches, args.seed)
-        init_refined = jrefined.load(args.init_refined) if args.init_refined else None
+        init_refined = jrefined.load_path(args.init_refined) if args.init_refined else None
         return batches.dataset_batches(args.data_root, args.batch_size, args.seed, self.device, image_masks=bool(args.image_masks),
                                        with_index=with_index, init_refined=init_refined)
 

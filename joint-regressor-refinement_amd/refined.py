@@ -10,12 +10,17 @@ the sign bit of a zero -- the only bits `--init_refined` does not get back), the
 `finish`, `load` and the validation work on CPU tensors with a gloo group as well.
 `RefinedExport` is `--save_refined` as the driver sees it: built once, called where a batch is uploaded, where its joints are scored, after
 its J step and at the end of the run.
+`smooth()` is `--smooth_refined DIR`: the table along the time axis.  `sequence_runs` orders the refined rows by (camera sequence, frame)
+from the frame paths and cuts them into runs of consecutive frames; k_pose_jitter and k_pose_smooth (csrc/smooth.hip) measure and filter
+the rotations per run, the existing export writes the filtered records into a copy of the table, and one read-back later
+`refined_smooth.npz` holds every array of `refined.npz` plus the jitter before and after.  `refined.npz` is never rewritten.
 """
 from __future__ import annotations
 
 import json
 import os
-from typing import Dict, Optional
+import re
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -142,22 +147,250 @@ def unpack(table: np.ndarray, status: int = 0) -> Dict[str, np.ndarray]:
     return out
 
 
-def load(directory: str, n: Optional[int] = None) -> Dict[str, np.ndarray]:
-    """the arrays of directory/refined.npz (+ 'meta': the dict of meta.json); checks the layout version, the shapes and, when given,
-    that the table has `n` rows"""
+def pack(arrays: Dict[str, np.ndarray]) -> np.ndarray:
+    """the arrays of refined.npz -> the (N,240) float32 rows they were unpacked from"""
+    N = arrays['has_refined'].shape[0]
+    table = np.zeros((N, ROW), dtype=np.float32)
+    table[:, POSE:POSE6D] = arrays['pose']
+    table[:, POSE6D:BETAS] = arrays['pose6d'].reshape(N, BETAS - POSE6D)
+    table[:, BETAS:CAM], table[:, CAM:MARKER], table[:, MARKER] = arrays['shape'], arrays['cam'], arrays['has_refined']
+    for k, name in enumerate(EXTRA_NAMES):
+        table[:, EXTRA + k] = arrays[name]
+    return table
+
+
+def load(directory: str, n: Optional[int] = None, name: str = 'refined.npz') -> Dict[str, np.ndarray]:
+    """the arrays of directory/refined.npz -- or of `name`, e.g. SMOOTH_NAME -- (+ 'meta': the dict of meta.json); checks the layout
+    version, the shapes and, when given, that the table has `n` rows"""
     with open(os.path.join(directory, 'meta.json')) as f:
         meta = json.load(f)
     if meta.get('layout_version') != LAYOUT_VERSION:
         raise ValueError(f'{directory}: row layout version {meta.get("layout_version")!r}, this build reads version {LAYOUT_VERSION}')
-    with np.load(os.path.join(directory, 'refined.npz'), allow_pickle=False) as z:
+    with np.load(os.path.join(directory, name), allow_pickle=False) as z:
         out = {k: z[k] for k in z.files}
     N = out['has_refined'].shape[0]
     shapes = {'pose': (N, 72), 'pose6d': (N, 24, 6), 'shape': (N, 10), 'cam': (N, 3), 'has_refined': (N,), 'mpjpe_mm': (N,), 'pampjpe_mm': (N,)}
     shapes.update({name: (N,) for name in EXTRA_NAMES})
     for k, shp in shapes.items():
         if k not in out or out[k].shape != shp:
-            raise ValueError(f'{directory}/refined.npz: {k} should be {shp}, is {out[k].shape if k in out else "missing"}')
+            raise ValueError(f'{directory}/{name}: {k} should be {shp}, is {out[k].shape if k in out else "missing"}')
     if n is not None and N != int(n):
         raise ValueError(f'{directory}: the table holds {N} samples, {int(n)} expected')
     out['meta'] = meta
+    return out
+
+
+def load_path(path: str, n: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """`--init_refined PATH`: a directory reads its refined.npz; a path that ends in `.npz` reads that file of its directory"""
+    if str(path).endswith('.npz'):
+        return load(os.path.dirname(path) or '.', n, name=os.path.basename(path))
+    return load(path, n)
+
+
+# ---- along the time axis (`--smooth_refined`) -------------------------------------------------------------------------------
+SMOOTH_NAME = 'refined_smooth.npz'
+SMOOTH_MAX_RADIUS = 16        # include/jrr.h: JRR_SMOOTH_MAX_RADIUS
+SMOOTH_STATUS_BITS = {1: 'bit 0: an entry of the time order lies outside the table', 2: 'bit 1: a listed row holds no refined pose'}
+_FRAME = re.compile(r'^img_(\d+)')
+
+
+def sequence_key(path) -> Tuple[Optional[str], int]:
+    """(sequence key, frame number) of a frame path `.../<action>/imageSequence/<camera>/img_%06d.jpg` (scripts/data.py:301): the key is
+    everything up to and including the camera directory, the frame the integer behind `img_`.  (None, -1) for a path without
+    `imageSequence`, without a camera directory below it or without a parsable frame number: such a frame is a sequence of its own."""
+    parts = re.split(r'[\\/]+', str(path)) if path else []
+    if 'imageSequence' not in parts:
+        return None, -1
+    at = parts.index('imageSequence')
+    m = _FRAME.match(parts[-1])
+    if at + 2 >= len(parts) or m is None:
+        return None, -1
+    return '/'.join(parts[:at + 2]), int(m.group(1))
+
+
+def sequence_runs(paths, has_refined) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(order (M,) int32, run (M,) int32, frame (M,) int64): the table rows with has_refined == 1 in time order -- sorted by (sequence
+    key, frame, dataset index) -- and their runs of consecutive frames.  Within a key the stride is the smallest positive frame
+    difference between neighbours of that sort; a run is a maximal stretch whose consecutive differences all equal it, so a gap, a
+    duplicate frame and an unrefined frame each end the run.  Run ids start at 0 and never decrease.  `paths`: one frame path per row,
+    or a pair (keys, frames) of arrays; a row without key (sequence_key; a negative frame in the second form) is a run of length 1
+    and sorts behind the keyed rows."""
+    has = np.asarray(has_refined).astype(bool)
+    N = has.shape[0]
+    if isinstance(paths, tuple) and len(paths) == 2 and len(paths[0]) == N and not isinstance(paths[0], str):
+        keys, frames = list(np.asarray(paths[0]).tolist()), np.asarray(paths[1]).astype(np.int64)
+        keys = [None if f < 0 else k for k, f in zip(keys, frames)]
+    else:
+        parsed = [sequence_key(p) for p in paths]
+        keys, frames = [k for k, _ in parsed], np.array([f for _, f in parsed], dtype=np.int64).reshape(-1)
+    if len(keys) != N or frames.shape != (N,):
+        raise ValueError(f'sequence_runs: {len(keys)} paths for a table of {N} rows')
+    names = sorted({k for k in keys if k is not None})
+    lut = {k: i for i, k in enumerate(names)}
+    # a row without key gets a key of its own behind every named one, in dataset order
+    kid = np.array([lut[k] if k is not None else len(names) + i for i, k in enumerate(keys)], dtype=np.int64).reshape(-1)
+    frames = np.where(kid >= len(names), -1, frames)
+    idx = np.nonzero(has)[0]
+    k, f = kid[idx], frames[idx]
+    o = np.lexsort((idx, f, k))
+    idx, k, f = idx[o], k[o], f[o]
+    if idx.size == 0:
+        return np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int64)
+    same, d = k[1:] == k[:-1], f[1:] - f[:-1]
+    stride = np.full(len(names) + N, np.iinfo(np.int64).max, dtype=np.int64)
+    pos = same & (d > 0)
+    np.minimum.at(stride, k[1:][pos], d[pos])
+    cont = pos & (d == stride[k[1:]])
+    run = np.concatenate([[0], np.cumsum(~cont)])
+    return idx.astype(np.int32), run.astype(np.int32), f.astype(np.int64)
+
+
+def smooth_weights(sigma: float, radius: Optional[int] = None) -> np.ndarray:
+    """weights[k] = float32(exp(-k^2 / (2 sigma^2))), k = 0 .. radius, evaluated in float64 and rounded once; radius None:
+    min(16, ceil(3 sigma))"""
+    sigma = float(sigma)
+    if not (sigma > 0 and np.isfinite(sigma)):
+        raise ValueError(f'smooth: sigma {sigma}: a positive number')
+    radius = min(SMOOTH_MAX_RADIUS, int(np.ceil(3 * sigma))) if radius is None else int(radius)
+    if not 0 <= radius <= SMOOTH_MAX_RADIUS:
+        raise ValueError(f'smooth: radius {radius}: 0 .. {SMOOTH_MAX_RADIUS}')
+    k = np.arange(radius + 1, dtype=np.float64)
+    return np.exp(-(k * k) / (2.0 * sigma * sigma)).astype(np.float32)
+
+
+def _nanmean(x) -> Optional[float]:
+    x = np.asarray(x, dtype=np.float64)
+    x = x[~np.isnan(x)]
+    return float(x.mean()) if x.size else None
+
+
+def smooth(directory: str, paths, sigma: float = 2.0, radius: Optional[int] = None, device=None, rescore=None) -> Dict[str, np.ndarray]:
+    """`--smooth_refined DIR`: the table of DIR/refined.npz filtered along time.  Uploads the table, measures its jitter
+    (jrr_pose_jitter), filters it (jrr_pose_smooth), writes the filtered records into a COPY of the table with the existing pose_export
+    operator -- so the smoothed `pose` is the same log map of the same 6-D map as in refined.npz --, measures the copy's jitter and
+    reads everything back once.  Writes DIR/refined_smooth.npz (every array of refined.npz + jitter_deg_raw / jitter_deg /
+    smooth_delta_deg, NaN outside the time order, and run_id / run_len / frame, -1 there) and adds `smooth` to DIR/meta.json;
+    refined.npz is not rewritten.  `paths` as sequence_runs takes them.  `rescore(raw, smoothed) -> (arrays, numbers)`: more
+    per-sample arrays for the file and numbers for meta.json, computed before the one write.  Returns the arrays."""
+    from . import engine as _engine
+    raw = load(directory)
+    meta = raw.pop('meta')
+    N = raw['has_refined'].shape[0]
+    order, run, frame = sequence_runs(paths, raw['has_refined'])
+    weights = smooth_weights(sigma, radius)
+    M, rad = order.shape[0], weights.shape[0] - 1
+    device = torch.device(args.device if device is None else device)
+    host_table = pack(raw)
+    if M:
+        table = torch.from_numpy(host_table).to(device)
+        d_order, d_run, d_w = (torch.from_numpy(a).to(device) for a in (order, run, weights))
+        status, status_x = torch.zeros(1, dtype=torch.int32, device=device), torch.zeros(1, dtype=torch.int32, device=device)
+        jit_raw = _engine.pose_jitter(table, d_order, d_run, status)
+        x6d, betas, cam, delta = _engine.pose_smooth(table, d_order, d_run, d_w, status)
+        rows = d_order.long()
+        copy = table.clone()
+        copy[rows, MARKER] = 0                                     # the export claims the rows it writes
+        _engine.pose_export(x6d, betas, cam, rows, copy, status_x, extra=table[rows, EXTRA:EXTRA + len(EXTRA_NAMES)].contiguous())
+        jit = _engine.pose_jitter(copy, d_order, d_run, status)
+        flat = torch.cat([copy.reshape(-1), jit_raw, jit, delta, status.float(), status_x.float()]).cpu().numpy()     # the one read-back
+        st, st_x = int(flat[-2]), int(flat[-1])
+        if st:
+            raise RuntimeError('smooth: status ' + '; '.join(msg for bit, msg in SMOOTH_STATUS_BITS.items() if st & bit))
+        host_table = flat[:N * ROW].reshape(N, ROW)
+        per_pos = flat[N * ROW:N * ROW + 3 * M].reshape(3, M)
+    else:
+        st_x, per_pos = 0, np.zeros((3, 0), dtype=np.float32)
+    out = unpack(host_table, status=st_x)
+    for k, name in enumerate(('jitter_deg_raw', 'jitter_deg', 'smooth_delta_deg')):
+        out[name] = np.full(N, np.nan, dtype=np.float32)
+        out[name][order] = per_pos[k]
+    n_runs = int(run[-1]) + 1 if M else 0
+    lengths = np.bincount(run, minlength=n_runs)
+    out['run_id'], out['run_len'], out['frame'] = np.full(N, -1, np.int32), np.full(N, -1, np.int32), np.full(N, -1, np.int64)
+    out['run_id'][order], out['run_len'][order], out['frame'][order] = run, lengths[run], frame
+    hist = np.bincount(lengths) if M else np.zeros(0, dtype=np.int64)
+    doc = {'sigma': float(sigma), 'radius': int(rad), 'positions': int(M), 'runs': n_runs,
+           'run_length_histogram': {str(n): int(c) for n, c in enumerate(hist) if c},
+           'jitter_deg_raw_mean': _nanmean(out['jitter_deg_raw']), 'jitter_deg_mean': _nanmean(out['jitter_deg']),
+           'smooth_delta_deg_mean': _nanmean(out['smooth_delta_deg'])}
+    if rescore is not None:
+        more, numbers = rescore(raw, out)
+        out.update(more)
+        doc.update(numbers)
+    np.savez(os.path.join(directory, SMOOTH_NAME), **out)
+    with open(os.path.join(directory, 'meta.json'), 'w') as f:
+        json.dump(dict(meta, smooth=doc), f, indent=1, sort_keys=True, default=str)
+    out['meta'] = dict(meta, smooth=doc)
+    return out
+
+
+def _rescore_fn(gt_j3d_mm: torch.Tensor, device):
+    """the joint error of the raw and the smoothed rows through the EXISTING operators -- SMPL, find_joints, jrr_evaluate_joints -- in
+    chunks of --batch_size under ONE regressor (--eval_j_regressor, else the initial one), the body as the driver resolves it"""
+    from . import checkpoint, engine as _engine, smpl_model, utils
+    from .smpl import SMPL
+
+    def rescore(raw, smoothed):
+        smpl = SMPL(args.smpl_dir, batch_size=1, allow_synthetic=args.synthetic or args.smpl_dir == 'SPIN/data/smpl').to(device)
+        J_np = smpl_model.default_h36m_regressor(args.j_regressor_init,
+                                                 allow_default=args.synthetic or args.j_regressor_init == 'SPIN/data/J_regressor_h36m.npy')
+        J_init = torch.from_numpy(J_np).float().to(device)
+        J = checkpoint.load_j_regressor(args.eval_j_regressor).float().to(device) if args.eval_j_regressor else J_init
+        mask = utils.find_j_reg_mask(J_init)
+        rows = np.nonzero(raw['has_refined'])[0]
+        N, bs = raw['has_refined'].shape[0], max(1, int(args.batch_size))
+        acc = torch.full((4, N), float('nan'), device=device)
+        engines: Dict[int, object] = {}
+        with torch.no_grad():
+            for a in range(0, rows.size, bs):
+                idx = torch.from_numpy(rows[a:a + bs])
+                B = int(idx.shape[0])
+                if B not in engines:
+                    engines[B] = _engine.RefineEngine(smpl.device_model, B)
+                    engines[B].set_j_regressor(J, mask)
+                gt = utils.move_pelvis(gt_j3d_mm[idx].to(device).float())
+                d_idx = idx.to(device)
+                for k, arrays in enumerate((raw, smoothed)):
+                    x6d = torch.from_numpy(arrays['pose6d'][rows[a:a + bs]]).to(device).float().contiguous()
+                    betas = torch.from_numpy(arrays['shape'][rows[a:a + bs]]).to(device).float().contiguous()
+                    joints = engines[B].find_joints_forward(betas, x6d=x6d)
+                    err_j, err_pa_j = _engine.evaluate_joints(joints.float().contiguous(), gt.contiguous())
+                    acc[2 * k, d_idx] = err_j.mean(1) * 1000
+                    acc[2 * k + 1, d_idx] = err_pa_j.mean(1) * 1000
+        host = acc.cpu().numpy()
+        names = ('mpjpe_eval_mm_raw', 'pampjpe_eval_mm_raw', 'mpjpe_eval_mm_smooth', 'pampjpe_eval_mm_smooth')
+        more = {name: host[k] for k, name in enumerate(names)}
+        numbers = {name + '_mean': _nanmean(host[k]) for k, name in enumerate(names)}
+        numbers['eval_j_regressor'] = args.eval_j_regressor or args.j_regressor_init
+        return more, numbers
+    return rescore
+
+
+def smooth_command(log=print) -> Optional[dict]:
+    """`python main.py --smooth_refined DIR --data_root ROOT [--smooth_sigma S] [--smooth_radius R]`: refined.smooth on the split the
+    table was written from, the frame paths from its images.pkl, plus the joint error of the raw and the smoothed rows.  One process:
+    under torchrun rank 0 works and the other ranks return.  Prints one summary line."""
+    from . import data as jdata
+    if jdist.env_rank_world()[0] != 0:                      # the command joins no process group: the launcher's rank decides
+        return None
+    if not args.data_root:
+        raise ValueError('--smooth_refined needs --data_root (the frame paths and the ground truth of the split the table was written from)')
+    location = jdata.split_location('validation', args.data_root)
+    paths = jdata.split_image_paths(location)
+    if paths is None:
+        raise FileNotFoundError(f'--smooth_refined: {os.path.join(location, "images.pkl")} is missing: the frame paths say which samples follow each other')
+    ds = jdata.data_set('validation', root=args.data_root)
+    n_table = load(args.smooth_refined)['has_refined'].shape[0]
+    if not (len(paths) == len(ds) == n_table):
+        raise ValueError(f'--smooth_refined: the table holds {n_table} samples, the split {len(ds)} with {len(paths)} frame paths')
+    device = torch.device(args.device)
+    torch.cuda.set_device(device)
+    out = smooth(args.smooth_refined, paths, sigma=args.smooth_sigma, radius=args.smooth_radius, device=device,
+                 rescore=_rescore_fn(ds.gt_j3d, device))
+    doc = out['meta']['smooth']
+    fmt = lambda v, spec='.4f': '-' if v is None else format(v, spec)
+    log(f'smoothed {doc["positions"]} poses in {doc["runs"]} runs (sigma {doc["sigma"]:g}, radius {doc["radius"]}): jitter '
+        f'{fmt(doc["jitter_deg_raw_mean"])} -> {fmt(doc["jitter_deg_mean"])} deg/frame^2, moved {fmt(doc["smooth_delta_deg_mean"])} deg, MPJPE '
+        f'{fmt(doc["mpjpe_eval_mm_raw_mean"])} -> {fmt(doc["mpjpe_eval_mm_smooth_mean"])}, PAMPJPE {fmt(doc["pampjpe_eval_mm_raw_mean"])} -> '
+        f'{fmt(doc["pampjpe_eval_mm_smooth_mean"])}; {os.path.join(args.smooth_refined, SMOOTH_NAME)}')
     return out

@@ -4,7 +4,8 @@
 Runs set_seed(0), optimize_pose_refiner() and then the evaluation report test_pose_refiner_model()
 (/root/reference/main.py:21-25).  The reference's two further evaluations (test_pose_refiner_model_VIBE_MEVA,
 main.py:26-27) need the external VIBE / MEVA checkouts: the networks are out of scope, what those functions do with the
-networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evaluate_vertices), which runs alone and exits."""
+networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evaluate_vertices), which runs alone and exits.
+`--smooth_refined DIR` (refined.smooth_command) filters a `--save_refined` table along time and exits as well."""
 import importlib
 import os
 import sys
@@ -32,6 +33,9 @@ if __name__ == '__main__':
         if dist.is_available() and dist.is_initialized():
             dist.barrier()
             dist.destroy_process_group()
+        sys.exit(0)
+    if args.smooth_refined:                                                  # a --save_refined table along the time axis; no training
+        importlib.import_module(PKG + '.refined').smooth_command()
         sys.exit(0)
     res = optimize.optimize_pose_refiner()                                   # main.py:23
     if args.save_refined and int(os.environ.get('RANK', '0')) == 0:
