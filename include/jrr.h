@@ -126,6 +126,29 @@ enum {
   JRR_REGRESS_MAX_REG = 4       /* regressors one jrr_regress_joints call applies to one read of the vertices */
 };
 
+/* row of the regressor report's table (jrr_regressor_shift_accumulate): JRR_SHIFT_ACC_ROW int64 per group, offsets in int64, then a
+ * trailer of JRR_SHIFT_ACC_TRAILER int64 behind the last row, the trailer of the evaluation table.  Layout version 1.
+ * Fixed point: a length c in metres is q = llrintf(c * 2^24) (the scaling is exact, one rounding to an integer).
+ * Overflow, at the cap |c| < 4 m and 1e8 < 2^26.6 poses in one word: |q| < 2^26, so a sum of q stays below 2^52.6; a product
+ * q_i * q_j is below 2^52, shifted by 16 below 2^36, summed below 2^62.6; |d| < 4 sqrt(3) (1 + 2^-20) < 2^2.8 m gives sums below
+ * 2^53.4, the pelvis-relative length, at most twice that, below 2^54.4.  Counts and bins are at most the number of poses.       */
+enum {
+  JRR_SHIFT_ACC_LAYOUT_VERSION = 1,
+  JRR_SHIFT_ACC_ROW = 1277,
+  JRR_SHIFT_ACC_COUNT = 0,      /* poses counted */
+  JRR_SHIFT_ACC_BAD = 1,        /* poses of this group left out (non-finite input, no body frame, a component at or beyond the cap) */
+  JRR_SHIFT_ACC_SUM = 2,        /* [17][3]: sum of q over the poses, body-frame x, y, z (units of 2^-24 m) */
+  JRR_SHIFT_ACC_MOM = 53,       /* [17][6]: sum of (q_i * q_j) >> 16, arithmetic shift of the int64 product, (i,j) = xx, xy, xz, yy, yz, zz
+                                   (units of 2^-32 m^2) */
+  JRR_SHIFT_ACC_ABS = 155,      /* [17]: sum of llrintf(|d| * 2^24) */
+  JRR_SHIFT_ACC_ABS_REL = 172,  /* [17]: sum of llrintf(|d - d[Pelvis]| * 2^24) */
+  JRR_SHIFT_ACC_HIST = 189,     /* [17][64]: histogram of |d|, bin min(63, (int)floorf(|d| * 500.0f)) */
+  JRR_SHIFT_ACC_BINS = 64,      /* 2-mm bins 0 .. 62, bin 63 = everything >= 126 mm */
+  JRR_SHIFT_ACC_TRAILER = 2,    /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
+  JRR_DISCS_MAX_SETS = 8,       /* jrr_draw_discs */
+  JRR_DISCS_MAX_POINTS = 256
+};
+
 #define JRR_FLAG_SIL_SIZE(size) ((((size) / 32) & 15) << 16)
 
 typedef struct jrr_model jrr_model_t;   /* device-resident, re-laid-out SMPL constants */
@@ -494,6 +517,41 @@ int jrr_regress_joints(const float* verts_dev, int batch, const void* workspace_
  * calls or on the sharding over ranks (sum the ranks' tables).                                                              */
 int jrr_eval_accumulate(const float* err_j_dev, const float* err_pa_j_dev, const int32_t* group_dev, int batch, int n_groups,
                         int64_t* acc_dev, void* stream);
+
+/* ---- regressor report (`--regressor_report`): how far the retrained regressor moved each joint, and discs on a picture ------
+ * No reference counterpart in code: the reference's teaser.png shows the joints of the accepted regressor, of the retrained one and
+ * the ground truth on the fitted mesh; scripts/test.py:107-123 regresses both sets and keeps only their errors.
+ *
+ * jrr_regressor_shift_accumulate ADDS the poses of joints_a_dev / joints_b_dev (batch,17,3) fp32 metres -- regressor A (initial) and B
+ * (retrained) on the same meshes, as the regressors produce them, not pelvis-centred -- to rows group_dev[b] of acc_dev: int64
+ * [n_groups][JRR_SHIFT_ACC_ROW] + JRR_SHIFT_ACC_TRAILER words, layout above; the caller zeroes it once per report.  group_dev NULL:
+ * every pose in group 0.  group < 0 counts in trailer word 0 only, group >= n_groups in trailer word 1 only, as in
+ * jrr_eval_accumulate; 1 <= n_groups <= JRR_EVAL_ACC_MAX_GROUPS.
+ * Per pose, every operation rounded once in fp32 in the order written, no product fused into a sum (a . b = (a0 b0 + a1 b1) + a2 b2,
+ * |a| = sqrtf(a . a), a x b = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0)), a[i] the joints of A:
+ *   x = a[4] - a[1] (L_Hip - R_Hip), u = a[8] - a[0] (Neck - Pelvis); xh = x / |x|; z = xh x u; zh = z / |z|; yh = zh x xh
+ *     (an upright SMPL body gives the identity: x to the body's left, y up, z forward)
+ *   per joint j: d = b[j] - a[j]; c = (d . xh, d . yh, d . zh); q = llrintf(c * 2^24); len = |d|; r = d - d[0], rel = |r|
+ * The pose counts in JRR_SHIFT_ACC_BAD only, and adds nothing else, when one of its 102 inputs is non-finite, or !(|x| >= 1e-4f), or
+ * !(|z| >= 1e-4f * |u|), or one of the 51 components fails |c| < 4.0f.  Otherwise COUNT += 1 and per joint SUM += q, MOM += (q_i q_j) >> 16,
+ * ABS += llrintf(len * 2^24), ABS_REL += llrintf(rel * 2^24), HIST[min(63, (int)floorf(len * 500.0f))] += 1.
+ * Integer atomics only: the table is a function of the multiset of (pose, group) pairs -- not of the order, the split into calls or
+ * the sharding over ranks (sum the ranks' tables).                                                                          */
+int jrr_regressor_shift_accumulate(const float* joints_a_dev, const float* joints_b_dev, const int32_t* group_dev, int batch,
+                                   int n_groups, int64_t* acc_dev, void* stream);
+/* jrr_draw_discs paints filled discs INTO an existing picture rgb_dev (batch,h,w,3) uint8, interleaved, any h, w >= 1 (h * w <= 2^28).
+ *   points_dev   (n_sets,batch,n_pts,2) fp32 (x, y) in the picture's pixel frame
+ *   radius_dev   (n_sets,batch,n_pts) fp32 or NULL: then every disc has the scalar `radius`
+ *   colours_host (n_sets,3) uint8
+ *   1 <= n_sets <= JRR_DISCS_MAX_SETS, 1 <= n_pts <= JRR_DISCS_MAX_POINTS; anything else returns JRR_ERR_ARG and touches nothing.
+ * The inside rule is jrr_fit_overlay's: pixel (x, y) has its centre at the integer coordinate and is inside the disc (px, py, r) iff
+ * dx * dx + dy * dy <= r * r with dx = (float)x - px, dy = (float)y - py, every term rounded once in fp32.  A later set paints over an
+ * earlier one, within a set a later point over an earlier one.  A point with a non-finite coordinate or radius, or r < 0, draws
+ * nothing (r = 0 at an exact pixel centre draws that pixel); discs are clipped to the picture; a pixel outside every disc keeps its
+ * bytes (it is not written).  One thread owns a pixel and walks the points in order: no atomics, the result is a function of the
+ * inputs alone.                                                                                                              */
+int jrr_draw_discs(uint8_t* rgb_dev, int batch, int h, int w, const float* points_dev, const float* radius_dev, float radius,
+                   const uint8_t* colours_host, int n_sets, int n_pts, void* stream);
 
 /* ---- 2-D reprojection --------------------------------------------
  * return_2d_joints core, scripts/renderer.py:35-49 (pytorch3d 0.3.0 PerspectiveCameras, R = I,

@@ -83,11 +83,20 @@ def build_parser() -> argparse.ArgumentParser:
                              'imageSequence without its trailing take number, or the one before that; samples without such a path form '
                              'the single group `all`')
     parser.add_argument('--eval_vertices', type=str, default=None, metavar='DIR',
-                        help='with --eval_report: evaluate both regressors on the meshes of DIR (vertices.npy (N,6890,3) float32 m in SMPL '
+                        help='with --eval_report and / or --regressor_report: evaluate both regressors on the meshes of DIR (vertices.npy (N,6890,3) float32 m in SMPL '
                              'vertex order, gt_j3d.npy (N,17,3) mm, optional paths.txt or group.npy + group_names.txt) and exit -- what '
                              'scripts/test.py:141-301 does with the vertices of other models; no SMPL model file is read.  The regressors '
                              'are multiplied by find_j_reg_mask of the initial one as at scripts/test.py:108 (the convention of '
                              'test_pose_refiner_model; :206-212 applies no mask -- the reference\'s mask is all ones, so the two agree)')
+    parser.add_argument('--regressor_report', type=str, default=None, metavar='DIR',
+                        help='regressor report: DIR/regressor.json and DIR/regressor.md -- per H36M joint the support of the initial and '
+                             'the retrained regressor and how far, in a frame fixed to the body, the retrained one moves the joint on the '
+                             'evaluated meshes -- with pose_*.png (the joints of both and the ground truth on the shaded body, front | '
+                             'side) and weights_*.png (the support vertices on the template body); works with --eval_vertices as well '
+                             '(regressor_report.py)')
+    parser.add_argument('--regressor_report_images', type=int, default=8, help='--regressor_report: pose pictures (the first scored poses of rank 0)')
+    parser.add_argument('--regressor_report_size', type=int, default=256,
+                        help='--regressor_report: height S of the (S, 2S) pictures, a size the rasteriser takes (a multiple of 32 up to 256)')
     parser.add_argument('--camera_iters', type=int, default=1000, help='camera pre-fit Adam steps (optimize.py:190)')
     parser.add_argument('--save_j_regressor', type=str, default=None,
                         help='write the trained regressor in the models/retrained_J_Regressor.pt format')

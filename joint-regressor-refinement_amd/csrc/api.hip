@@ -1053,6 +1053,42 @@ extern "C" int jrr_eval_accumulate(const float* err_j, const float* err_pa_j, co
   return JRR_OK;
 }
 
+extern "C" int jrr_regressor_shift_accumulate(const float* joints_a, const float* joints_b, const int32_t* group, int batch, int n_groups,
+                                              int64_t* acc, void* stream) {
+  if (!joints_a || !joints_b || !acc || batch < 0 || ((uintptr_t)acc & 7) != 0) {
+    jrr_set_error("jrr_regressor_shift_accumulate: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS) {
+    jrr_set_error("jrr_regressor_shift_accumulate: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_shift_accumulate(joints_a, joints_b, group, n_groups, acc, batch, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_draw_discs(uint8_t* rgb, int batch, int h, int w, const float* points, const float* radius_dev, float radius,
+                              const uint8_t* colours_host, int n_sets, int n_pts, void* stream) {
+  if (!rgb || !points || !colours_host || batch < 0 || h < 1 || w < 1 || (long long)h * w > (1ll << 28)) {
+    jrr_set_error("jrr_draw_discs: bad argument (h, w >= 1, h * w <= 2^28)");
+    return JRR_ERR_ARG;
+  }
+  if (n_sets < 1 || n_sets > JRR_DISCS_MAX_SETS || n_pts < 1 || n_pts > JRR_DISCS_MAX_POINTS) {
+    jrr_set_error("jrr_draw_discs: %d sets of %d points: 1 .. %d sets of 1 .. %d points", n_sets, n_pts, (int)JRR_DISCS_MAX_SETS,
+                  (int)JRR_DISCS_MAX_POINTS);
+    return JRR_ERR_ARG;
+  }
+  if ((long long)batch * (((long long)h * w + 255) / 256) > 0x7fffffffll) {
+    jrr_set_error("jrr_draw_discs: batch %d of %d x %d pictures: more workgroups than one launch takes", batch, h, w);
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_draw_discs(rgb, batch, h, w, points, radius_dev, radius, colours_host, n_sets, n_pts, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
 // =============================================================================================
 // 2-D reprojection (row f1)
 // =============================================================================================

@@ -224,6 +224,14 @@ int launch_regress_joints(const float* verts, const void* ws, int n_reg, float* 
 int launch_eval_accumulate(const float* err_j, const float* err_pa_j, const int32_t* group, int n_groups, int64_t* acc, int B,
                            hipStream_t s);
 
+// regrep.hip
+// ADD the body-frame displacements joints_b - joints_a (B,17,3) to rows `group` (nullable: group 0) of the int64 table acc
+// (include/jrr.h, JRR_SHIFT_ACC_*)
+int launch_shift_accumulate(const float* ja, const float* jb, const int32_t* group, int n_groups, int64_t* acc, int B, hipStream_t s);
+// filled discs into rgb (B,h,w,3) uint8: pts (n_sets,B,n_pts,2), rad (n_sets,B,n_pts) or nullptr (then `radius`), colours [n_sets][3] host
+int launch_draw_discs(uint8_t* rgb, int B, int h, int w, const float* pts, const float* rad, float radius, const uint8_t* colours,
+                      int n_sets, int n_pts, hipStream_t s);
+
 // image.hip
 constexpr int IC_MAX_SIZE = 256;       // largest crop (pixels per side; sizes are multiples of 4)
 constexpr int IC_MAX_ROI_W = 1024;     // widest block of a frame a sample may hand over (pixels; frames are cut to 1000 x 1000)

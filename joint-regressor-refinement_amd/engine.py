@@ -691,6 +691,54 @@ def eval_accumulate(err_j: torch.Tensor, err_pa_j: torch.Tensor, group: torch.Te
           'eval_accumulate')
 
 
+SHIFT_ACC_ROW, SHIFT_ACC_TRAILER = 1277, 2      # include/jrr.h: JRR_SHIFT_ACC_ROW, JRR_SHIFT_ACC_TRAILER
+DISCS_MAX_SETS, DISCS_MAX_POINTS = 8, 256       # include/jrr.h: JRR_DISCS_MAX_SETS, JRR_DISCS_MAX_POINTS
+
+
+def regressor_shift_accumulate(joints_a: torch.Tensor, joints_b: torch.Tensor, group: Optional[torch.Tensor], n_groups: int,
+                               acc: torch.Tensor) -> None:
+    """jrr_regressor_shift_accumulate: ADD the body-frame displacements joints_b - joints_a (B,17,3) m to rows `group` (B, int32; None:
+    group 0) of the int64 table `acc` (n_groups * 1277 + 2 words, include/jrr.h JRR_SHIFT_ACC_*)"""
+    lib = _lib.load()
+    B = joints_a.shape[0]
+    joints_a, joints_b = joints_a.contiguous(), joints_b.contiguous()
+    assert joints_a.shape == (B, 17, 3) and joints_b.shape == (B, 17, 3)
+    assert joints_a.dtype == torch.float32 and joints_b.dtype == torch.float32 and acc.dtype == torch.int64
+    assert acc.is_contiguous() and acc.numel() == n_groups * SHIFT_ACC_ROW + SHIFT_ACC_TRAILER
+    assert joints_a.is_cuda and joints_b.device == joints_a.device and acc.device == joints_a.device
+    if group is not None:
+        group = group.contiguous()
+        assert group.shape == (B,) and group.dtype == torch.int32 and group.device == joints_a.device
+    check(lib.jrr_regressor_shift_accumulate(ptr(joints_a), ptr(joints_b), ptr(group), B, int(n_groups), ptr(acc),
+                                             stream_ptr(joints_a.device)), 'regressor_shift_accumulate')
+
+
+def draw_discs(rgb: torch.Tensor, points: torch.Tensor, colours, radius: float = 2.0, radii: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """jrr_draw_discs: filled discs INTO the contiguous uint8 picture `rgb` (B,h,w,3), which is returned.  points (n_sets,B,n_pts,2)
+    float32 (x, y) in pixels; colours: n_sets (r, g, b) byte triples; radii (n_sets,B,n_pts) or the scalar radius.  A later set paints
+    over an earlier one, a later point over an earlier one; a non-finite point or radius, or a negative radius, draws nothing."""
+    lib = _lib.load()
+    if not (torch.is_tensor(rgb) and rgb.dim() == 4 and rgb.shape[3] == 3 and rgb.dtype == torch.uint8 and rgb.is_cuda and rgb.is_contiguous()):
+        raise ValueError('draw_discs: rgb must be a contiguous uint8 device tensor (B,h,w,3)')
+    B, h, w, _ = rgb.shape
+    dev = rgb.device
+    if points.dim() != 4 or points.shape[1] != B or points.shape[3] != 2 or points.dtype != torch.float32 or points.device != dev:
+        raise ValueError(f'draw_discs: points must be float32 (n_sets,{B},n_pts,2) on {dev}, got {tuple(points.shape)} {points.dtype}')
+    points = points.contiguous()
+    n_sets, n_pts = int(points.shape[0]), int(points.shape[2])
+    cols = np.ascontiguousarray(np.asarray(colours, dtype=np.int64).reshape(-1, 3))
+    if cols.shape[0] != n_sets or cols.min(initial=0) < 0 or cols.max(initial=0) > 255:
+        raise ValueError(f'draw_discs: {n_sets} colours of three bytes each')
+    cols = cols.astype(np.uint8)
+    if radii is not None:
+        if tuple(radii.shape) != (n_sets, B, n_pts) or radii.dtype != torch.float32 or radii.device != dev:
+            raise ValueError(f'draw_discs: radii must be float32 {(n_sets, B, n_pts)} on {dev}')
+        radii = radii.contiguous()
+    check(lib.jrr_draw_discs(ptr(rgb), B, h, w, ptr(points), ptr(radii), float(radius), cols.ctypes.data_as(c_void_p), n_sets, n_pts,
+                             stream_ptr(dev)), 'draw_discs')
+    return rgb
+
+
 def project_joints(joints: torch.Tensor, cam: torch.Tensor) -> torch.Tensor:
     """return_2d_joints core (scripts/renderer.py:35-49): (B,17,3), (B,3) -> screen xy (B,17,2)"""
     lib = _lib.load()

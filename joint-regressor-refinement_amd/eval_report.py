@@ -274,10 +274,12 @@ def open_vertices_dir(directory: str, kind: str = 'action'):
 def evaluate_vertices(log=print) -> Optional[dict]:
     """`--eval_vertices DIR --eval_report OUT`: rank r takes shard_bounds(N, r, world) of the meshes in chunks of --batch_size
     (pinned uploads), both regressors on one read of the vertices, one all-reduce per report at the end."""
-    from . import checkpoint, engine as _engine, smpl_model, utils
+    from . import checkpoint, engine as _engine, regressor_report, smpl_model, utils
     from .args import args
-    if not args.eval_report:
-        raise ValueError('--eval_vertices needs --eval_report DIR (where eval.json / eval.md go)')
+    if not args.eval_report and not args.regressor_report:
+        raise ValueError('--eval_vertices needs --eval_report or --regressor_report DIR (where eval.json / eval.md, regressor.json / '
+                         'regressor.md go)')
+    regressor_report.check_flags(args._get())
     verts, gt, names, ids = open_vertices_dir(args.eval_vertices, args.eval_groups)          # before any launch
     jdist.init(args.dist_backend)
     rank, local_rank, world = jdist.env_rank_world()
@@ -290,7 +292,9 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     J_before = torch.from_numpy(J_np).float()
     Js = torch.stack([J_before, J_after.cpu()]).to(device)
     table = _engine.JointRegressorTable(Js, utils.find_j_reg_mask(Js[0]))     # the mask of scripts/test.py:51-53,108
-    reports = {'before': EvalReport(names, device), 'after': EvalReport(names, device)}
+    reports = {'before': EvalReport(names, device), 'after': EvalReport(names, device)} if args.eval_report else None
+    mask_np = utils.find_j_reg_mask(J_before).numpy()
+    shift = regressor_report.Run(args._get(), names, device, J_np, J_after.cpu().numpy(), mask_np, 'vertices') if args.regressor_report else None
     N = verts.shape[0]
     lo, hi = jdist.shard_bounds(N, rank, world)
     bs = max(1, int(args.batch_size))
@@ -312,11 +316,19 @@ def evaluate_vertices(log=print) -> Optional[dict]:
             used[k % 2] = True
             joints = table.regress(dv)
             gtc = utils.move_pelvis(dg)                                       # scripts/test.py:87
-            reports['before'].add(joints[0], gtc, di)
-            reports['after'].add(joints[1], gtc, di)
+            if reports is not None:
+                reports['before'].add(joints[0], gtc, di)
+                reports['after'].add(joints[1], gtc, di)
+            if shift is not None:
+                shift.add(dv, joints[0], joints[1], gtc, di, ids[a:b] >= 0)
+    initial, retrained = (args.j_regressor_init, sha16(args.j_regressor_init, J_np)), (path, sha16(path))
+    if shift is not None:      # the body model is for the pictures alone: only when --smpl_dir resolves, or --synthetic allows the synthetic one
+        model_np = regressor_report.resolve_body_model(args.smpl_dir, args.synthetic) if rank == 0 else None
+        shift_doc = shift.finish(initial, retrained, model_np, log=log)
+        if reports is None:
+            return shift_doc
     results = {k: r.finish() for k, r in reports.items()}
-    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', dict(vars(args._get())),
-                (args.j_regressor_init, sha16(args.j_regressor_init, J_np)), (path, sha16(path)))
+    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', dict(vars(args._get())), initial, retrained)
     if rank == 0:
         for k in ('before', 'after'):
             r = results[k][ALL]

@@ -232,13 +232,14 @@ def mesh_shade(verts: torch.Tensor, cam: torch.Tensor, pix_to_face: torch.Tensor
     return (out, depth, nmap) if (want_depth or want_normals) else out
 
 
-def side_view(verts: torch.Tensor, cam: torch.Tensor, degrees: float = 90.0) -> torch.Tensor:
+def side_view(verts: torch.Tensor, cam: torch.Tensor, degrees: float = 90.0, centre: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The vertices that the SAME `cam` renders as the body seen from the side: verts (B,V,3) in SMPL space -> (B,V,3).  In view space
     (x, y, z) -> (-2x + cx, -2y + cy, 2z + cz) each pose is turned by `degrees` about the vertical axis through its centroid, so its
     distance from the camera stays what it was.  The view-space offsets from the centroid are d = (v - mean v) * (-2, -2, 2), exact in
     floating point; the result is v + ((R - I) d) * (-1/2, -1/2, 1/2), the map back to SMPL space, exact as well -- the camera's
     translation cancels.  A turn by 0 adds zeros: the identity bit for bit.  A torch op on the tensors' device; not differentiated
-    through by anything here."""
+    through by anything here.  `centre` (B,1,3), default the centroid of `verts`: other points of the same bodies (their joints) are
+    turned WITH the vertices by passing the vertices' centroid."""
     if verts.dim() != 3 or verts.shape[2] != 3 or not verts.is_floating_point():
         raise ValueError(f'verts: expected a floating-point (B,V,3), got {tuple(verts.shape)} {verts.dtype}')
     if tuple(cam.shape) != (verts.shape[0], 3) or cam.device != verts.device:
@@ -249,9 +250,36 @@ def side_view(verts: torch.Tensor, cam: torch.Tensor, degrees: float = 90.0) -> 
     else:
         c, s = math.cos(math.radians(degrees)), math.sin(math.radians(degrees))
     flip = verts.new_tensor([-2.0, -2.0, 2.0])
-    d = (verts - verts.mean(dim=1, keepdim=True)) * flip
+    if centre is None:
+        centre = verts.mean(dim=1, keepdim=True)
+    elif tuple(centre.shape) != (verts.shape[0], 1, 3) or centre.device != verts.device:
+        raise ValueError(f'centre: expected {(verts.shape[0], 1, 3)} on {verts.device}, got {tuple(centre.shape)} on {centre.device}')
+    d = (verts - centre) * flip
     turned = torch.stack([(c - 1.0) * d[..., 0] + s * d[..., 2], torch.zeros_like(d[..., 1]), (c - 1.0) * d[..., 2] - s * d[..., 0]], dim=-1)
     return verts + turned * verts.new_tensor([-0.5, -0.5, 0.5])
+
+
+def frame_camera(verts: torch.Tensor, size: int, margin: float = 0.1) -> torch.Tensor:
+    """A camera translation (B,3) that frames each pose of verts (B,V,3) in a size x size picture of the rasteriser, for meshes that
+    come without a camera (`--eval_vertices`).  The rasteriser projects (include/jrr.h, jrr_mesh_shade step 1) X = -2x + cx,
+    Y = -2y + cy, Z = 2z + cz, (u, v) = (F X / Z, F Y / Z) with F = 5000 / size, and the picture is |u|, |v| <= 1.  Rule, per pose, from
+    the bounding box of its vertices [lo, hi]:
+        cx = lo_x + hi_x, cy = lo_y + hi_y       the box's centre projects to the picture's centre
+        E  = max(hi_x - lo_x, hi_y - lo_y)       the larger half extent in view units (the projection doubles x and y)
+        cz = F E / (1 - margin) - 2 lo_z         the nearest vertex sits at depth Z0 = F E / (1 - margin)
+    Every vertex then has Z >= Z0 > 0 and |X|, |Y| <= E, so |u|, |v| <= 1 - margin: all of them land inside the picture, and the larger
+    extent fills (1 - margin) Z0 / (Z0 + 2 (hi_z - lo_z)) of it -- Z0 is tens of metres at F = 5000 / size, so nearly 1 - margin.  A pose of
+    zero extent gets E = 1e-6.  Computed in float64, returned in the vertices' dtype on their device."""
+    if verts.dim() != 3 or verts.shape[2] != 3 or not verts.is_floating_point():
+        raise ValueError(f'verts: expected a floating-point (B,V,3), got {tuple(verts.shape)} {verts.dtype}')
+    if not 0.0 <= float(margin) < 1.0 or int(size) < 1:
+        raise ValueError(f'frame_camera: size {size} >= 1 and margin {margin} in [0, 1)')
+    v = verts.detach().double()
+    lo, hi = v.min(dim=1).values, v.max(dim=1).values
+    F = 5000.0 / float(int(size))
+    E = torch.maximum(hi[:, 0] - lo[:, 0], hi[:, 1] - lo[:, 1]).clamp(min=1e-6)
+    cam = torch.stack([lo[:, 0] + hi[:, 0], lo[:, 1] + hi[:, 1], F * E / (1.0 - float(margin)) - 2.0 * lo[:, 2]], dim=1)
+    return cam.to(verts.dtype)
 
 
 def _chunk(tag: bytes, data: bytes) -> bytes:

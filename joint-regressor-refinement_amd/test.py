@@ -17,7 +17,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import batches, checkpoint, engine as _engine, eval_report, smpl_model, utils
+from . import batches, checkpoint, engine as _engine, eval_report, regressor_report, smpl_model, utils
 from .args import args
 from .smpl import SMPL
 
@@ -64,8 +64,12 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     J_regressor_initial = torch.from_numpy(J_np).float().to(device)                                      # :48-49
     j_reg_mask = utils.find_j_reg_mask(J_regressor_initial)                                              # :51-53
 
-    source = validation_batches(smpl.model_np, J_np, device, with_index=bool(args.eval_report))
+    source = validation_batches(smpl.model_np, J_np, device, with_index=bool(args.eval_report or args.regressor_report))
     reports, group_ids = None, None
+    shift = None
+    if args.regressor_report:  # what the retrained regressor did to each joint: one more launch per batch, the vertices of its forward kept
+        names, group_ids = _groups()
+        shift = regressor_report.Run(args._get(), names, device, J_np, J_regressor.cpu().numpy(), j_reg_mask.cpu().numpy(), 'parameters')
     if args.eval_report:       # per group / per joint / PCK next to the four printed means: two more launches per evaluate, no read-back
         names, group_ids = _groups()
         reports = {'before': eval_report.EvalReport(names, device), 'after': eval_report.EvalReport(names, device)}
@@ -76,16 +80,22 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
         for batch in source:
             B = int(batch['pose6d'].shape[0])
             if B not in engines:
-                engines[B] = _engine.RefineEngine(smpl.device_model, B)
+                engines[B] = _engine.RefineEngine(smpl.device_model, B, flags=_engine.FLAG_KEEP_VERTS) if shift is not None else \
+                    _engine.RefineEngine(smpl.device_model, B)
             eng = engines[B]
             x6d = batch['pose6d'].to(device).float().contiguous()
             betas = batch['betas'].to(device).float().contiguous()
             gt = utils.move_pelvis(batch['gt_j3d'].to(device).float())                                   # :87
             eng.set_j_regressor(J_regressor_initial, j_reg_mask)
-            joints = eng.find_joints_forward(betas, x6d=x6d)                                             # :107-108
+            if shift is not None:
+                joints, verts = eng.find_joints_forward(betas, x6d=x6d, return_verts=True)
+                joints_initial = joints
+            else:
+                joints = eng.find_joints_forward(betas, x6d=x6d)                                         # :107-108
             mb, pb = utils.evaluate(joints, gt)                                                         # :110-111
-            if reports is not None:
+            if reports is not None or shift is not None:
                 gid = _batch_groups(batch, group_ids, B, device)
+            if reports is not None:
                 reports['before'].add(joints, gt, gid)
             eng.set_j_regressor(J_regressor, j_reg_mask)
             joints = eng.find_joints_forward(betas, x6d=x6d)                                             # :116-117
@@ -93,6 +103,8 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
             mpjpe_before.append(mb); pampjpe_before.append(pb); mpjpe_after.append(ma); pampjpe_after.append(pa)
             if reports is not None:
                 reports['after'].add(joints, gt, gid)
+            if shift is not None:
+                shift.add(verts, joints_initial, joints, gt, gid, None if 'valid' not in batch else batch['valid'].cpu().bool().numpy())
     if not mpjpe_before:
         raise RuntimeError('no validation batch (drop_last=True needs at least --batch_size samples)')
     mean = lambda xs: float(torch.tensor(xs, dtype=torch.float64).mean())
@@ -104,6 +116,9 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
         rep['eval_report'] = eval_report.write(args.eval_report, results, names, args.eval_groups if group_ids is not None else 'none', 'parameters',
                                                dict(vars(args._get())), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
                                                (path, eval_report.sha16(path)))
+    if shift is not None:
+        rep['regressor_report'] = shift.finish((args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
+                                               (path, eval_report.sha16(path)), smpl.model_np, smpl.device_model, reduce=False)
     log('MPJPE')                                                                                         # :125-138
     log(f"{rep['mpjpe_before']:.4f}")
     log('PAMPJPE')

@@ -5,6 +5,7 @@ Runs set_seed(0), optimize_pose_refiner() and then the evaluation report test_po
 (/root/reference/main.py:21-25).  The reference's two further evaluations (test_pose_refiner_model_VIBE_MEVA,
 main.py:26-27) need the external VIBE / MEVA checkouts: the networks are out of scope, what those functions do with the
 networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evaluate_vertices), which runs alone and exits.
+`--regressor_report DIR` (regressor_report.py) adds to either evaluation what the retrained regressor did to each joint, with pictures.
 `--smooth_refined DIR` (refined.smooth_command) filters a `--save_refined` table along time and exits as well."""
 import importlib
 import os
@@ -27,6 +28,7 @@ if __name__ == '__main__':
         except ImportError:
             print('wandb is not installed; logging to stdout')
     utils.set_seed(0)
+    importlib.import_module(PKG + '.regressor_report').check_flags(args._get())   # --regressor_report: refused before anything runs
     if args.eval_vertices:                                                   # scripts/test.py:141-301 on the meshes of a directory
         importlib.import_module(PKG + '.eval_report').evaluate_vertices()
         import torch.distributed as dist
