@@ -1,5 +1,6 @@
-// C ABI (include/jrr.h): error plumbing, run-time knobs, engine / workspace planning, and the launch sequences of the operator-level
-// entry points.  The body-model re-layout is model.hip, the fused inner loop and the J step refine.hip (shared state: engine.h).
+// The engine behind the C ABI (include/jrr.h): error plumbing, run-time knobs, engine / workspace planning, the regressor upload, the
+// SMPL operators, and the small operators whose kernels live in the hot-path file prep.hip.  Every other entry point sits in the file
+// of the kernels it launches; the body-model re-layout is model.hip, the fused inner loop and the J step refine.hip (shared: engine.h).
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
@@ -412,34 +413,6 @@ int jrr::set_j_regressor_impl(jrr_engine* e, const float* J, const float* mask, 
   return JRR_OK;
 }
 
-extern "C" int jrr_engine_set_pose_disc(jrr_engine_t* e, const float* P, void* stream) {
-  if (!e || !P) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!(e->flags & JRR_FLAG_POSE_DISC)) { jrr_set_error("engine created without JRR_FLAG_POSE_DISC"); return JRR_ERR_STATE; }
-  hipStream_t s = (hipStream_t)stream;
-  JRR_HIP(hipMemcpyAsync(e->Pd, P, (size_t)DP_TOTAL * 4, hipMemcpyDeviceToDevice, s));
-  launch_transpose(e->Pd + DP_FC0_W, e->W0T, 1024, 768, s);    // [out][in] -> [in][out]
-  launch_transpose(e->Pd + DP_FC2_W, e->W2T, 1024, 1024, s);
-  launch_scale_rows(e->Pd + DP_FC2_W, e->Pd + DP_FC4_W, e->W2s, 1024, 1024, s);   // row n of fc2.w times fc4.w[n]
-  launch_to_quads(e->W0T, 1024, e->W0Tq, 768, 1024, s);                // A operands A[k][m] of the four loop GEMMs, in quads
-  launch_to_quads(e->W2T, 1024, e->W2Tq, 1024, 1024, s);
-  launch_to_quads(e->W2s, 1024, e->W2sq, 1024, 1024, s);
-  launch_to_quads(e->Pd + DP_FC0_W, 768, e->W0q, 1024, 768, s);
-  launch_conv_image(e->Pd, e->convL, s);
-  CHECK_LAUNCH();
-  e->have_pd = true;
-  return JRR_OK;
-}
-
-extern "C" int jrr_engine_set_shape_disc(jrr_engine_t* e, const float* P, void* stream) {
-  if (!e || !P) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!(e->flags & JRR_FLAG_SHAPE_DISC)) { jrr_set_error("engine created without JRR_FLAG_SHAPE_DISC"); return JRR_ERR_STATE; }
-  JRR_HIP(hipMemcpyAsync(e->Ps, P, (size_t)JRR_SHAPE_DISC_PARAMS * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  e->have_sd = true;
-  return JRR_OK;
-}
-
 // =============================================================================================
 // operator-level entry points
 // =============================================================================================
@@ -458,120 +431,6 @@ extern "C" int jrr_rot6d_backward(const float* x, const float* dR, float* dx, in
   return JRR_OK;
 }
 
-/* find_crop on uint8 frames (scripts/data.py:220-271) and the mask preparation (scripts/data.py:121,130-132) */
-extern "C" int jrr_image_crop(const uint8_t* pix, size_t pix_bytes, const int64_t* desc, const float* bboxes, int batch, const float* mean,
-                              const float* stdv, int size0, float* out0, int size1, float* out1, int32_t* status, void* stream) {
-  if (!pix || !desc || !bboxes || !out0 || !status || batch < 0 || batch > 65535 || (size1 != 0 && !out1) || ((mean == nullptr) != (stdv == nullptr))) {
-    jrr_set_error("jrr_image_crop: bad argument");
-    return JRR_ERR_ARG;
-  }
-  auto bad_size = [](int n) { return n < 4 || n > IC_MAX_SIZE || n % 4 != 0; };
-  if (bad_size(size0) || (size1 != 0 && bad_size(size1))) {
-    jrr_set_error("jrr_image_crop: crop sizes %d, %d: one or two sizes, multiples of 4, at most %d", size0, size1, IC_MAX_SIZE);
-    return JRR_ERR_ARG;
-  }
-  if (((uintptr_t)pix & 15) != 0 || pix_bytes % 16 != 0 || pix_bytes == 0) {
-    jrr_set_error("jrr_image_crop: the pixel buffer must be 16-byte aligned and a non-zero multiple of 16 bytes long");
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  launch_image_crop(pix, pix_bytes, desc, bboxes, batch, mean, stdv, size0, out0, size1, out1, status, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-extern "C" int jrr_mask_prepare(const uint8_t* masks, int batch, int h, int w, float* out, int32_t* valid, void* stream) {
-  if (!masks || !out || !valid || batch < 0 || h <= 0 || w <= 0 || (((uintptr_t)masks | (uintptr_t)out) & 15) != 0) {
-    jrr_set_error("jrr_mask_prepare: bad argument");
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  launch_mask_prepare(masks, batch, h, w, out, valid, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-/* the fit report: viz() of scripts/optimize.py:35-48 around the inner loop (:204-218, :268-274) */
-extern "C" int jrr_silhouette_compare(const float* alpha, const float* mask, int batch, int h, int w, float thr_render, float thr_mask,
-                                      int32_t* counts, void* stream) {
-  if (!alpha || !mask || !counts || batch < 0 || batch > (1 << 24) || h <= 0 || w <= 0 || (long long)h * w > (1LL << 30)) {
-    jrr_set_error("jrr_silhouette_compare: bad argument");
-    return JRR_ERR_ARG;
-  }
-  if (((long long)h * w) % 4 != 0 || (((uintptr_t)alpha | (uintptr_t)mask) & 15) != 0 || ((uintptr_t)counts & 3) != 0) {
-    jrr_set_error("jrr_silhouette_compare: %d x %d: h * w must be a multiple of 4 and the images 16-byte aligned", h, w);
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  JRR_HIP(hipMemsetAsync(counts, 0, (size_t)batch * 4 * sizeof(int32_t), (hipStream_t)stream));
-  launch_sil_compare(alpha, mask, batch, h, w, thr_render, thr_mask, counts, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-extern "C" int jrr_fit_overlay(const float* alpha, const float* mask, const float* image, const float* mean, const float* stdv,
-                               const float* joints2d, int n_sets, int batch, int size, float thr_render, float thr_mask, float radius,
-                               uint8_t* rgb, void* stream) {
-  if (!alpha || !mask || !rgb || batch < 0 || batch > (1 << 24) || n_sets < 0 || n_sets > 3 || (n_sets > 0 && !joints2d) ||
-      ((mean == nullptr) != (stdv == nullptr)) || (mean && !image)) {
-    jrr_set_error("jrr_fit_overlay: bad argument");
-    return JRR_ERR_ARG;
-  }
-  if (size < 4 || size > 256 || size % 4 != 0) {
-    jrr_set_error("jrr_fit_overlay: size %d: a multiple of 4, at most 256", size);
-    return JRR_ERR_ARG;
-  }
-  if ((((uintptr_t)alpha | (uintptr_t)mask | (uintptr_t)image) & 15) != 0 || ((uintptr_t)rgb & 3) != 0) {
-    jrr_set_error("jrr_fit_overlay: alpha, mask and image must be 16-byte aligned, the output 4-byte aligned");
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  launch_fit_overlay(alpha, mask, image, mean, stdv, joints2d, n_sets, batch, size, thr_render, thr_mask, radius, rgb, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-/* the fit report's shaded views (--fit_report_mesh): no engine, no body model */
-extern "C" int jrr_vertex_normals(const float* verts, const int32_t* faces, const int32_t* adj_offset, const int32_t* adj_face, int batch,
-                                  int n_verts, int n_faces, float* normals, void* stream) {
-  if (!verts || !faces || !adj_offset || !adj_face || !normals || batch < 0 || n_verts < 1 || n_faces < 1 || n_faces > (1 << 28) ||
-      (long long)batch * n_verts > (1LL << 30)) {
-    jrr_set_error("jrr_vertex_normals: bad argument");
-    return JRR_ERR_ARG;
-  }
-  if ((((uintptr_t)verts | (uintptr_t)faces | (uintptr_t)adj_offset | (uintptr_t)adj_face | (uintptr_t)normals) & 3) != 0) {
-    jrr_set_error("jrr_vertex_normals: every array must be 4-byte aligned");
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  launch_vertex_normals(verts, faces, adj_offset, adj_face, normals, batch, n_verts, n_faces, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-extern "C" int jrr_mesh_shade(const float* verts, const float* normals, const int32_t* faces, const float* cam, const int32_t* pix_to_face,
-                              const float* image, const float* mean, const float* stdv, int batch, int n_verts, int n_faces, int size,
-                              const float* colour_host, float opacity, float ambient, const float* light_host, float background,
-                              uint8_t* rgb, float* depth, float* normal, int32_t* status, void* stream) {
-  if (!verts || !normals || !faces || !cam || !pix_to_face || !colour_host || !light_host || !rgb || batch < 0 || batch > (1 << 24) ||
-      n_verts < 1 || n_faces < 1 || n_faces > (1 << 28) || (long long)batch * n_verts > (1LL << 30) ||
-      ((mean == nullptr) != (stdv == nullptr)) || (mean && !image)) {
-    jrr_set_error("jrr_mesh_shade: bad argument");
-    return JRR_ERR_ARG;
-  }
-  if (size < 4 || size > 256 || size % 4 != 0) {
-    jrr_set_error("jrr_mesh_shade: size %d: a multiple of 4, at most 256", size);
-    return JRR_ERR_ARG;
-  }
-  if ((((uintptr_t)pix_to_face | (uintptr_t)image | (uintptr_t)depth | (uintptr_t)normal) & 15) != 0 ||
-      (((uintptr_t)verts | (uintptr_t)normals | (uintptr_t)faces | (uintptr_t)cam | (uintptr_t)rgb | (uintptr_t)status) & 3) != 0) {
-    jrr_set_error("jrr_mesh_shade: pix_to_face, image, depth and normal must be 16-byte aligned, everything else 4-byte aligned");
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  launch_mesh_shade(verts, normals, faces, cam, pix_to_face, image, mean, stdv, batch, n_verts, n_faces, size, colour_host, opacity, ambient,
-                    light_host, background, rgb, depth, normal, status, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
 /* smplx batch_rodrigues (pose2rot=True branch of the SMPL operator) */
 extern "C" int jrr_rodrigues_forward(const float* aa, float* R, int n, void* stream) {
   if (!aa || !R || n < 0) return JRR_ERR_ARG;
@@ -584,37 +443,6 @@ extern "C" int jrr_rodrigues_backward(const float* aa, const float* dR, float* d
   if (!aa || !dR || !daa || n < 0) return JRR_ERR_ARG;
   if (n == 0) return JRR_OK;
   launch_rodrigues_bwd(aa, dR, daa, n, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-/* the log map and the refined-pose table (--save_refined) */
-extern "C" int jrr_rotmat_to_axis_angle(const float* R, float* aa, int n, void* stream) {
-  if (!R || !aa || n < 0) {
-    jrr_set_error("jrr_rotmat_to_axis_angle: bad argument");
-    return JRR_ERR_ARG;
-  }
-  if (n == 0) return JRR_OK;
-  launch_rotmat_log(R, aa, n, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-extern "C" int jrr_pose_export(const float* x6d, const float* betas, const float* cam, const float* extra, int n_extra, const int64_t* index,
-                               float* table, int64_t n_rows, int32_t* status, int batch, void* stream) {
-  if (!x6d || !betas || !cam || !index || !table || !status || batch < 0 || n_rows < 0) {
-    jrr_set_error("jrr_pose_export: bad argument");
-    return JRR_ERR_ARG;
-  }
-  if (n_extra < 0 || n_extra > JRR_EXPORT_MAX_EXTRA) {
-    jrr_set_error("jrr_pose_export: n_extra %d: 0 .. %d", n_extra, (int)JRR_EXPORT_MAX_EXTRA);
-    return JRR_ERR_ARG;
-  }
-  if (((uintptr_t)table & 15) != 0 || ((uintptr_t)x6d & 7) != 0 || ((uintptr_t)index & 7) != 0 || ((uintptr_t)status & 3) != 0) {
-    jrr_set_error("jrr_pose_export: the table must be 16-byte aligned (x6d and index 8-byte, status 4-byte)");
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  launch_pose_export(x6d, betas, cam, n_extra > 0 ? extra : nullptr, n_extra, index, table, n_rows, status, batch, (hipStream_t)stream);
   CHECK_LAUNCH();
   return JRR_OK;
 }
@@ -766,325 +594,11 @@ extern "C" int jrr_joint_loss(const float* joints, const float* gt_mm, float wei
   return JRR_OK;
 }
 
-// ---- pose discriminator --------------------------------------------------------------------
-// Six launches per forward + input gradient (scripts/discriminator.py:32-54 and its adjoint):
-//   k_dconv_fwd (per-joint MLP, MFMA)  ->  fc0 GEMM (+bias, ReLU)  ->  fc2 GEMM (+bias, ReLU, the fc4 dot product
-//   w4 . a2 as per-column partials in the epilogue; what it stores is relu'(a2) as 0 / 1: nothing else of a2 is read again)
-//   ->  fc2 adjoint GEMM on that indicator (dz from the partial dots in the prologue multiplies the finished column sums
-//   in the epilogue; fc2.w pre-scaled by w4: the rank-one output-layer adjoint is never materialised)  ->  fc0 adjoint
-//   GEMM  ->  k_dconv_bwd.
-// All four GEMMs: exact 128x64 tiles (512 workgroups at 4096 poses), 3-deep LDS-DMA ring.
-// The loop path keeps every activation in quads [row/4][pose][4] (k_disc_gemm); the weight-gradient path of the outer
-// step (disc_backward_params) needs row-major activations for its transposes / row sums and runs the row-major kernels.
-// conv_done: the per-joint MLP already ran (fused into the chain-forward launch, launch_prep_fwd_dconv)
-int jrr::disc_forward(jrr_engine* e, const float* x6d, float* out, hipStream_t s, bool quad, bool conv_done) {
-  if (!conv_done) launch_disc_conv_fwd(e->convL, x6d, e->H2T, out, e->B, e->BP, s, quad ? 1 : 0);
-  GemmArgs g;
-  g.mask = nullptr; g.split_stride = 0; g.N = e->BP; g.ldb = e->BP; g.ldo = e->BP;
-  g.A = quad ? e->W0Tq : e->W0T; g.lda = 1024; g.Bm = e->H2T; g.Out = e->A1T; g.bias = e->Pd + DP_FC0_B; g.M = 1024; g.K = 768;
-  int rc = quad ? launch_disc_gemm_q(g, EPI_BIAS_RELU, 0, s) : launch_gemm_128x64(g, EPI_BIAS_RELU, 1, s);
-  if (rc) return rc;
-  g.A = quad ? e->W2Tq : e->W2T; g.lda = 1024; g.Bm = e->A1T; g.Out = e->A2T; g.bias = e->Pd + DP_FC2_B; g.M = 1024; g.K = 1024;
-  if (!quad) return launch_gemm_128x64(g, EPI_BIAS_RELU, 1, s);
-  g.dotw = e->Pd + DP_FC4_W; g.dot_out = e->zpart;
-  return launch_disc_gemm_q(g, EPI_BIAS_RELU_DOT, 0, s);
-}
-
-// skip_conv: the caller runs the per-joint MLP adjoint itself (fused with the dF^T slab sum, launch_dconv_bwd_reduce)
-int jrr::disc_backward_input(jrr_engine* e, const float* x6d, float* out, const float* gout, float scale, float target, float* gx,
-                             hipStream_t s, float* sq, bool skip_conv) {
-  GemmArgs g;
-  g.bias = nullptr; g.split_stride = 0; g.N = e->BP; g.ldb = e->BP; g.ldo = e->BP;
-  // dA1T[k][b] = relu'(A1T) * sum_n (fc4.w[n] fc2.w[n][k]) relu'(A2T[n][b]) dz[b]
-  g.A = e->W2sq; g.lda = 1024; g.Bm = e->A2T; g.Out = e->dA1T; g.mask = e->A1T; g.M = 1024; g.K = 1024;
-  g.zpart = e->zpart; g.nzpart = 16; g.zbias = e->Pd + DP_FC4_B; g.gout = gout; g.gout_ld = 25; g.scale = scale; g.target = target;
-  g.nvalid = e->B; g.sq0 = sq; g.out0 = out; g.out0_ld = 25;
-  int rc = launch_disc_gemm_q(g, EPI_MASK, 2, s);
-  if (rc) return rc;
-  // dH2T[k][b] = sum_n fc0.w[n][k] dA1T[n][b]
-  GemmArgs h;
-  h.bias = nullptr; h.split_stride = 0; h.N = e->BP; h.ldb = e->BP; h.ldo = e->BP;
-  h.A = e->W0q; h.lda = 768; h.Bm = e->dA1T; h.Out = e->dH2T; h.mask = nullptr; h.M = 768; h.K = 1024;
-  rc = launch_disc_gemm_q(h, EPI_STORE, 0, s);
-  if (rc) return rc;
-  if (!skip_conv) launch_disc_conv_bwd(e->convL, x6d, e->dH2T, gout, scale, target, gx, e->B, e->BP, s, sq, 1);
-  return 0;
-}
-
-extern "C" int jrr_pose_disc_forward(jrr_engine_t* e, const float* x6d, float* out, void* stream) {
-  if (!e || !x6d || !out) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
-  hipStream_t s = (hipStream_t)stream;
-  int rc = disc_forward(e, x6d, out, s);
-  if (rc) return rc;
-  launch_disc_z_finish(e->zpart, 16, e->BP, e->Pd + DP_FC4_B, out, e->B, s);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_pose_disc_backward_input(jrr_engine_t* e, const float* x6d, float weight, float target, float* dx,
-                                            void* stream) {
-  if (!e || !x6d || !dx) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
-  const float scale = (float)(2.0 * (double)weight / ((double)e->bnorm * 25.0));
-  int rc = disc_backward_input(e, x6d, nullptr, nullptr, scale, target, dx, (hipStream_t)stream);
-  if (rc) return rc;
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_pose_disc_vjp_input(jrr_engine_t* e, const float* x6d, const float* gout, float* dx, void* stream) {
-  if (!e || !x6d || !gout || !dx) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
-  int rc = disc_backward_input(e, x6d, nullptr, gout, 0.f, 0.f, dx, (hipStream_t)stream);
-  if (rc) return rc;
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-// weight gradients of the pose discriminator: either of the MSE against `target` (gout == NULL; scale = 2/(bnorm*25))
-// or the vector-Jacobian product for an arbitrary upstream gradient gout (B,25)
-static int disc_backward_params(jrr_engine* e, const float* x6d, const float* gout, float scale, float target, float* dP,
-                                float* sqerr, hipStream_t s) {
-  int rc = disc_forward(e, x6d, e->dsc, s, false);        // row-major activations for the transposes / row sums below
-  if (rc) return rc;
-  launch_disc_out(e->Pd, e->A2T, e->dsc, e->dA2T, gout, scale, target, e->B, e->BP, s, e->dz0);
-  if (sqerr) launch_sqerr_rows(e->dsc, 25, target, sqerr, e->B, s);
-  // fc4: dw[n] += sum_b A2T[n][b] dz0[b] ; db += sum_b dz0[b]
-  launch_rowdot_accum(e->A2T, e->BP, e->dz0, dP + DP_FC4_W, 1024, e->BP, s);
-  launch_rowdot_accum(e->dz0, e->BP, nullptr, dP + DP_FC4_B, 1, e->BP, s);
-  // fc2: dW[n][k] += sum_b dA2T[n][b] A1T[k][b] (pose-major copies feed the K-major GEMM) ; db[n] += sum_b dA2T[n][b]
-  launch_transpose(e->dA2T, e->TrA, 1024, e->BP, s);
-  launch_transpose(e->A1T, e->TrB, 1024, e->BP, s);
-  GemmArgs g;
-  g.bias = nullptr; g.mask = nullptr; g.split_stride = 0;
-  // the pose dimension is the reduction: split it so that the 64 output tiles become >= 512 workgroups; partial
-  // slabs, then a wide accumulate-reduce into the flat gradient (deterministic, no atomics)
-  const int wsplit = e->BP >= 4096 ? 8 : e->BP >= 1024 ? 4 : e->BP >= 256 ? 2 : 1;
-  g.A = e->TrA; g.lda = 1024; g.Bm = e->TrB; g.ldb = 1024; g.Out = e->wgs; g.ldo = 1024; g.M = 1024; g.N = 1024; g.K = e->BP;
-  g.split_stride = (size_t)1024 * 1024;
-  rc = launch_gemm_128(g, EPI_STORE, wsplit, s);
-  if (rc) return rc;
-  launch_reduce_slabs(e->wgs, wsplit, (size_t)1024 * 1024, dP + DP_FC2_W, (size_t)1024 * 1024, s, 1);
-  g.split_stride = 0;
-  launch_rowdot_accum(e->dA2T, e->BP, nullptr, dP + DP_FC2_B, 1024, e->BP, s);
-  // back through fc2
-  g.A = e->Pd + DP_FC2_W; g.lda = 1024; g.Bm = e->dA2T; g.ldb = e->BP; g.Out = e->dA1T; g.ldo = e->BP; g.mask = e->A1T;
-  g.M = 1024; g.N = e->BP; g.K = 1024;
-  rc = launch_gemm_128x64(g, EPI_MASK, 1, s);
-  if (rc) return rc;
-  // fc0
-  launch_transpose(e->dA1T, e->TrA, 1024, e->BP, s);
-  launch_transpose(e->H2T, e->TrB, 768, e->BP, s);
-  g.mask = nullptr;
-  g.A = e->TrA; g.lda = 1024; g.Bm = e->TrB; g.ldb = 768; g.Out = e->wgs; g.ldo = 768; g.M = 1024; g.N = 768; g.K = e->BP;
-  g.split_stride = (size_t)1024 * 768;
-  rc = launch_gemm_128(g, EPI_STORE, wsplit, s);
-  if (rc) return rc;
-  launch_reduce_slabs(e->wgs, wsplit, (size_t)1024 * 768, dP + DP_FC0_W, (size_t)1024 * 768, s, 1);
-  g.split_stride = 0;
-  launch_rowdot_accum(e->dA1T, e->BP, nullptr, dP + DP_FC0_B, 1024, e->BP, s);
-  g.A = e->Pd + DP_FC0_W; g.lda = 768; g.Bm = e->dA1T; g.ldb = e->BP; g.Out = e->dH2T; g.ldo = e->BP; g.M = 768; g.N = e->BP; g.K = 1024;
-  rc = launch_gemm_128x64(g, EPI_STORE, 1, s);
-  if (rc) return rc;
-  {   // conv / head weight gradients: one slab per wave [pose group][joint][1280], reduced in two wide steps
-      // (over the pose groups, then over the joints) into the flat gradient
-    const int ng = e->BP / 64;
-    float* slab_shared = e->wgs;
-    float* slab_heads = slab_shared + (size_t)NJ * ng * 1280;
-    float* tmp = slab_heads + (size_t)ng * 792;
-    launch_disc_conv_bwd_params(e->Pd, x6d, e->dH2T, gout, scale, target, slab_shared, slab_heads, e->B, e->BP, s);
-    launch_reduce_slabs(slab_shared, ng, (size_t)NJ * 1280, tmp, (size_t)NJ * 1280, s, 0);
-    launch_reduce_slabs(tmp, NJ, 1280, dP + DP_CONV0_W, 1280, s, 1);
-    launch_reduce_slabs(slab_heads, ng, 792, dP + DP_HEADS, 792, s, 1);
-  }
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_pose_disc_backward_params(jrr_engine_t* e, const float* x6d, float target, float* dP, float* sqerr,
-                                             void* stream) {
-  if (!e || !x6d || !dP) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
-  return disc_backward_params(e, x6d, nullptr, (float)(2.0 / ((double)e->bnorm * 25.0)), target, dP, sqerr, (hipStream_t)stream);
-}
-
-extern "C" int jrr_pose_disc_vjp_params(jrr_engine_t* e, const float* x6d, const float* gout, float* dP, void* stream) {
-  if (!e || !x6d || !gout || !dP) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
-  return disc_backward_params(e, x6d, gout, 0.f, 0.f, dP, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int jrr_shape_disc_vjp_params(jrr_engine_t* e, const float* betas, const float* gout, float* dP, void* stream) {
-  if (!e || !betas || !gout || !dP) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
-  launch_shape_disc_bwd_params(e->Ps, betas, gout, 0.f, 0.f, dP, nullptr, e->B, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_shape_disc_backward_params(jrr_engine_t* e, const float* betas, float target, float* dP, float* sqerr,
-                                              void* stream) {
-  if (!e || !betas || !dP) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
-  const float scale = (float)(2.0 / ((double)e->bnorm * 1.0));
-  launch_shape_disc_bwd_params(e->Ps, betas, nullptr, scale, target, dP, sqerr, e->B, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_shape_disc_forward(jrr_engine_t* e, const float* betas, float* out, void* stream) {
-  if (!e || !betas || !out) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
-  launch_shape_disc(e->Ps, betas, out, nullptr, 0.f, 0.f, e->B, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_shape_disc_vjp_input(jrr_engine_t* e, const float* betas, const float* gout, float* dbetas, void* stream) {
-  if (!e || !betas || !gout || !dbetas) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
-  launch_shape_disc(e->Ps, betas, nullptr, dbetas, 0.f, 0.f, e->B, (hipStream_t)stream, gout);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_refine_aux_losses(jrr_engine_t* e, float* pose_disc_sq, float* shape_disc_sq, void* stream) {
-  if (!e) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  hipStream_t s = (hipStream_t)stream;
-  if (pose_disc_sq) {
-    if (!((e->flags & JRR_FLAG_POSE_DISC) && e->have_pd)) { jrr_set_error("pose discriminator term not active"); return JRR_ERR_STATE; }
-    launch_colsum(e->dsq, 25, e->BP, pose_disc_sq, e->B, s);
-  }
-  if (shape_disc_sq) {
-    if (!((e->flags & JRR_FLAG_SHAPE_DISC) && e->have_sd)) { jrr_set_error("shape discriminator term not active"); return JRR_ERR_STATE; }
-    JRR_HIP(hipMemcpyAsync(shape_disc_sq, e->ssq, (size_t)e->B * 4, hipMemcpyDeviceToDevice, s));
-  }
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
 extern "C" int jrr_adam_step(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step, float lr,
                              float beta1, float beta2, float eps, void* stream) {
   if (!p || !g || !m || !v || !step) return JRR_ERR_ARG;
   if (n == 0) return JRR_OK;
   launch_adam_flat(p, g, m, v, n, step, lr, beta1, beta2, eps, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_evaluate(const float* pred, const float* target_mm, float* err, float* err_pa, int batch, void* stream) {
-  if (!pred || !target_mm || !err || !err_pa || batch <= 0) return JRR_ERR_ARG;
-  launch_evaluate(pred, target_mm, err, err_pa, batch, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-/* the evaluation report (--eval_report / --eval_vertices): per-joint errors, joints of foreign meshes, the int64 accumulator */
-extern "C" int jrr_evaluate_joints(const float* pred, const float* target_mm, float* err_j, float* err_pa_j, int batch, void* stream) {
-  if (!pred || !target_mm || !err_j || !err_pa_j || batch < 0) {
-    jrr_set_error("jrr_evaluate_joints: bad argument");
-    return JRR_ERR_ARG;
-  }
-  if ((((uintptr_t)err_j | (uintptr_t)err_pa_j) & 15) != 0) {
-    jrr_set_error("jrr_evaluate_joints: err_j and err_pa_j must be 16-byte aligned");
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  launch_evaluate_joints(pred, target_mm, err_j, err_pa_j, batch, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-extern "C" size_t jrr_regress_joints_workspace_bytes(int n_reg) {
-  return (n_reg < 1 || n_reg > JRR_REGRESS_MAX_REG) ? 0 : regress_workspace_bytes(n_reg);
-}
-extern "C" int jrr_regress_joints_prepare(const float* J, int n_reg, const float* mask, void* workspace, size_t workspace_bytes,
-                                          void* stream) {
-  if (!J || !workspace || n_reg < 1 || n_reg > JRR_REGRESS_MAX_REG || ((uintptr_t)workspace & 15) != 0) {
-    jrr_set_error("jrr_regress_joints_prepare: bad argument (1 <= n_reg <= %d, workspace 16-byte aligned)", (int)JRR_REGRESS_MAX_REG);
-    return JRR_ERR_ARG;
-  }
-  if (workspace_bytes < regress_workspace_bytes(n_reg)) {
-    jrr_set_error("jrr_regress_joints_prepare: the workspace needs jrr_regress_joints_workspace_bytes(%d) = %zu bytes", n_reg,
-                  regress_workspace_bytes(n_reg));
-    return JRR_ERR_WORKSPACE;
-  }
-  launch_regress_prepare(J, mask, n_reg, workspace, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-extern "C" int jrr_regress_joints(const float* verts, int batch, const void* workspace, int n_reg, float* joints, void* stream) {
-  if (!verts || !workspace || !joints || batch < 0 || n_reg < 1 || n_reg > JRR_REGRESS_MAX_REG || ((uintptr_t)verts & 7) != 0 ||
-      ((uintptr_t)workspace & 15) != 0) {
-    jrr_set_error("jrr_regress_joints: bad argument (1 <= n_reg <= %d, verts 8-byte aligned)", (int)JRR_REGRESS_MAX_REG);
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  if (launch_regress_joints(verts, workspace, n_reg, joints, batch, (hipStream_t)stream) != 0) {
-    jrr_set_error("jrr_regress_joints: the device refuses %d bytes of LDS per workgroup", V * 3 * 4);
-    return JRR_ERR_HIP;
-  }
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-extern "C" int jrr_eval_accumulate(const float* err_j, const float* err_pa_j, const int32_t* group, int batch, int n_groups, int64_t* acc,
-                                   void* stream) {
-  if (!err_j || !err_pa_j || !group || !acc || batch < 0 || ((uintptr_t)acc & 7) != 0) {
-    jrr_set_error("jrr_eval_accumulate: bad argument");
-    return JRR_ERR_ARG;
-  }
-  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS) {
-    jrr_set_error("jrr_eval_accumulate: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  launch_eval_accumulate(err_j, err_pa_j, group, n_groups, acc, batch, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_regressor_shift_accumulate(const float* joints_a, const float* joints_b, const int32_t* group, int batch, int n_groups,
-                                              int64_t* acc, void* stream) {
-  if (!joints_a || !joints_b || !acc || batch < 0 || ((uintptr_t)acc & 7) != 0) {
-    jrr_set_error("jrr_regressor_shift_accumulate: bad argument");
-    return JRR_ERR_ARG;
-  }
-  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS) {
-    jrr_set_error("jrr_regressor_shift_accumulate: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  launch_shift_accumulate(joints_a, joints_b, group, n_groups, acc, batch, (hipStream_t)stream);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-extern "C" int jrr_draw_discs(uint8_t* rgb, int batch, int h, int w, const float* points, const float* radius_dev, float radius,
-                              const uint8_t* colours_host, int n_sets, int n_pts, void* stream) {
-  if (!rgb || !points || !colours_host || batch < 0 || h < 1 || w < 1 || (long long)h * w > (1ll << 28)) {
-    jrr_set_error("jrr_draw_discs: bad argument (h, w >= 1, h * w <= 2^28)");
-    return JRR_ERR_ARG;
-  }
-  if (n_sets < 1 || n_sets > JRR_DISCS_MAX_SETS || n_pts < 1 || n_pts > JRR_DISCS_MAX_POINTS) {
-    jrr_set_error("jrr_draw_discs: %d sets of %d points: 1 .. %d sets of 1 .. %d points", n_sets, n_pts, (int)JRR_DISCS_MAX_SETS,
-                  (int)JRR_DISCS_MAX_POINTS);
-    return JRR_ERR_ARG;
-  }
-  if ((long long)batch * (((long long)h * w + 255) / 256) > 0x7fffffffll) {
-    jrr_set_error("jrr_draw_discs: batch %d of %d x %d pictures: more workgroups than one launch takes", batch, h, w);
-    return JRR_ERR_ARG;
-  }
-  if (batch == 0) return JRR_OK;
-  launch_draw_discs(rgb, batch, h, w, points, radius_dev, radius, colours_host, n_sets, n_pts, (hipStream_t)stream);
   CHECK_LAUNCH();
   return JRR_OK;
 }
@@ -1120,90 +634,3 @@ extern "C" int jrr_camera_prefit(jrr_engine_t* e, const float* x6d, const float*
   CHECK_LAUNCH();
   return JRR_OK;
 }
-
-// =============================================================================================
-// soft silhouette (row f2)
-// =============================================================================================
-static int sil_check(jrr_engine* e) {
-  if (!(e->flags & JRR_FLAG_SILHOUETTE)) { jrr_set_error("engine created without JRR_FLAG_SILHOUETTE"); return JRR_ERR_STATE; }
-  if (!e->m.faces) { jrr_set_error("model has no faces (jrr_model_set_faces)"); return JRR_ERR_STATE; }
-  return 0;
-}
-
-extern "C" int jrr_silhouette_forward(jrr_engine_t* e, const float* verts, const float* cam, float* alpha, void* stream) {
-  if (!e || !verts || !cam || !alpha) return JRR_ERR_ARG;
-  int rc = sil_check(e);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
-  launch_sil_project(verts, V * 3, cam, e->ndc, e->B, s, e->sil);
-  launch_sil_raster(e->ndc, e->m.faces_pk, e->m.nfaces, e->cover, e->ncover, alpha, e->B, s, e->sil);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_silhouette_backward(jrr_engine_t* e, const float* galpha, float* dverts, float* dcam, void* stream) {
-  if (!e || !galpha || !dverts || !dcam) return JRR_ERR_ARG;
-  int rc = sil_check(e);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
-  launch_sil_bwd(e->ndc, e->m.faces, e->cover, e->ncover, nullptr, galpha, 0.f, dverts, V * 3, dcam, 0, e->B, s, e->sil);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_silhouette_pix_to_face(jrr_engine_t* e, int32_t* p2f, void* stream) {
-  if (!e || !p2f) return JRR_ERR_ARG;
-  int rc = sil_check(e);
-  if (rc) return rc;
-  launch_sil_pix_to_face(e->cover, e->ncover, p2f, e->B, (hipStream_t)stream, e->sil);
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-
-extern "C" int jrr_engine_set_silhouette(jrr_engine_t* e, const float* mask, float* cam, float* cam_m, float* cam_v) {
-  if (!e) return JRR_ERR_ARG;
-  e->fwd_cached = false;
-  if (mask) {
-    int rc = sil_check(e);
-    if (rc) return rc;
-    if (!cam || !cam_m || !cam_v) { jrr_set_error("set_silhouette: cam / cam_m / cam_v required"); return JRR_ERR_ARG; }
-    if (e->sil != 224 && e->sil != 256) {
-      jrr_set_error("set_silhouette: the silhouette term inside the loop is built for 224 x 224 and 256 x 256 images (this engine: %d); "
-                    "the other sizes serve the stand-alone renderer", e->sil);
-      return JRR_ERR_STATE;
-    }
-    e->cam = cam; e->cam_m = cam_m; e->cam_v = cam_v;
-  }
-  e->sil_mask = mask;
-  e->smask_valid = false;          // sum(mask^2) per pose: recomputed on the stream of the next jrr_refine_run
-  return JRR_OK;
-}
-
-// The silhouette term exactly as the fused inner loop evaluates it (k_sil_raster<true>: in-kernel projection from the
-// row-quad vertex buffer, packed fixed-point adjoint, write-back over the vertex pieces), as an operator: SMPL forward of
-// (x6d, betas), then loss and gradient w.r.t. the vertices and the camera.
-extern "C" int jrr_silhouette_loss_grad(jrr_engine_t* e, const float* x6d, const float* betas, const float* cam,
-                                        const float* mask, float* sqsil, float* dverts, float* dcam, void* stream) {
-  if (!e || !x6d || !betas || !cam || !mask) { jrr_set_error("silhouette_loss_grad: null"); return JRR_ERR_ARG; }
-  int rc = sil_check(e);
-  if (rc) return rc;
-  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
-  if (!e->VTb) { jrr_set_error("silhouette_loss_grad needs JRR_FLAG_KEEP_VERTS"); return JRR_ERR_STATE; }
-  hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
-  smpl_forward(e, x6d, nullptr, betas, true, true, nullptr, s, nullptr, nullptr, 0, true);      // vertices pose-major, as in the loop
-  launch_mask_sq(mask, e->smask, e->B, s, e->sil);
-  e->smask_valid = false;
-  const float silscale = (float)(2.0 * 100.0 / ((double)e->bnorm * (double)e->sil * (double)e->sil));      // optimize.py:252 weight 100
-  { int rcs = launch_sil_raster_adj(e->VTb, e->BP, cam, e->m.faces_int_pk ? e->m.faces_int_pk : e->m.faces_pk, e->m.nfaces, mask, e->smask, e->cover,
-                                    e->ncover, e->sqsil, silscale, e->gcam, 0, e->B, s, e->sil, e->VPM);
-    if (rcs) return rcs; }      // (sizes other than 224 / 256: the stand-alone forward / backward pair only)
-  if (sqsil) JRR_HIP(hipMemcpyAsync(sqsil, e->sqsil, (size_t)e->B * 4, hipMemcpyDeviceToDevice, s));
-  if (dverts) launch_verts_untranspose(e->VTb, dverts, V * 3, V, nullptr, nullptr, e->B, e->BP, s, e->m.p2v);
-  if (dcam) JRR_HIP(hipMemcpyAsync(dcam, e->gcam, (size_t)e->B * 3 * 4, hipMemcpyDeviceToDevice, s));
-  CHECK_LAUNCH();
-  return JRR_OK;
-}
-

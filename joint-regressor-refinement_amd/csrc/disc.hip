@@ -8,8 +8,7 @@
 //   linears.i.{w,b} 1280+33i (+32)          i = 0..23
 //   fc0.w 2072 (1024x768)  fc0.b 788504  fc2.w 789528 (1024x1024)  fc2.b 1838104
 //   fc4.w 1839128 (1x1024) fc4.b 1840152
-#include "jrr_common.h"
-#include "kernels.h"
+#include "engine.h"
 #include "dconv.h"
 
 namespace jrr {
@@ -56,7 +55,7 @@ __global__ void k_conv_image(const float* __restrict__ P, float* __restrict__ L)
   }
   for (int i = threadIdx.x; i < 24 * 33; i += blockDim.x) L[CL_WH + i] = P[DP_HEADS + i];
 }
-int launch_conv_image(const float* P, float* img, hipStream_t s) {
+static int launch_conv_image(const float* P, float* img, hipStream_t s) {
   hipLaunchKernelGGL(k_conv_image, dim3(1), dim3(256), 0, s, P, img);
   return 0;
 }
@@ -356,7 +355,7 @@ __global__ void k_disc_z_finish(const float* __restrict__ zpart, int nz, int ld,
   for (int t = 0; t < nz; ++t) z += zpart[(size_t)t * ld + b];
   out[(size_t)b * 25] = sigmoidf(z);
 }
-int launch_disc_z_finish(const float* zpart, int nz, int ld, const float* zbias, float* out, int B, hipStream_t s) {
+static int launch_disc_z_finish(const float* zpart, int nz, int ld, const float* zbias, float* out, int B, hipStream_t s) {
   hipLaunchKernelGGL(k_disc_z_finish, dim3((B + 255) / 256), dim3(256), 0, s, zpart, nz, ld, zbias, out, B);
   return 0;
 }
@@ -365,7 +364,7 @@ __global__ void k_scale_rows(const float* __restrict__ in, const float* __restri
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < (size_t)rows * cols) out[i] = w[i / cols] * in[i];
 }
-int launch_scale_rows(const float* in, const float* w, float* out, int rows, int cols, hipStream_t s) {
+static int launch_scale_rows(const float* in, const float* w, float* out, int rows, int cols, hipStream_t s) {
   hipLaunchKernelGGL(k_scale_rows, dim3((unsigned)(((size_t)rows * cols + 255) / 256)), dim3(256), 0, s, in, w, out, rows, cols);
   return 0;
 }
@@ -383,22 +382,24 @@ int launch_colsum(const float* M, int rows, int ld, float* out, int B, hipStream
   return 0;
 }
 
-int launch_rowdot_accum(const float* M, int ld, const float* vec, float* out, int rows, int cols, hipStream_t s) {
+static int launch_rowdot_accum(const float* M, int ld, const float* vec, float* out, int rows, int cols, hipStream_t s) {
   hipLaunchKernelGGL(k_rowdot_accum, dim3(rows), dim3(256), 0, s, M, ld, vec, out, cols);
   return 0;
 }
-int launch_disc_conv_bwd_params(const float* P, const float* x6d, const float* dH2T, const float* gout, float scale,
+// conv / per-joint-head weight gradients as partial slabs: shared [24 * BP/64][1280] (conv0 W,b | conv2 W,b in the
+// DP_* order) and heads [BP/64][792]; the caller reduces them into the flat gradient
+static int launch_disc_conv_bwd_params(const float* P, const float* x6d, const float* dH2T, const float* gout, float scale,
                                 float target, float* slab_shared, float* slab_heads, int B, int BP, hipStream_t s) {
   hipLaunchKernelGGL(k_disc_conv_bwd_params, dim3(BP / 64, NJ), dim3(64), 0, s, P, x6d, dH2T, gout, scale, target, slab_shared,
                      slab_heads, B, BP);
   return 0;
 }
-int launch_shape_disc_bwd_params(const float* P, const float* betas, const float* gout, float scale, float target,
+static int launch_shape_disc_bwd_params(const float* P, const float* betas, const float* gout, float scale, float target,
                                  float* dparams, float* sqerr, int B, hipStream_t s) {
   hipLaunchKernelGGL(k_shape_disc_bwd_params, dim3((B + 63) / 64), dim3(64), 0, s, P, betas, gout, scale, target, dparams, sqerr, B);
   return 0;
 }
-int launch_sqerr_rows(const float* out, int ncol, float target, float* sqerr, int B, hipStream_t s) {
+static int launch_sqerr_rows(const float* out, int ncol, float target, float* sqerr, int B, hipStream_t s) {
   hipLaunchKernelGGL(k_sqerr_rows, dim3((B + 255) / 256), dim3(256), 0, s, out, ncol, target, sqerr, B);
   return 0;
 }
@@ -426,8 +427,8 @@ int launch_disc_conv_fwd(const float* P, const float* x6d, float* H2T, float* ou
   else hipLaunchKernelGGL((k_dconv_fwd<false>), dim3((BP / 32) * 6), dim3(256), 0, s, P, x6d, H2T, out, B, BP);
   return 0;
 }
-int launch_disc_out(const float* P, const float* A2T, float* out, float* dA2T, const float* gout, float scale,
-                    float target, int B, int BP, hipStream_t s, float* dz0, float* sq0) {
+static int launch_disc_out(const float* P, const float* A2T, float* out, float* dA2T, const float* gout, float scale,
+                    float target, int B, int BP, hipStream_t s, float* dz0 = nullptr, float* sq0 = nullptr) {
   hipLaunchKernelGGL(k_disc_out, dim3(BP / 64), dim3(1024), 0, s, P, A2T, out, dA2T, gout, scale, target, B, BP, dz0, sq0);
   return 0;
 }
@@ -444,3 +445,225 @@ int launch_shape_disc(const float* P, const float* betas, float* out, float* gb,
 }
 
 }  // namespace jrr
+
+using namespace jrr;
+
+extern "C" int jrr_engine_set_pose_disc(jrr_engine_t* e, const float* P, void* stream) {
+  if (!e || !P) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!(e->flags & JRR_FLAG_POSE_DISC)) { jrr_set_error("engine created without JRR_FLAG_POSE_DISC"); return JRR_ERR_STATE; }
+  hipStream_t s = (hipStream_t)stream;
+  JRR_HIP(hipMemcpyAsync(e->Pd, P, (size_t)DP_TOTAL * 4, hipMemcpyDeviceToDevice, s));
+  launch_transpose(e->Pd + DP_FC0_W, e->W0T, 1024, 768, s);    // [out][in] -> [in][out]
+  launch_transpose(e->Pd + DP_FC2_W, e->W2T, 1024, 1024, s);
+  launch_scale_rows(e->Pd + DP_FC2_W, e->Pd + DP_FC4_W, e->W2s, 1024, 1024, s);   // row n of fc2.w times fc4.w[n]
+  launch_to_quads(e->W0T, 1024, e->W0Tq, 768, 1024, s);                // A operands A[k][m] of the four loop GEMMs, in quads
+  launch_to_quads(e->W2T, 1024, e->W2Tq, 1024, 1024, s);
+  launch_to_quads(e->W2s, 1024, e->W2sq, 1024, 1024, s);
+  launch_to_quads(e->Pd + DP_FC0_W, 768, e->W0q, 1024, 768, s);
+  launch_conv_image(e->Pd, e->convL, s);
+  CHECK_LAUNCH();
+  e->have_pd = true;
+  return JRR_OK;
+}
+
+extern "C" int jrr_engine_set_shape_disc(jrr_engine_t* e, const float* P, void* stream) {
+  if (!e || !P) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!(e->flags & JRR_FLAG_SHAPE_DISC)) { jrr_set_error("engine created without JRR_FLAG_SHAPE_DISC"); return JRR_ERR_STATE; }
+  JRR_HIP(hipMemcpyAsync(e->Ps, P, (size_t)JRR_SHAPE_DISC_PARAMS * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  e->have_sd = true;
+  return JRR_OK;
+}
+
+// ---- pose discriminator --------------------------------------------------------------------
+// Six launches per forward + input gradient (scripts/discriminator.py:32-54 and its adjoint):
+//   k_dconv_fwd (per-joint MLP, MFMA)  ->  fc0 GEMM (+bias, ReLU)  ->  fc2 GEMM (+bias, ReLU, the fc4 dot product
+//   w4 . a2 as per-column partials in the epilogue; what it stores is relu'(a2) as 0 / 1: nothing else of a2 is read again)
+//   ->  fc2 adjoint GEMM on that indicator (dz from the partial dots in the prologue multiplies the finished column sums
+//   in the epilogue; fc2.w pre-scaled by w4: the rank-one output-layer adjoint is never materialised)  ->  fc0 adjoint
+//   GEMM  ->  k_dconv_bwd.
+// All four GEMMs: exact 128x64 tiles (512 workgroups at 4096 poses), 3-deep LDS-DMA ring.
+// The loop path keeps every activation in quads [row/4][pose][4] (k_disc_gemm); the weight-gradient path of the outer
+// step (disc_backward_params) needs row-major activations for its transposes / row sums and runs the row-major kernels.
+// conv_done: the per-joint MLP already ran (fused into the chain-forward launch, launch_prep_fwd_dconv)
+int jrr::disc_forward(jrr_engine* e, const float* x6d, float* out, hipStream_t s, bool quad, bool conv_done) {
+  if (!conv_done) launch_disc_conv_fwd(e->convL, x6d, e->H2T, out, e->B, e->BP, s, quad ? 1 : 0);
+  GemmArgs g;
+  g.mask = nullptr; g.split_stride = 0; g.N = e->BP; g.ldb = e->BP; g.ldo = e->BP;
+  g.A = quad ? e->W0Tq : e->W0T; g.lda = 1024; g.Bm = e->H2T; g.Out = e->A1T; g.bias = e->Pd + DP_FC0_B; g.M = 1024; g.K = 768;
+  int rc = quad ? launch_disc_gemm_q(g, EPI_BIAS_RELU, 0, s) : launch_gemm_128x64(g, EPI_BIAS_RELU, 1, s);
+  if (rc) return rc;
+  g.A = quad ? e->W2Tq : e->W2T; g.lda = 1024; g.Bm = e->A1T; g.Out = e->A2T; g.bias = e->Pd + DP_FC2_B; g.M = 1024; g.K = 1024;
+  if (!quad) return launch_gemm_128x64(g, EPI_BIAS_RELU, 1, s);
+  g.dotw = e->Pd + DP_FC4_W; g.dot_out = e->zpart;
+  return launch_disc_gemm_q(g, EPI_BIAS_RELU_DOT, 0, s);
+}
+
+// skip_conv: the caller runs the per-joint MLP adjoint itself (fused with the dF^T slab sum, launch_dconv_bwd_reduce)
+int jrr::disc_backward_input(jrr_engine* e, const float* x6d, float* out, const float* gout, float scale, float target, float* gx,
+                             hipStream_t s, float* sq, bool skip_conv) {
+  GemmArgs g;
+  g.bias = nullptr; g.split_stride = 0; g.N = e->BP; g.ldb = e->BP; g.ldo = e->BP;
+  // dA1T[k][b] = relu'(A1T) * sum_n (fc4.w[n] fc2.w[n][k]) relu'(A2T[n][b]) dz[b]
+  g.A = e->W2sq; g.lda = 1024; g.Bm = e->A2T; g.Out = e->dA1T; g.mask = e->A1T; g.M = 1024; g.K = 1024;
+  g.zpart = e->zpart; g.nzpart = 16; g.zbias = e->Pd + DP_FC4_B; g.gout = gout; g.gout_ld = 25; g.scale = scale; g.target = target;
+  g.nvalid = e->B; g.sq0 = sq; g.out0 = out; g.out0_ld = 25;
+  int rc = launch_disc_gemm_q(g, EPI_MASK, 2, s);
+  if (rc) return rc;
+  // dH2T[k][b] = sum_n fc0.w[n][k] dA1T[n][b]
+  GemmArgs h;
+  h.bias = nullptr; h.split_stride = 0; h.N = e->BP; h.ldb = e->BP; h.ldo = e->BP;
+  h.A = e->W0q; h.lda = 768; h.Bm = e->dA1T; h.Out = e->dH2T; h.mask = nullptr; h.M = 768; h.K = 1024;
+  rc = launch_disc_gemm_q(h, EPI_STORE, 0, s);
+  if (rc) return rc;
+  if (!skip_conv) launch_disc_conv_bwd(e->convL, x6d, e->dH2T, gout, scale, target, gx, e->B, e->BP, s, sq, 1);
+  return 0;
+}
+
+extern "C" int jrr_pose_disc_forward(jrr_engine_t* e, const float* x6d, float* out, void* stream) {
+  if (!e || !x6d || !out) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
+  hipStream_t s = (hipStream_t)stream;
+  int rc = disc_forward(e, x6d, out, s);
+  if (rc) return rc;
+  launch_disc_z_finish(e->zpart, 16, e->BP, e->Pd + DP_FC4_B, out, e->B, s);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
+extern "C" int jrr_pose_disc_backward_input(jrr_engine_t* e, const float* x6d, float weight, float target, float* dx,
+                                            void* stream) {
+  if (!e || !x6d || !dx) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
+  const float scale = (float)(2.0 * (double)weight / ((double)e->bnorm * 25.0));
+  int rc = disc_backward_input(e, x6d, nullptr, nullptr, scale, target, dx, (hipStream_t)stream);
+  if (rc) return rc;
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
+extern "C" int jrr_pose_disc_vjp_input(jrr_engine_t* e, const float* x6d, const float* gout, float* dx, void* stream) {
+  if (!e || !x6d || !gout || !dx) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
+  int rc = disc_backward_input(e, x6d, nullptr, gout, 0.f, 0.f, dx, (hipStream_t)stream);
+  if (rc) return rc;
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
+// weight gradients of the pose discriminator: either of the MSE against `target` (gout == NULL; scale = 2/(bnorm*25))
+// or the vector-Jacobian product for an arbitrary upstream gradient gout (B,25)
+static int disc_backward_params(jrr_engine* e, const float* x6d, const float* gout, float scale, float target, float* dP,
+                                float* sqerr, hipStream_t s) {
+  int rc = disc_forward(e, x6d, e->dsc, s, false);        // row-major activations for the transposes / row sums below
+  if (rc) return rc;
+  launch_disc_out(e->Pd, e->A2T, e->dsc, e->dA2T, gout, scale, target, e->B, e->BP, s, e->dz0);
+  if (sqerr) launch_sqerr_rows(e->dsc, 25, target, sqerr, e->B, s);
+  // fc4: dw[n] += sum_b A2T[n][b] dz0[b] ; db += sum_b dz0[b]
+  launch_rowdot_accum(e->A2T, e->BP, e->dz0, dP + DP_FC4_W, 1024, e->BP, s);
+  launch_rowdot_accum(e->dz0, e->BP, nullptr, dP + DP_FC4_B, 1, e->BP, s);
+  // fc2: dW[n][k] += sum_b dA2T[n][b] A1T[k][b] (pose-major copies feed the K-major GEMM) ; db[n] += sum_b dA2T[n][b]
+  launch_transpose(e->dA2T, e->TrA, 1024, e->BP, s);
+  launch_transpose(e->A1T, e->TrB, 1024, e->BP, s);
+  GemmArgs g;
+  g.bias = nullptr; g.mask = nullptr; g.split_stride = 0;
+  // the pose dimension is the reduction: split it so that the 64 output tiles become >= 512 workgroups; partial
+  // slabs, then a wide accumulate-reduce into the flat gradient (deterministic, no atomics)
+  const int wsplit = e->BP >= 4096 ? 8 : e->BP >= 1024 ? 4 : e->BP >= 256 ? 2 : 1;
+  g.A = e->TrA; g.lda = 1024; g.Bm = e->TrB; g.ldb = 1024; g.Out = e->wgs; g.ldo = 1024; g.M = 1024; g.N = 1024; g.K = e->BP;
+  g.split_stride = (size_t)1024 * 1024;
+  rc = launch_gemm_128(g, EPI_STORE, wsplit, s);
+  if (rc) return rc;
+  launch_reduce_slabs(e->wgs, wsplit, (size_t)1024 * 1024, dP + DP_FC2_W, (size_t)1024 * 1024, s, 1);
+  g.split_stride = 0;
+  launch_rowdot_accum(e->dA2T, e->BP, nullptr, dP + DP_FC2_B, 1024, e->BP, s);
+  // back through fc2
+  g.A = e->Pd + DP_FC2_W; g.lda = 1024; g.Bm = e->dA2T; g.ldb = e->BP; g.Out = e->dA1T; g.ldo = e->BP; g.mask = e->A1T;
+  g.M = 1024; g.N = e->BP; g.K = 1024;
+  rc = launch_gemm_128x64(g, EPI_MASK, 1, s);
+  if (rc) return rc;
+  // fc0
+  launch_transpose(e->dA1T, e->TrA, 1024, e->BP, s);
+  launch_transpose(e->H2T, e->TrB, 768, e->BP, s);
+  g.mask = nullptr;
+  g.A = e->TrA; g.lda = 1024; g.Bm = e->TrB; g.ldb = 768; g.Out = e->wgs; g.ldo = 768; g.M = 1024; g.N = 768; g.K = e->BP;
+  g.split_stride = (size_t)1024 * 768;
+  rc = launch_gemm_128(g, EPI_STORE, wsplit, s);
+  if (rc) return rc;
+  launch_reduce_slabs(e->wgs, wsplit, (size_t)1024 * 768, dP + DP_FC0_W, (size_t)1024 * 768, s, 1);
+  g.split_stride = 0;
+  launch_rowdot_accum(e->dA1T, e->BP, nullptr, dP + DP_FC0_B, 1024, e->BP, s);
+  g.A = e->Pd + DP_FC0_W; g.lda = 768; g.Bm = e->dA1T; g.ldb = e->BP; g.Out = e->dH2T; g.ldo = e->BP; g.M = 768; g.N = e->BP; g.K = 1024;
+  rc = launch_gemm_128x64(g, EPI_STORE, 1, s);
+  if (rc) return rc;
+  {   // conv / head weight gradients: one slab per wave [pose group][joint][1280], reduced in two wide steps
+      // (over the pose groups, then over the joints) into the flat gradient
+    const int ng = e->BP / 64;
+    float* slab_shared = e->wgs;
+    float* slab_heads = slab_shared + (size_t)NJ * ng * 1280;
+    float* tmp = slab_heads + (size_t)ng * 792;
+    launch_disc_conv_bwd_params(e->Pd, x6d, e->dH2T, gout, scale, target, slab_shared, slab_heads, e->B, e->BP, s);
+    launch_reduce_slabs(slab_shared, ng, (size_t)NJ * 1280, tmp, (size_t)NJ * 1280, s, 0);
+    launch_reduce_slabs(tmp, NJ, 1280, dP + DP_CONV0_W, 1280, s, 1);
+    launch_reduce_slabs(slab_heads, ng, 792, dP + DP_HEADS, 792, s, 1);
+  }
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
+extern "C" int jrr_pose_disc_backward_params(jrr_engine_t* e, const float* x6d, float target, float* dP, float* sqerr,
+                                             void* stream) {
+  if (!e || !x6d || !dP) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
+  return disc_backward_params(e, x6d, nullptr, (float)(2.0 / ((double)e->bnorm * 25.0)), target, dP, sqerr, (hipStream_t)stream);
+}
+
+extern "C" int jrr_pose_disc_vjp_params(jrr_engine_t* e, const float* x6d, const float* gout, float* dP, void* stream) {
+  if (!e || !x6d || !gout || !dP) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
+  return disc_backward_params(e, x6d, gout, 0.f, 0.f, dP, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int jrr_shape_disc_vjp_params(jrr_engine_t* e, const float* betas, const float* gout, float* dP, void* stream) {
+  if (!e || !betas || !gout || !dP) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
+  launch_shape_disc_bwd_params(e->Ps, betas, gout, 0.f, 0.f, dP, nullptr, e->B, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
+extern "C" int jrr_shape_disc_backward_params(jrr_engine_t* e, const float* betas, float target, float* dP, float* sqerr,
+                                              void* stream) {
+  if (!e || !betas || !dP) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
+  const float scale = (float)(2.0 / ((double)e->bnorm * 1.0));
+  launch_shape_disc_bwd_params(e->Ps, betas, nullptr, scale, target, dP, sqerr, e->B, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
+extern "C" int jrr_shape_disc_forward(jrr_engine_t* e, const float* betas, float* out, void* stream) {
+  if (!e || !betas || !out) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
+  launch_shape_disc(e->Ps, betas, out, nullptr, 0.f, 0.f, e->B, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
+extern "C" int jrr_shape_disc_vjp_input(jrr_engine_t* e, const float* betas, const float* gout, float* dbetas, void* stream) {
+  if (!e || !betas || !gout || !dbetas) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
+  launch_shape_disc(e->Ps, betas, nullptr, dbetas, 0.f, 0.f, e->B, (hipStream_t)stream, gout);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}

@@ -1,19 +1,12 @@
-// Internal (never installed): the engine's state and the host helpers shared by the translation units behind include/jrr.h --
-// model.hip (body-model re-layout), api.hip (engine lifecycle, operator wrappers), refine.hip (fused inner loop, J step).
+// Internal (never installed): the engine's state and the host helpers shared by the translation units that work on an engine --
+// model.hip (body-model re-layout), api.hip (knobs, engine lifecycle and workspace, regressor upload, SMPL operators), refine.hip (fused
+// inner loop, J step), disc.hip (discriminator operators and parameter upload), sil.hip (silhouette operators).  The engine-less feature
+// files need jrr_common.h only.
 #pragma once
 #include <vector>
 
 #include "jrr_common.h"
 #include "kernels.h"
-
-#define CHECK_LAUNCH()                                                            \
-  do {                                                                            \
-    hipError_t _e = hipGetLastError();                                            \
-    if (_e != hipSuccess) {                                                       \
-      jrr_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
-      return JRR_ERR_HIP;                                                         \
-    }                                                                             \
-  } while (0)
 
 struct jrr_engine {
   jrr::Model m;
@@ -117,6 +110,8 @@ int smpl_forward(jrr_engine* e, const float* x6d, const float* R, const float* b
                  hipStream_t s, const int* vmask = nullptr, const int* tl = nullptr, int ntl = 0, bool verts_pm = false);
 int blend_adjoint_gemm(jrr_engine* e, hipStream_t s, const int* tl = nullptr, int ntl = 0, int nsplit = 0);
 int fold_rebuild(jrr_engine* e, hipStream_t s);
+
+// ---- disc.hip ----
 // conv_done: the per-joint MLP already ran (fused into the chain-forward launch, launch_prep_fwd_dconv)
 int disc_forward(jrr_engine* e, const float* x6d, float* out, hipStream_t s, bool quad = true, bool conv_done = false);
 // skip_conv: the caller runs the per-joint MLP adjoint itself (fused with the dF^T slab sum, launch_dconv_bwd_reduce)

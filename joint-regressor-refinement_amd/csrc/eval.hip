@@ -3,7 +3,6 @@
 //   batch_compute_similarity_transform_torch   /root/reference/scripts/eval_utils.py:7-58
 // One pose per thread; the body is evalk.h's, shared with the per-joint kernel of evalrep.hip.
 #include "jrr_common.h"
-#include "kernels.h"
 #include "evalk.h"
 
 namespace jrr {
@@ -29,9 +28,13 @@ __global__ __launch_bounds__(64) void k_evaluate(const float* __restrict__ pred,
 #undef JRR_EVAL_PA_END
 }
 
-int launch_evaluate(const float* pred, const float* target_mm, float* err, float* err_pa, int B, hipStream_t s) {
-  hipLaunchKernelGGL(k_evaluate, dim3((B + 63) / 64), dim3(64), 0, s, pred, target_mm, err, err_pa, B);
-  return 0;
-}
-
 }  // namespace jrr
+
+using namespace jrr;
+
+extern "C" int jrr_evaluate(const float* pred, const float* target_mm, float* err, float* err_pa, int batch, void* stream) {
+  if (!pred || !target_mm || !err || !err_pa || batch <= 0) return JRR_ERR_ARG;
+  hipLaunchKernelGGL(k_evaluate, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, pred, target_mm, err, err_pa, batch);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}

@@ -25,7 +25,6 @@
 //                        of include/jrr.h (JRR_EVAL_ACC_*), int64, integer atomics only: independent of order, of the split into calls
 //                        and of the sharding over ranks.
 #include "jrr_common.h"
-#include "kernels.h"
 #include "evalk.h"
 #include "../../include/jrr.h"
 
@@ -73,12 +72,6 @@ __global__ __launch_bounds__(EJ_POSES) void k_evaluate_joints(const float* __res
   }
 }
 
-int launch_evaluate_joints(const float* pred, const float* target_mm, float* err_j, float* err_pa_j, int B, hipStream_t s) {
-  hipLaunchKernelGGL(k_evaluate_joints, dim3((unsigned)((B + EJ_POSES - 1) / EJ_POSES)), dim3(EJ_POSES), 0, s, pred, target_mm, err_j,
-                     err_pa_j, B);
-  return 0;
-}
-
 // ---- regress: workspace = int32 head[RG_HEAD] | float vals[n_reg][17][V] | int32 cols[n_reg][17][V] -----------------------------
 constexpr int RG_HEAD = 128;                       // head[r * 17 + j] = entries of row j of regressor r (at most 4 * 17 = 68 used)
 constexpr int RG_THREADS = 256;
@@ -86,7 +79,7 @@ constexpr int RG_CHUNK = (V + RG_THREADS - 1) / RG_THREADS;      // 27 consecuti
 constexpr int RG_SPARSE_MAX = 64;                  // longest list k_regress_joints<false> takes: one entry per lane
 static_assert(JRR_REGRESS_MAX_REG * NH <= RG_HEAD, "the head holds every row's count");
 
-size_t regress_workspace_bytes(int n_reg) { return (size_t)RG_HEAD * 4 + (size_t)n_reg * NH * V * 8; }
+static size_t regress_workspace_bytes(int n_reg) { return (size_t)RG_HEAD * 4 + (size_t)n_reg * NH * V * 8; }
 
 __device__ __forceinline__ float* rg_vals(void* ws) { return reinterpret_cast<float*>(reinterpret_cast<int*>(ws) + RG_HEAD); }
 __device__ __forceinline__ const float* rg_vals(const void* ws) {
@@ -130,11 +123,6 @@ __global__ __launch_bounds__(RG_THREADS) void k_regress_prepare(const float* __r
     if (!(x <= 0.f)) { vals[at] = x / total; cols[at] = c; ++at; }
   }
   if (tid == RG_THREADS - 1) reinterpret_cast<int*>(ws)[r * NH + j] = s_cnt[tid];
-}
-
-int launch_regress_prepare(const float* J, const float* mask, int n_reg, void* ws, hipStream_t s) {
-  hipLaunchKernelGGL(k_regress_prepare, dim3(NH, n_reg), dim3(RG_THREADS), 0, s, J, mask, n_reg, ws);
-  return 0;
 }
 
 // grid: one workgroup of 4 waves per pose.  USE_LDS selects the vertex source and which lists this instantiation works on.
@@ -185,13 +173,14 @@ __global__ __launch_bounds__(RG_THREADS) void k_regress_joints(const float* __re
   }
 }
 
-bool regress_attributes() {
+static bool regress_attributes() {
   static const bool ok = hipFuncSetAttribute((const void*)k_regress_joints<true>, hipFuncAttributeMaxDynamicSharedMemorySize, V * 3 * 4) ==
                          hipSuccess;
   return ok;
 }
 
-int launch_regress_joints(const float* verts, const void* ws, int n_reg, float* joints, int B, hipStream_t s) {
+// joints (n_reg,B,17,3) <- normalised regressors of ws x verts (B,6890,3); -1 when the device refuses the LDS the dense path needs
+static int launch_regress_joints(const float* verts, const void* ws, int n_reg, float* joints, int B, hipStream_t s) {
   if (!regress_attributes()) return -1;
   hipLaunchKernelGGL(k_regress_joints<false>, dim3((unsigned)B), dim3(RG_THREADS), 0, s, verts, ws, n_reg, joints, B);
   hipLaunchKernelGGL(k_regress_joints<true>, dim3((unsigned)B), dim3(RG_THREADS), V * 3 * 4, s, verts, ws, n_reg, joints, B);
@@ -234,11 +223,71 @@ __global__ __launch_bounds__(256) void k_eval_accumulate(const float* __restrict
   }
 }
 
-int launch_eval_accumulate(const float* err_j, const float* err_pa_j, const int32_t* group, int n_groups, int64_t* acc, int B,
-                           hipStream_t s) {
-  hipLaunchKernelGGL(k_eval_accumulate, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, err_j, err_pa_j, group, n_groups,
-                     reinterpret_cast<long long*>(acc), B);
-  return 0;
-}
-
 }  // namespace jrr
+
+using namespace jrr;
+
+/* the evaluation report (--eval_report / --eval_vertices): per-joint errors, joints of foreign meshes, the int64 accumulator */
+extern "C" int jrr_evaluate_joints(const float* pred, const float* target_mm, float* err_j, float* err_pa_j, int batch, void* stream) {
+  if (!pred || !target_mm || !err_j || !err_pa_j || batch < 0) {
+    jrr_set_error("jrr_evaluate_joints: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if ((((uintptr_t)err_j | (uintptr_t)err_pa_j) & 15) != 0) {
+    jrr_set_error("jrr_evaluate_joints: err_j and err_pa_j must be 16-byte aligned");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  hipLaunchKernelGGL(k_evaluate_joints, dim3((unsigned)((batch + EJ_POSES - 1) / EJ_POSES)), dim3(EJ_POSES), 0, (hipStream_t)stream, pred, target_mm,
+                     err_j, err_pa_j, batch);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" size_t jrr_regress_joints_workspace_bytes(int n_reg) {
+  return (n_reg < 1 || n_reg > JRR_REGRESS_MAX_REG) ? 0 : regress_workspace_bytes(n_reg);
+}
+extern "C" int jrr_regress_joints_prepare(const float* J, int n_reg, const float* mask, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+  if (!J || !workspace || n_reg < 1 || n_reg > JRR_REGRESS_MAX_REG || ((uintptr_t)workspace & 15) != 0) {
+    jrr_set_error("jrr_regress_joints_prepare: bad argument (1 <= n_reg <= %d, workspace 16-byte aligned)", (int)JRR_REGRESS_MAX_REG);
+    return JRR_ERR_ARG;
+  }
+  if (workspace_bytes < regress_workspace_bytes(n_reg)) {
+    jrr_set_error("jrr_regress_joints_prepare: the workspace needs jrr_regress_joints_workspace_bytes(%d) = %zu bytes", n_reg,
+                  regress_workspace_bytes(n_reg));
+    return JRR_ERR_WORKSPACE;
+  }
+  hipLaunchKernelGGL(k_regress_prepare, dim3(NH, n_reg), dim3(RG_THREADS), 0, (hipStream_t)stream, J, mask, n_reg, workspace);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_regress_joints(const float* verts, int batch, const void* workspace, int n_reg, float* joints, void* stream) {
+  if (!verts || !workspace || !joints || batch < 0 || n_reg < 1 || n_reg > JRR_REGRESS_MAX_REG || ((uintptr_t)verts & 7) != 0 ||
+      ((uintptr_t)workspace & 15) != 0) {
+    jrr_set_error("jrr_regress_joints: bad argument (1 <= n_reg <= %d, verts 8-byte aligned)", (int)JRR_REGRESS_MAX_REG);
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  if (launch_regress_joints(verts, workspace, n_reg, joints, batch, (hipStream_t)stream) != 0) {
+    jrr_set_error("jrr_regress_joints: the device refuses %d bytes of LDS per workgroup", V * 3 * 4);
+    return JRR_ERR_HIP;
+  }
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_eval_accumulate(const float* err_j, const float* err_pa_j, const int32_t* group, int batch, int n_groups, int64_t* acc,
+                                   void* stream) {
+  if (!err_j || !err_pa_j || !group || !acc || batch < 0 || ((uintptr_t)acc & 7) != 0) {
+    jrr_set_error("jrr_eval_accumulate: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS) {
+    jrr_set_error("jrr_eval_accumulate: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  hipLaunchKernelGGL(k_eval_accumulate, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, err_j, err_pa_j, group, n_groups,
+                     reinterpret_cast<long long*>(acc), batch);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}

@@ -16,7 +16,6 @@
 //   240-float rows of include/jrr.h (JRR_EXPORT_*) are assembled in LDS and scattered into the table by dataset index, 16 bytes per
 //   lane along the row.  676 B read and 960 B written per pose; no engine, no engine state.
 #include "jrr_common.h"
-#include "kernels.h"
 #include "rot6.h"
 #include "../../include/jrr.h"
 
@@ -78,11 +77,6 @@ __global__ __launch_bounds__(256) void k_rotmat_log(const float* __restrict__ R,
   for (int k = 0; k < 3; ++k) aa[(size_t)i * 3 + k] = a[k];
 }
 
-int launch_rotmat_log(const float* R, float* aa, int n, hipStream_t s) {
-  hipLaunchKernelGGL(k_rotmat_log, dim3((n + 255) / 256), dim3(256), 0, s, R, aa, n);
-  return 0;
-}
-
 // grid: ceil(B / 8) workgroups of 192 threads; thread (p, j) owns joint j of pose 8 * blockIdx + p and float 216 + j of its row
 __global__ __launch_bounds__(EX_THREADS) void k_pose_export(const float* __restrict__ x6d, const float* __restrict__ betas,
                                                             const float* __restrict__ cam, const float* __restrict__ extra, int n_extra,
@@ -141,11 +135,38 @@ __global__ __launch_bounds__(EX_THREADS) void k_pose_export(const float* __restr
   }
 }
 
-int launch_pose_export(const float* x6d, const float* betas, const float* cam, const float* extra, int n_extra, const int64_t* index,
-                       float* table, int64_t n_rows, int32_t* status, int B, hipStream_t s) {
-  hipLaunchKernelGGL(k_pose_export, dim3((unsigned)((B + EX_POSES - 1) / EX_POSES)), dim3(EX_THREADS), 0, s, x6d, betas, cam, extra, n_extra,
-                     reinterpret_cast<const long long*>(index), table, (long long)n_rows, status, B);
-  return 0;
-}
-
 }  // namespace jrr
+
+using namespace jrr;
+
+/* the log map and the refined-pose table (--save_refined) */
+extern "C" int jrr_rotmat_to_axis_angle(const float* R, float* aa, int n, void* stream) {
+  if (!R || !aa || n < 0) {
+    jrr_set_error("jrr_rotmat_to_axis_angle: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (n == 0) return JRR_OK;
+  hipLaunchKernelGGL(k_rotmat_log, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, R, aa, n);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_pose_export(const float* x6d, const float* betas, const float* cam, const float* extra, int n_extra, const int64_t* index,
+                               float* table, int64_t n_rows, int32_t* status, int batch, void* stream) {
+  if (!x6d || !betas || !cam || !index || !table || !status || batch < 0 || n_rows < 0) {
+    jrr_set_error("jrr_pose_export: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (n_extra < 0 || n_extra > JRR_EXPORT_MAX_EXTRA) {
+    jrr_set_error("jrr_pose_export: n_extra %d: 0 .. %d", n_extra, (int)JRR_EXPORT_MAX_EXTRA);
+    return JRR_ERR_ARG;
+  }
+  if (((uintptr_t)table & 15) != 0 || ((uintptr_t)x6d & 7) != 0 || ((uintptr_t)index & 7) != 0 || ((uintptr_t)status & 3) != 0) {
+    jrr_set_error("jrr_pose_export: the table must be 16-byte aligned (x6d and index 8-byte, status 4-byte)");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  hipLaunchKernelGGL(k_pose_export, dim3((unsigned)((batch + EX_POSES - 1) / EX_POSES)), dim3(EX_THREADS), 0, (hipStream_t)stream, x6d, betas, cam,
+                     n_extra > 0 ? extra : nullptr, n_extra, reinterpret_cast<const long long*>(index), table, (long long)n_rows, status, batch);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}

@@ -12,10 +12,11 @@
 // host side operation by operation, each one rounded once (mul_rn() keeps a product from being fused into the addition that follows), so that
 // host and kernel agree on every tap index: the host uploads only the block of each frame that its crops can touch.
 #include "jrr_common.h"
-#include "kernels.h"
 
 namespace jrr {
 
+constexpr int IC_MAX_SIZE = 256;       // largest crop (pixels per side; sizes are multiples of 4)
+constexpr int IC_MAX_ROI_W = 1024;     // widest block of a frame a sample may hand over (pixels; frames are cut to 1000 x 1000)
 constexpr int IC_ROWS = 4;                        // output rows per workgroup
 constexpr int IC_SLOTS = 2 * IC_ROWS;             // staged source rows
 constexpr int IC_ROWBYTES = 3 * IC_MAX_ROI_W + 32;  // a span of IC_MAX_ROI_W pixels starting anywhere in a 16-byte chunk, rounded up to chunks
@@ -168,7 +169,10 @@ __global__ __launch_bounds__(IC_THREADS) void k_image_crop(ImageCropArgs a) {
   if (err) atomicOr(a.status, err);
 }
 
-int launch_image_crop(const uint8_t* pix, size_t pix_bytes, const int64_t* desc, const float* bbox, int B, const float* mean,
+// status bits of k_image_crop (ORed into *status, never cleared by the kernel): 1 = a tap of non-zero weight inside the frame but
+// outside the sample's block (nothing is read there), 2 = a descriptor that does not fit the pixel buffer (the sample reads nothing)
+// desc [B][8] = {byte offset, row pitch, roi_y0, roi_x0, roi_h, roi_w, frame_H, frame_W}; pix 16-byte aligned, pix_bytes % 16 == 0
+static int launch_image_crop(const uint8_t* pix, size_t pix_bytes, const int64_t* desc, const float* bbox, int B, const float* mean,
                       const float* stdv, int n0, float* out0, int n1, float* out1, int* status, hipStream_t s) {
   ImageCropArgs a;
   a.pix = pix; a.pix_bytes = (long long)pix_bytes; a.desc = reinterpret_cast<const long long*>(desc); a.bbox = bbox;
@@ -206,10 +210,39 @@ __global__ __launch_bounds__(256) void k_mask_prepare(const uint8_t* __restrict_
   }
 }
 
-int launch_mask_prepare(const uint8_t* masks, int B, int h, int w, float* out, int* valid, hipStream_t s) {
-  const size_t total = (size_t)B * h * w;
-  hipLaunchKernelGGL(k_mask_prepare, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, s, masks, out, valid, B, h, w);
-  return 0;
-}
-
 }  // namespace jrr
+
+using namespace jrr;
+
+/* find_crop on uint8 frames (scripts/data.py:220-271) and the mask preparation (scripts/data.py:121,130-132) */
+extern "C" int jrr_image_crop(const uint8_t* pix, size_t pix_bytes, const int64_t* desc, const float* bboxes, int batch, const float* mean,
+                              const float* stdv, int size0, float* out0, int size1, float* out1, int32_t* status, void* stream) {
+  if (!pix || !desc || !bboxes || !out0 || !status || batch < 0 || batch > 65535 || (size1 != 0 && !out1) || ((mean == nullptr) != (stdv == nullptr))) {
+    jrr_set_error("jrr_image_crop: bad argument");
+    return JRR_ERR_ARG;
+  }
+  auto bad_size = [](int n) { return n < 4 || n > IC_MAX_SIZE || n % 4 != 0; };
+  if (bad_size(size0) || (size1 != 0 && bad_size(size1))) {
+    jrr_set_error("jrr_image_crop: crop sizes %d, %d: one or two sizes, multiples of 4, at most %d", size0, size1, IC_MAX_SIZE);
+    return JRR_ERR_ARG;
+  }
+  if (((uintptr_t)pix & 15) != 0 || pix_bytes % 16 != 0 || pix_bytes == 0) {
+    jrr_set_error("jrr_image_crop: the pixel buffer must be 16-byte aligned and a non-zero multiple of 16 bytes long");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_image_crop(pix, pix_bytes, desc, bboxes, batch, mean, stdv, size0, out0, size1, out1, status, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_mask_prepare(const uint8_t* masks, int batch, int h, int w, float* out, int32_t* valid, void* stream) {
+  if (!masks || !out || !valid || batch < 0 || h <= 0 || w <= 0 || (((uintptr_t)masks | (uintptr_t)out) & 15) != 0) {
+    jrr_set_error("jrr_mask_prepare: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  const size_t total = (size_t)batch * h * w;
+  hipLaunchKernelGGL(k_mask_prepare, dim3((unsigned)((total + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, masks, out, valid, batch, h, w);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}

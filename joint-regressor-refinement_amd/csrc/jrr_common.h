@@ -215,3 +215,11 @@ void jrr_set_error(const char* fmt, ...);
       return JRR_ERR_HIP;                                                             \
     }                                                                                 \
   } while (0)
+#define CHECK_LAUNCH()                                                            \
+  do {                                                                            \
+    hipError_t _e = hipGetLastError();                                            \
+    if (_e != hipSuccess) {                                                       \
+      jrr_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(_e), __FILE__, __LINE__); \
+      return JRR_ERR_HIP;                                                         \
+    }                                                                             \
+  } while (0)

@@ -1,4 +1,7 @@
-// Internal launcher interface between the host translation units (api.hip, model.hip, refine.hip: engine.h) and the kernel translation units.
+// Internal launcher interface: the launch_* functions that cross a translation unit, i.e. the kernels of prep / lbs / gemm / sup / fold
+// and the few of disc / sil that the engine (api.hip) and the fused loop (refine.hip) launch.  A launcher with no caller outside the file
+// of its kernel is static there and is not listed; the feature files (image, report, shade, export, eval, evalrep, regrep, smooth) keep
+// their include/jrr.h entry points beside their kernels and declare nothing here.
 #pragma once
 #include "jrr_common.h"
 
@@ -121,7 +124,6 @@ int launch_jgrad_sparse(const JSupport& sup, const float* dJT, const float* VTq,
 // joints of the stored vertices with the current regressor, one slab [3][32][BP] (rows i < 17), support entries only
 // step_inc (nullable): incremented by one thread of the launch (the reuse iteration's Adam step count: one launch less)
 int launch_rejoints_sparse(const JSupport& sup, const float* VTq, float* out, int BP, hipStream_t s, int32_t* step_inc = nullptr);
-int launch_jsup_tilemask(const JSupport& sup, hipStream_t s);
 int launch_jsup_scatter(const JSupport& sup, const float* in, const int* p2v, float* dJ, hipStream_t s);
 // sup / p2v / dJs (nullable): also deliver the gradient on the support lists, dJs [17][JSUP_CAP]
 int launch_jreg_bwd(const float* J, const float* mask, const float* Jn, const float* rowsum, const float* dJn, int ldn,
@@ -155,23 +157,15 @@ int launch_gemm_q32(const float* A, int ldA, size_t planeA, const float* Bm, int
                     const int* skip_flag = nullptr);
 int launch_jgrad_q(const float* dJT, const float* VTq, float* Out, int BP, int ksplit, hipStream_t s, const int* skip_flag = nullptr);
 
-// sil.hip
-// S = image size (224 or 256; focal length 5000 / S)
-int launch_sil_project(const float* verts, int ldv, const float* cam, float* ndc, int B, hipStream_t s, int S = 224);
-// cover [B][S*S] / ncover [B]: the covered pixels of each pose (pixel << 14 | winning face), written by the
-// rasteriser and consumed by the adjoint
-int launch_sil_raster(const float* ndc, const unsigned* faces_pk, int nfaces, unsigned* cover, int* ncover, float* alpha, int B,
-                      hipStream_t s, int S = 224);
+// sil.hip (the two launchers of the loop's silhouette term; S = image size, 224 or 256, focal length 5000 / S)
 // smask [B] = per-pose sum(mask^2) over the image (launch_mask_sq): the rasteriser only visits the mesh's pixel box
 int launch_mask_sq(const float* mask, float* smask, int B, hipStream_t s, int S = 224);
 int launch_sil_raster_adj(float* VQ, int BP, const float* cam, const unsigned* faces_pk, int nfaces, const float* mask, const float* smask,
                           unsigned* cover, int* ncover, float* sqsil, float scale, float* gcam, int accumulate_cam, int B,
                           hipStream_t s, int S = 224, const float* VPM = nullptr);
 // VPM (nullable): the vertices pose-major [BP][3][VP] (launch_lbs_fwd with verts_pose_major); NULL: read from the row quads of VQ
-int launch_sil_pix_to_face(const unsigned* cover, const int* ncover, int* p2f, int B, hipStream_t s, int S = 224);
-int launch_sil_bwd(const float* ndc, const int* faces, const unsigned* cover, const int* ncover, const float* mask,
-                   const float* galpha, float scale, float* dverts, int ldv, float* gcam, int accumulate_cam, int B,
-                   hipStream_t s, int S = 224);
+// cover [B][S*S] / ncover [B]: the covered pixels of each pose (pixel << 14 | winning face), written by the rasteriser and consumed by
+// the adjoint
 
 // sup.hip / supk.h: the joint-loss iteration on the regressor's support VERTICES, one workgroup per 32-pose group
 constexpr int SUP_NSV = 64;       // most support vertices the fused iteration is built for (192 coordinate rows)
@@ -211,88 +205,12 @@ int launch_fold_fwd(const float* MT, const float* AT, const float* G0, float* Js
 int launch_fold_bwd(const float* dJT, const float* AT, const float* MT, const float* G0, float* dMT, float* dA, int BP,
                     hipStream_t s);
 
-// eval.hip
-int launch_evaluate(const float* pred, const float* target_mm, float* err, float* err_pa, int B, hipStream_t s);
-
-// evalrep.hip
-// the per-joint distances behind launch_evaluate's means; err_j / err_pa_j (B,17), 16-byte aligned
-int launch_evaluate_joints(const float* pred, const float* target_mm, float* err_j, float* err_pa_j, int B, hipStream_t s);
-size_t regress_workspace_bytes(int n_reg);
-int launch_regress_prepare(const float* J, const float* mask, int n_reg, void* ws, hipStream_t s);
-// joints (n_reg,B,17,3) <- normalised regressors of ws x verts (B,6890,3); -1 when the device refuses the LDS the dense path needs
-int launch_regress_joints(const float* verts, const void* ws, int n_reg, float* joints, int B, hipStream_t s);
-int launch_eval_accumulate(const float* err_j, const float* err_pa_j, const int32_t* group, int n_groups, int64_t* acc, int B,
-                           hipStream_t s);
-
-// regrep.hip
-// ADD the body-frame displacements joints_b - joints_a (B,17,3) to rows `group` (nullable: group 0) of the int64 table acc
-// (include/jrr.h, JRR_SHIFT_ACC_*)
-int launch_shift_accumulate(const float* ja, const float* jb, const int32_t* group, int n_groups, int64_t* acc, int B, hipStream_t s);
-// filled discs into rgb (B,h,w,3) uint8: pts (n_sets,B,n_pts,2), rad (n_sets,B,n_pts) or nullptr (then `radius`), colours [n_sets][3] host
-int launch_draw_discs(uint8_t* rgb, int B, int h, int w, const float* pts, const float* rad, float radius, const uint8_t* colours,
-                      int n_sets, int n_pts, hipStream_t s);
-
-// image.hip
-constexpr int IC_MAX_SIZE = 256;       // largest crop (pixels per side; sizes are multiples of 4)
-constexpr int IC_MAX_ROI_W = 1024;     // widest block of a frame a sample may hand over (pixels; frames are cut to 1000 x 1000)
-// status bits of k_image_crop (ORed into *status, never cleared by the kernel): 1 = a tap of non-zero weight inside the frame but
-// outside the sample's block (nothing is read there), 2 = a descriptor that does not fit the pixel buffer (the sample reads nothing)
-// desc [B][8] = {byte offset, row pitch, roi_y0, roi_x0, roi_h, roi_w, frame_H, frame_W}; pix 16-byte aligned, pix_bytes % 16 == 0
-int launch_image_crop(const uint8_t* pix, size_t pix_bytes, const int64_t* desc, const float* bbox, int B, const float* mean,
-                      const float* stdv, int n0, float* out0, int n1, float* out1, int* status, hipStream_t s);
-int launch_mask_prepare(const uint8_t* masks, int B, int h, int w, float* out, int* valid, hipStream_t s);
-
-// report.hip
-// counts [B][4] = {render & mask, render | mask, render, mask} pixel counts, ADDED to what counts holds; h * w % 4 == 0
-int launch_sil_compare(const float* alpha, const float* mask, int B, int h, int w, float thr_r, float thr_m, int32_t* counts, hipStream_t s);
-// rgb (B,size,size,3) uint8; image / mean + stdv / j2d nullable (j2d with n_sets = 0); size % 4 == 0, at most 256
-int launch_fit_overlay(const float* alpha, const float* mask, const float* image, const float* mean, const float* stdv, const float* j2d,
-                       int n_sets, int B, int size, float thr_r, float thr_m, float radius, uint8_t* rgb, hipStream_t s);
-
-// shade.hip
-// normals (B,V,3) = the area-weighted sum of the face normals at each vertex over its CSR list adj_offset [V + 1] / adj_face [3 F], unit length
-int launch_vertex_normals(const float* verts, const int32_t* faces, const int32_t* adj_offset, const int32_t* adj_face, float* normals,
-                          int B, int V, int F, hipStream_t s);
-// rgb (B,size,size,3) uint8 of the shaded mesh behind p2f (B,size,size); image / mean + stdv / depth / normal / status nullable;
-// colour and light [3] host values; size % 4 == 0, at most 256
-int launch_mesh_shade(const float* verts, const float* normals, const int32_t* faces, const float* cam, const int32_t* p2f, const float* image,
-                      const float* mean, const float* stdv, int B, int V, int F, int size, const float* colour, float opacity, float ambient,
-                      const float* light, float background, uint8_t* rgb, float* depth, float* normal, int32_t* status, hipStream_t s);
-
-// export.hip
-// the log map R (n,3,3) -> axis-angle (n,3), angle in [0, pi] (include/jrr.h, jrr_rotmat_to_axis_angle)
-int launch_rotmat_log(const float* R, float* aa, int n, hipStream_t s);
-// rows of JRR_EXPORT_ROW floats scattered into table (n_rows rows, 16-byte aligned) by index; extra nullable, 0 <= n_extra <= 10
-int launch_pose_export(const float* x6d, const float* betas, const float* cam, const float* extra, int n_extra, const int64_t* index,
-                       float* table, int64_t n_rows, int32_t* status, int B, hipStream_t s);
-
-// smooth.hip
-// the time-axis filter over a refined-pose table and the jitter of it (include/jrr.h, jrr_pose_smooth / jrr_pose_jitter); positions
-// [begin, begin + count) of the m listed ones, 0 <= radius <= 16, x6d_out 16-byte aligned
-int launch_pose_smooth(const float* table, int64_t n_rows, const int32_t* order, const int32_t* run, int M, const float* weights, int radius,
-                       int begin, int count, float* x6d_out, float* betas_out, float* cam_out, float* delta_deg, int32_t* status, hipStream_t s);
-int launch_pose_jitter(const float* table, int64_t n_rows, const int32_t* order, const int32_t* run, int M, int begin, int count,
-                       float* jitter_deg, int32_t* status, hipStream_t s);
-
-// disc.hip
+// disc.hip (the pose / shape discriminator operators and the engine's parameter upload sit in disc.hip itself)
 int launch_transpose(const float* in, float* out, int rows, int cols, hipStream_t s, int ldin = 0, int ldout = 0);
 constexpr int CONV_IMAGE_FLOATS = 4224;     // LDS parameter image of the per-joint MLP kernels (disc.hip CL_*), rounded up
-int launch_conv_image(const float* P, float* img, hipStream_t s);
 // (the per-joint MLP launchers take the IMAGE, not the flat parameter vector)
 int launch_disc_conv_fwd(const float* P, const float* x6d, float* H2T, float* out, int B, int BP, hipStream_t s, int quad = 0);
-int launch_disc_out(const float* P, const float* A2T, float* out, float* dA2T, const float* gout, float scale,
-                    float target, int B, int BP, hipStream_t s, float* dz0 = nullptr, float* sq0 = nullptr);
-int launch_disc_z_finish(const float* zpart, int nz, int ld, const float* zbias, float* out, int B, hipStream_t s);
-int launch_scale_rows(const float* in, const float* w, float* out, int rows, int cols, hipStream_t s);
 int launch_colsum(const float* M, int rows, int ld, float* out, int B, hipStream_t s);
-int launch_rowdot_accum(const float* M, int ld, const float* vec, float* out, int rows, int cols, hipStream_t s);
-// conv / per-joint-head weight gradients as partial slabs: shared [24 * BP/64][1280] (conv0 W,b | conv2 W,b in the
-// DP_* order) and heads [BP/64][792]; the caller reduces them into the flat gradient
-int launch_disc_conv_bwd_params(const float* P, const float* x6d, const float* dH2T, const float* gout, float scale,
-                                float target, float* slab_shared, float* slab_heads, int B, int BP, hipStream_t s);
-int launch_shape_disc_bwd_params(const float* P, const float* betas, const float* gout, float scale, float target,
-                                 float* dparams, float* sqerr, int B, hipStream_t s);
-int launch_sqerr_rows(const float* out, int ncol, float target, float* sqerr, int B, hipStream_t s);
 int launch_disc_conv_bwd(const float* P, const float* x6d, const float* dH2T, const float* gout, float scale,
                          float target, float* gx, int B, int BP, hipStream_t s, float* sqj = nullptr, int quad = 0);
 int launch_shape_disc(const float* P, const float* betas, float* out, float* gb, float scale, float target, int B,

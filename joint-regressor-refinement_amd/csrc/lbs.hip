@@ -1362,7 +1362,7 @@ __global__ __launch_bounds__(256) void k_jsup_tilemask(JSupport sup) {
   }
   if (known && threadIdx.x == 0 && sup.flag[0] == 0) atomicOr(&sup.flag[JSUP_ERR], 2);
 }
-int launch_jsup_tilemask(const JSupport& sup, hipStream_t s) {
+static int launch_jsup_tilemask(const JSupport& sup, hipStream_t s) {
   hipLaunchKernelGGL(k_jsup_tilemask, dim3(1), dim3(256), 0, s, sup);
   return 0;
 }

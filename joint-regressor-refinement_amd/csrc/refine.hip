@@ -412,6 +412,22 @@ extern "C" int jrr_refine_run_j_steps(jrr_engine_t* e, float* x6d, float* betas,
   return refine_run_impl(e, x6d, betas, gt_mm, adam_m, adam_v, step, lr, n_iters, sqerr, (after_j_step & 1) != 0, &js, stream);
 }
 
+extern "C" int jrr_refine_aux_losses(jrr_engine_t* e, float* pose_disc_sq, float* shape_disc_sq, void* stream) {
+  if (!e) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  hipStream_t s = (hipStream_t)stream;
+  if (pose_disc_sq) {
+    if (!((e->flags & JRR_FLAG_POSE_DISC) && e->have_pd)) { jrr_set_error("pose discriminator term not active"); return JRR_ERR_STATE; }
+    launch_colsum(e->dsq, 25, e->BP, pose_disc_sq, e->B, s);
+  }
+  if (shape_disc_sq) {
+    if (!((e->flags & JRR_FLAG_SHAPE_DISC) && e->have_sd)) { jrr_set_error("shape discriminator term not active"); return JRR_ERR_STATE; }
+    JRR_HIP(hipMemcpyAsync(shape_disc_sq, e->ssq, (size_t)e->B * 4, hipMemcpyDeviceToDevice, s));
+  }
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
 // =============================================================================================
 // J step (scripts/optimize.py:300-312)
 // =============================================================================================

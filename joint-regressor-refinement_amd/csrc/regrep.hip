@@ -13,7 +13,6 @@
 // Every floating-point operation is stated in include/jrr.h and rounded once, in the order written (no product is fused into a sum), so
 // a host restatement follows it.
 #include "jrr_common.h"
-#include "kernels.h"
 #include "../../include/jrr.h"
 
 namespace jrr {
@@ -102,12 +101,6 @@ __global__ __launch_bounds__(RR_THREADS) void k_shift_accumulate(const float* __
   }
 }
 
-int launch_shift_accumulate(const float* ja, const float* jb, const int32_t* group, int n_groups, int64_t* acc, int B, hipStream_t s) {
-  hipLaunchKernelGGL(k_shift_accumulate, dim3((unsigned)((B + RR_THREADS - 1) / RR_THREADS)), dim3(RR_THREADS), 0, s, ja, jb, group,
-                     n_groups, reinterpret_cast<long long*>(acc), B);
-  return 0;
-}
-
 struct DiscArgs {
   uint8_t* rgb; const float* pts; const float* rad; float radius;
   int B, h, w, n_sets, n_pts;
@@ -146,7 +139,7 @@ __global__ __launch_bounds__(RR_THREADS) void k_draw_discs(DiscArgs a, int nblk)
   o[0] = a.colour[set][0]; o[1] = a.colour[set][1]; o[2] = a.colour[set][2];
 }
 
-int launch_draw_discs(uint8_t* rgb, int B, int h, int w, const float* pts, const float* rad, float radius, const uint8_t* colours,
+static int launch_draw_discs(uint8_t* rgb, int B, int h, int w, const float* pts, const float* rad, float radius, const uint8_t* colours,
                       int n_sets, int n_pts, hipStream_t s) {
   DiscArgs a;
   a.rgb = rgb; a.pts = pts; a.rad = rad; a.radius = radius; a.B = B; a.h = h; a.w = w; a.n_sets = n_sets; a.n_pts = n_pts;
@@ -158,3 +151,42 @@ int launch_draw_discs(uint8_t* rgb, int B, int h, int w, const float* pts, const
 }
 
 }  // namespace jrr
+
+using namespace jrr;
+
+extern "C" int jrr_regressor_shift_accumulate(const float* joints_a, const float* joints_b, const int32_t* group, int batch, int n_groups,
+                                              int64_t* acc, void* stream) {
+  if (!joints_a || !joints_b || !acc || batch < 0 || ((uintptr_t)acc & 7) != 0) {
+    jrr_set_error("jrr_regressor_shift_accumulate: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS) {
+    jrr_set_error("jrr_regressor_shift_accumulate: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  hipLaunchKernelGGL(k_shift_accumulate, dim3((unsigned)((batch + RR_THREADS - 1) / RR_THREADS)), dim3(RR_THREADS), 0, (hipStream_t)stream, joints_a,
+                     joints_b, group, n_groups, reinterpret_cast<long long*>(acc), batch);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_draw_discs(uint8_t* rgb, int batch, int h, int w, const float* points, const float* radius_dev, float radius,
+                              const uint8_t* colours_host, int n_sets, int n_pts, void* stream) {
+  if (!rgb || !points || !colours_host || batch < 0 || h < 1 || w < 1 || (long long)h * w > (1ll << 28)) {
+    jrr_set_error("jrr_draw_discs: bad argument (h, w >= 1, h * w <= 2^28)");
+    return JRR_ERR_ARG;
+  }
+  if (n_sets < 1 || n_sets > JRR_DISCS_MAX_SETS || n_pts < 1 || n_pts > JRR_DISCS_MAX_POINTS) {
+    jrr_set_error("jrr_draw_discs: %d sets of %d points: 1 .. %d sets of 1 .. %d points", n_sets, n_pts, (int)JRR_DISCS_MAX_SETS,
+                  (int)JRR_DISCS_MAX_POINTS);
+    return JRR_ERR_ARG;
+  }
+  if ((long long)batch * (((long long)h * w + 255) / 256) > 0x7fffffffll) {
+    jrr_set_error("jrr_draw_discs: batch %d of %d x %d pictures: more workgroups than one launch takes", batch, h, w);
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_draw_discs(rgb, batch, h, w, points, radius_dev, radius, colours_host, n_sets, n_pts, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}

@@ -11,7 +11,6 @@
 // 16-byte loads of alpha, mask and the three image planes; the pose's joints wait in LDS.  Every operation is stated in include/jrr.h
 // and rounded once (no product is fused into an addition), so a host restatement reproduces every byte.
 #include "jrr_common.h"
-#include "kernels.h"
 
 namespace jrr {
 
@@ -62,7 +61,8 @@ __global__ __launch_bounds__(RP_THREADS) void k_sil_compare(const float* __restr
   }
 }
 
-int launch_sil_compare(const float* alpha, const float* mask, int B, int h, int w, float thr_r, float thr_m, int32_t* counts, hipStream_t s) {
+// counts [B][4] = {render & mask, render | mask, render, mask} pixel counts, ADDED to what counts holds; h * w % 4 == 0
+static int launch_sil_compare(const float* alpha, const float* mask, int B, int h, int w, float thr_r, float thr_m, int32_t* counts, hipStream_t s) {
   const int nq = h * w / 4;
   const int per = RP_THREADS * SC_QUADS_PER_THREAD;
   const int want = (nq + per - 1) / per, nblk = want < 64 ? want : 64;
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(RP_THREADS) void k_fit_overlay(OverlayArgs a, int n
     out[d] = (unsigned)o[4 * d] | ((unsigned)o[4 * d + 1] << 8) | ((unsigned)o[4 * d + 2] << 16) | ((unsigned)o[4 * d + 3] << 24);
 }
 
-int launch_fit_overlay(const float* alpha, const float* mask, const float* image, const float* mean, const float* stdv, const float* j2d,
+static int launch_fit_overlay(const float* alpha, const float* mask, const float* image, const float* mean, const float* stdv, const float* j2d,
                        int n_sets, int B, int size, float thr_r, float thr_m, float radius, uint8_t* rgb, hipStream_t s) {
   OverlayArgs a;
   a.alpha = alpha; a.mask = mask; a.image = image; a.mean = mean; a.stdv = stdv; a.j2d = j2d; a.n_sets = n_sets;
@@ -165,3 +165,44 @@ int launch_fit_overlay(const float* alpha, const float* mask, const float* image
 }
 
 }  // namespace jrr
+
+using namespace jrr;
+
+/* the fit report: viz() of scripts/optimize.py:35-48 around the inner loop (:204-218, :268-274) */
+extern "C" int jrr_silhouette_compare(const float* alpha, const float* mask, int batch, int h, int w, float thr_render, float thr_mask,
+                                      int32_t* counts, void* stream) {
+  if (!alpha || !mask || !counts || batch < 0 || batch > (1 << 24) || h <= 0 || w <= 0 || (long long)h * w > (1LL << 30)) {
+    jrr_set_error("jrr_silhouette_compare: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (((long long)h * w) % 4 != 0 || (((uintptr_t)alpha | (uintptr_t)mask) & 15) != 0 || ((uintptr_t)counts & 3) != 0) {
+    jrr_set_error("jrr_silhouette_compare: %d x %d: h * w must be a multiple of 4 and the images 16-byte aligned", h, w);
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  JRR_HIP(hipMemsetAsync(counts, 0, (size_t)batch * 4 * sizeof(int32_t), (hipStream_t)stream));
+  launch_sil_compare(alpha, mask, batch, h, w, thr_render, thr_mask, counts, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_fit_overlay(const float* alpha, const float* mask, const float* image, const float* mean, const float* stdv,
+                               const float* joints2d, int n_sets, int batch, int size, float thr_render, float thr_mask, float radius,
+                               uint8_t* rgb, void* stream) {
+  if (!alpha || !mask || !rgb || batch < 0 || batch > (1 << 24) || n_sets < 0 || n_sets > 3 || (n_sets > 0 && !joints2d) ||
+      ((mean == nullptr) != (stdv == nullptr)) || (mean && !image)) {
+    jrr_set_error("jrr_fit_overlay: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (size < 4 || size > 256 || size % 4 != 0) {
+    jrr_set_error("jrr_fit_overlay: size %d: a multiple of 4, at most 256", size);
+    return JRR_ERR_ARG;
+  }
+  if ((((uintptr_t)alpha | (uintptr_t)mask | (uintptr_t)image) & 15) != 0 || ((uintptr_t)rgb & 3) != 0) {
+    jrr_set_error("jrr_fit_overlay: alpha, mask and image must be 16-byte aligned, the output 4-byte aligned");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_fit_overlay(alpha, mask, image, mean, stdv, joints2d, n_sets, batch, size, thr_render, thr_mask, radius, rgb, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}

@@ -14,7 +14,6 @@
 // restatement follows it.  Every index read from device memory -- adjacency offsets, face indices, vertex indices, pix_to_face -- is
 // checked against its array before it is used: nothing is read outside the arrays whatever the data.
 #include "jrr_common.h"
-#include "kernels.h"
 
 namespace jrr {
 
@@ -53,14 +52,6 @@ __global__ __launch_bounds__(SH_THREADS) void k_vertex_normals(const float* __re
   const float d = len < 1e-6f ? 1e-6f : len;                    // torch's clamp(min = 1e-6): a NaN stays a NaN (fmaxf would drop it)
   float* o = normals + (size_t)idx * 3;
   o[0] = sx / d; o[1] = sy / d; o[2] = sz / d;
-}
-
-int launch_vertex_normals(const float* verts, const int32_t* faces, const int32_t* adj_offset, const int32_t* adj_face, float* normals,
-                          int B, int V, int F, hipStream_t s) {
-  const long long n = (long long)B * V;
-  hipLaunchKernelGGL(k_vertex_normals, dim3((unsigned)((n + SH_THREADS - 1) / SH_THREADS)), dim3(SH_THREADS), 0, s, verts, faces, adj_offset,
-                     adj_face, normals, B, V, F);
-  return 0;
 }
 
 struct ShadeArgs {
@@ -184,7 +175,7 @@ __global__ __launch_bounds__(SH_THREADS) void k_mesh_shade(ShadeArgs a, int nblk
   if (bits != 0 && a.status != nullptr) atomicOr(a.status, bits);
 }
 
-int launch_mesh_shade(const float* verts, const float* normals, const int32_t* faces, const float* cam, const int32_t* p2f, const float* image,
+static int launch_mesh_shade(const float* verts, const float* normals, const int32_t* faces, const float* cam, const int32_t* p2f, const float* image,
                       const float* mean, const float* stdv, int B, int V, int F, int size, const float* colour, float opacity, float ambient,
                       const float* light, float background, uint8_t* rgb, float* depth, float* normal, int32_t* status, hipStream_t s) {
   ShadeArgs a;
@@ -198,3 +189,50 @@ int launch_mesh_shade(const float* verts, const float* normals, const int32_t* f
 }
 
 }  // namespace jrr
+
+using namespace jrr;
+
+/* the fit report's shaded views (--fit_report_mesh): no engine, no body model */
+extern "C" int jrr_vertex_normals(const float* verts, const int32_t* faces, const int32_t* adj_offset, const int32_t* adj_face, int batch,
+                                  int n_verts, int n_faces, float* normals, void* stream) {
+  if (!verts || !faces || !adj_offset || !adj_face || !normals || batch < 0 || n_verts < 1 || n_faces < 1 || n_faces > (1 << 28) ||
+      (long long)batch * n_verts > (1LL << 30)) {
+    jrr_set_error("jrr_vertex_normals: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if ((((uintptr_t)verts | (uintptr_t)faces | (uintptr_t)adj_offset | (uintptr_t)adj_face | (uintptr_t)normals) & 3) != 0) {
+    jrr_set_error("jrr_vertex_normals: every array must be 4-byte aligned");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  const long long n = (long long)batch * n_verts;
+  hipLaunchKernelGGL(k_vertex_normals, dim3((unsigned)((n + SH_THREADS - 1) / SH_THREADS)), dim3(SH_THREADS), 0, (hipStream_t)stream, verts, faces,
+                     adj_offset, adj_face, normals, batch, n_verts, n_faces);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_mesh_shade(const float* verts, const float* normals, const int32_t* faces, const float* cam, const int32_t* pix_to_face,
+                              const float* image, const float* mean, const float* stdv, int batch, int n_verts, int n_faces, int size,
+                              const float* colour_host, float opacity, float ambient, const float* light_host, float background,
+                              uint8_t* rgb, float* depth, float* normal, int32_t* status, void* stream) {
+  if (!verts || !normals || !faces || !cam || !pix_to_face || !colour_host || !light_host || !rgb || batch < 0 || batch > (1 << 24) ||
+      n_verts < 1 || n_faces < 1 || n_faces > (1 << 28) || (long long)batch * n_verts > (1LL << 30) ||
+      ((mean == nullptr) != (stdv == nullptr)) || (mean && !image)) {
+    jrr_set_error("jrr_mesh_shade: bad argument");
+    return JRR_ERR_ARG;
+  }
+  if (size < 4 || size > 256 || size % 4 != 0) {
+    jrr_set_error("jrr_mesh_shade: size %d: a multiple of 4, at most 256", size);
+    return JRR_ERR_ARG;
+  }
+  if ((((uintptr_t)pix_to_face | (uintptr_t)image | (uintptr_t)depth | (uintptr_t)normal) & 15) != 0 ||
+      (((uintptr_t)verts | (uintptr_t)normals | (uintptr_t)faces | (uintptr_t)cam | (uintptr_t)rgb | (uintptr_t)status) & 3) != 0) {
+    jrr_set_error("jrr_mesh_shade: pix_to_face, image, depth and normal must be 16-byte aligned, everything else 4-byte aligned");
+    return JRR_ERR_ARG;
+  }
+  if (batch == 0) return JRR_OK;
+  launch_mesh_shade(verts, normals, faces, cam, pix_to_face, image, mean, stdv, batch, n_verts, n_faces, size, colour_host, opacity, ambient,
+                    light_host, background, rgb, depth, normal, status, (hipStream_t)stream);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}

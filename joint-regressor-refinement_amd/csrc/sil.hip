@@ -19,8 +19,7 @@
 //   k_sil_bwd      per pose: the same adjoint for an arbitrary upstream gradient (standalone API), from the list
 // Measured costs that shaped this (MI355X): LDS float atomics retire ~1 lane per 2.5 clocks (so: 4 per covered
 // pixel, NDC space, not 6 in world space); the face sweep is VALU-bound (max-over-lanes bounding box trips).
-#include "jrr_common.h"
-#include "kernels.h"
+#include "engine.h"
 
 namespace jrr {
 
@@ -637,7 +636,7 @@ __global__ void k_sil_pix_to_face(const unsigned* __restrict__ cover, const int*
     out[e >> SIL_FBITS] = (int)(e & ((1u << SIL_FBITS) - 1));
   }
 }
-int launch_sil_pix_to_face(const unsigned* cover, const int* ncover, int* p2f, int B, hipStream_t s, int S) {
+static int launch_sil_pix_to_face(const unsigned* cover, const int* ncover, int* p2f, int B, hipStream_t s, int S) {
   hipLaunchKernelGGL(k_sil_pix_to_face, dim3(B), dim3(1024), 0, s, cover, ncover, p2f, S);
   return 0;
 }
@@ -665,11 +664,11 @@ static int sil_size_ok(int S, bool in_loop = false) {
   else jrr_set_error("silhouette: image size %d (the stand-alone renderer takes the multiples of 32 up to 256)", S);
   return JRR_ERR_ARG;
 }
-int launch_sil_project(const float* verts, int ldv, const float* cam, float* ndc, int B, hipStream_t s, int S) {
+static int launch_sil_project(const float* verts, int ldv, const float* cam, float* ndc, int B, hipStream_t s, int S) {
   hipLaunchKernelGGL(k_sil_project, dim3((B * V + 255) / 256), dim3(256), 0, s, verts, ldv, cam, (NdcV*)ndc, B, 5000.f / (float)S);
   return 0;
 }
-int launch_sil_raster(const float* ndc, const unsigned* faces_pk, int nfaces, unsigned* cover, int* ncover, float* alpha, int B,
+static int launch_sil_raster(const float* ndc, const unsigned* faces_pk, int nfaces, unsigned* cover, int* ncover, float* alpha, int B,
                       hipStream_t s, int S) {
   sil_attrs();
   if (sil_size_ok(S)) return JRR_ERR_ARG;
@@ -705,7 +704,7 @@ int launch_sil_raster_adj(float* VQ, int BP, const float* cam, const unsigned* f
   return 0;
 }
 // writes ALL of dverts[b][0 .. 6890*3) (no zero-fill needed); gcam: overwrite or accumulate
-int launch_sil_bwd(const float* ndc, const int* faces, const unsigned* cover, const int* ncover, const float* mask,
+static int launch_sil_bwd(const float* ndc, const int* faces, const unsigned* cover, const int* ncover, const float* mask,
                    const float* galpha, float scale, float* dverts, int ldv, float* gcam, int accumulate_cam, int B,
                    hipStream_t s, int S) {
   sil_attrs();
@@ -723,3 +722,88 @@ int launch_sil_bwd(const float* ndc, const int* faces, const unsigned* cover, co
 }
 
 }  // namespace jrr
+
+using namespace jrr;
+
+static int sil_check(jrr_engine* e) {
+  if (!(e->flags & JRR_FLAG_SILHOUETTE)) { jrr_set_error("engine created without JRR_FLAG_SILHOUETTE"); return JRR_ERR_STATE; }
+  if (!e->m.faces) { jrr_set_error("model has no faces (jrr_model_set_faces)"); return JRR_ERR_STATE; }
+  return 0;
+}
+
+extern "C" int jrr_silhouette_forward(jrr_engine_t* e, const float* verts, const float* cam, float* alpha, void* stream) {
+  if (!e || !verts || !cam || !alpha) return JRR_ERR_ARG;
+  int rc = sil_check(e);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  e->fwd_cached = false;
+  launch_sil_project(verts, V * 3, cam, e->ndc, e->B, s, e->sil);
+  launch_sil_raster(e->ndc, e->m.faces_pk, e->m.nfaces, e->cover, e->ncover, alpha, e->B, s, e->sil);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
+extern "C" int jrr_silhouette_backward(jrr_engine_t* e, const float* galpha, float* dverts, float* dcam, void* stream) {
+  if (!e || !galpha || !dverts || !dcam) return JRR_ERR_ARG;
+  int rc = sil_check(e);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  e->fwd_cached = false;
+  launch_sil_bwd(e->ndc, e->m.faces, e->cover, e->ncover, nullptr, galpha, 0.f, dverts, V * 3, dcam, 0, e->B, s, e->sil);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
+extern "C" int jrr_silhouette_pix_to_face(jrr_engine_t* e, int32_t* p2f, void* stream) {
+  if (!e || !p2f) return JRR_ERR_ARG;
+  int rc = sil_check(e);
+  if (rc) return rc;
+  launch_sil_pix_to_face(e->cover, e->ncover, p2f, e->B, (hipStream_t)stream, e->sil);
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+
+extern "C" int jrr_engine_set_silhouette(jrr_engine_t* e, const float* mask, float* cam, float* cam_m, float* cam_v) {
+  if (!e) return JRR_ERR_ARG;
+  e->fwd_cached = false;
+  if (mask) {
+    int rc = sil_check(e);
+    if (rc) return rc;
+    if (!cam || !cam_m || !cam_v) { jrr_set_error("set_silhouette: cam / cam_m / cam_v required"); return JRR_ERR_ARG; }
+    if (e->sil != 224 && e->sil != 256) {
+      jrr_set_error("set_silhouette: the silhouette term inside the loop is built for 224 x 224 and 256 x 256 images (this engine: %d); "
+                    "the other sizes serve the stand-alone renderer", e->sil);
+      return JRR_ERR_STATE;
+    }
+    e->cam = cam; e->cam_m = cam_m; e->cam_v = cam_v;
+  }
+  e->sil_mask = mask;
+  e->smask_valid = false;          // sum(mask^2) per pose: recomputed on the stream of the next jrr_refine_run
+  return JRR_OK;
+}
+
+// The silhouette term exactly as the fused inner loop evaluates it (k_sil_raster<true>: in-kernel projection from the
+// row-quad vertex buffer, packed fixed-point adjoint, write-back over the vertex pieces), as an operator: SMPL forward of
+// (x6d, betas), then loss and gradient w.r.t. the vertices and the camera.
+extern "C" int jrr_silhouette_loss_grad(jrr_engine_t* e, const float* x6d, const float* betas, const float* cam,
+                                        const float* mask, float* sqsil, float* dverts, float* dcam, void* stream) {
+  if (!e || !x6d || !betas || !cam || !mask) { jrr_set_error("silhouette_loss_grad: null"); return JRR_ERR_ARG; }
+  int rc = sil_check(e);
+  if (rc) return rc;
+  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
+  if (!e->VTb) { jrr_set_error("silhouette_loss_grad needs JRR_FLAG_KEEP_VERTS"); return JRR_ERR_STATE; }
+  hipStream_t s = (hipStream_t)stream;
+  e->fwd_cached = false;
+  smpl_forward(e, x6d, nullptr, betas, true, true, nullptr, s, nullptr, nullptr, 0, true);      // vertices pose-major, as in the loop
+  launch_mask_sq(mask, e->smask, e->B, s, e->sil);
+  e->smask_valid = false;
+  const float silscale = (float)(2.0 * 100.0 / ((double)e->bnorm * (double)e->sil * (double)e->sil));      // optimize.py:252 weight 100
+  { int rcs = launch_sil_raster_adj(e->VTb, e->BP, cam, e->m.faces_int_pk ? e->m.faces_int_pk : e->m.faces_pk, e->m.nfaces, mask, e->smask, e->cover,
+                                    e->ncover, e->sqsil, silscale, e->gcam, 0, e->B, s, e->sil, e->VPM);
+    if (rcs) return rcs; }      // (sizes other than 224 / 256: the stand-alone forward / backward pair only)
+  if (sqsil) JRR_HIP(hipMemcpyAsync(sqsil, e->sqsil, (size_t)e->B * 4, hipMemcpyDeviceToDevice, s));
+  if (dverts) launch_verts_untranspose(e->VTb, dverts, V * 3, V, nullptr, nullptr, e->B, e->BP, s, e->m.p2v);
+  if (dcam) JRR_HIP(hipMemcpyAsync(dcam, e->gcam, (size_t)e->B * 3 * 4, hipMemcpyDeviceToDevice, s));
+  CHECK_LAUNCH();
+  return JRR_OK;
+}

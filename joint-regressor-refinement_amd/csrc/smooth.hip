@@ -23,7 +23,6 @@
 // Status bits (JRR_SMOOTH_STATUS_*): an `order` entry outside [0, n_rows), a listed row whose marker is not 1.0f.  Such a position is
 //   nobody's neighbour and its own outputs are NaN.
 #include "jrr_common.h"
-#include "kernels.h"
 #include "rot6.h"
 #include "../../include/jrr.h"
 
@@ -244,20 +243,6 @@ __global__ __launch_bounds__(SM_THREADS) void k_pose_jitter(const float* __restr
   }
 }
 
-int launch_pose_smooth(const float* table, int64_t n_rows, const int32_t* order, const int32_t* run, int M, const float* weights, int radius,
-                       int begin, int count, float* x6d_out, float* betas_out, float* cam_out, float* delta_deg, int32_t* status, hipStream_t s) {
-  hipLaunchKernelGGL(k_pose_smooth, dim3((unsigned)((count + SM_TILE - 1) / SM_TILE)), dim3(SM_THREADS), 0, s, table, (long long)n_rows, order, run,
-                     M, weights, radius, begin, count, x6d_out, betas_out, cam_out, delta_deg, status);
-  return 0;
-}
-
-int launch_pose_jitter(const float* table, int64_t n_rows, const int32_t* order, const int32_t* run, int M, int begin, int count,
-                       float* jitter_deg, int32_t* status, hipStream_t s) {
-  hipLaunchKernelGGL(k_pose_jitter, dim3((unsigned)((count + SM_TILE - 1) / SM_TILE)), dim3(SM_THREADS), 0, s, table, (long long)n_rows, order, run,
-                     M, begin, count, jitter_deg, status);
-  return 0;
-}
-
 }  // namespace jrr
 
 using namespace jrr;
@@ -291,8 +276,8 @@ extern "C" int jrr_pose_smooth(const float* table, int64_t n_rows, const int32_t
     return JRR_ERR_ARG;
   }
   if (count == 0) return JRR_OK;
-  launch_pose_smooth(table, n_rows, order, run, m, weights, radius, begin, count, x6d_out, betas_out, cam_out, delta_deg, status,
-                     (hipStream_t)stream);
+  hipLaunchKernelGGL(k_pose_smooth, dim3((unsigned)((count + SM_TILE - 1) / SM_TILE)), dim3(SM_THREADS), 0, (hipStream_t)stream, table,
+                     (long long)n_rows, order, run, m, weights, radius, begin, count, x6d_out, betas_out, cam_out, delta_deg, status);
   JRR_HIP(hipGetLastError());
   return JRR_OK;
 }
@@ -307,7 +292,8 @@ extern "C" int jrr_pose_jitter(const float* table, int64_t n_rows, const int32_t
     return JRR_ERR_ARG;
   }
   if (count == 0) return JRR_OK;
-  launch_pose_jitter(table, n_rows, order, run, m, begin, count, jitter_deg, status, (hipStream_t)stream);
+  hipLaunchKernelGGL(k_pose_jitter, dim3((unsigned)((count + SM_TILE - 1) / SM_TILE)), dim3(SM_THREADS), 0, (hipStream_t)stream, table,
+                     (long long)n_rows, order, run, m, begin, count, jitter_deg, status);
   JRR_HIP(hipGetLastError());
   return JRR_OK;
 }

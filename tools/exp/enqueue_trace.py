@@ -3,7 +3,10 @@ ahead of the library) that runs nothing and logs every enqueue -- kernel name, g
 sizes (done on host memory); event records / waits; stream creation.  The driver below walks every shape of the fused inner loop: the
 support-vertex iteration composed and as side-stream halves (the regressor's support lists are written into the workspace as the device
 would have left them), its split launches, the tile-listed / all-tiles LBS chain, forward reuse after a J step, folded, silhouette, the
-in-call J steps, loss history, profiling.  Two libraries that print the same trace enqueue the same work in the same order (the kernels'
+in-call J steps, loss history, profiling.  The "operators" section then calls every entry point that lives beside its kernels (image,
+report, shade, export, eval, evalrep, regrep, smooth; the discriminator and silhouette operators on the engines built before) once at
+the smallest sizes it accepts and once with an argument it refuses; the status and jrr_last_error() of the refusal are part of the
+trace.  Two libraries that print the same trace enqueue the same work in the same order (the kernels'
 ARGUMENTS are not compared: that is what the bit-for-bit comparison of results on a GPU is for).
 
     python tools/exp/enqueue_trace.py <libA.so> <libB.so> [outdir]     compares the two under the default environment and each loop knob
@@ -109,6 +112,39 @@ class Run:
     def reproj(self): ck(lib.jrr_engine_set_reprojection(self.e, self.p(self.j2d), self.p(self.cam), self.p(self.cm), self.p(self.cv)), 'set_reprojection')
     def close(self): lib.jrr_engine_destroy(self.e); note('engine_destroy')
 
+def op(name, *args, tag=''):
+    return ck(getattr(lib, name)(*args), name + tag)
+_bufs = {}
+def buf(nbytes, shift=0):      # zero-filled, 256-byte aligned (+ shift); one buffer per size, shared by the calls: nothing runs
+    if nbytes not in _bufs: _bufs[nbytes] = aligned(nbytes + 64)
+    return _bufs[nbytes][1] + shift
+def disc_ops(r, refuse):
+    """the discriminator operators on engine r; refuse: the engine has neither discriminator"""
+    B, t = r.B, ' refused' if refuse else ''
+    x, o, g, dP, sq = buf(B * 144 * 4), buf(B * 25 * 4), buf(B * 25 * 4), buf(1840153 * 4), buf(B * 4)
+    op('jrr_pose_disc_forward', r.e, x, o, None, tag=t)
+    op('jrr_pose_disc_backward_input', r.e, x, 1.0, 1.0, x, None, tag=t)
+    op('jrr_pose_disc_vjp_input', r.e, x, g, x, None, tag=t)
+    op('jrr_pose_disc_backward_params', r.e, x, 1.0, dP, sq, None, tag=t)
+    op('jrr_pose_disc_vjp_params', r.e, x, g, dP, None, tag=t)
+    b = buf(B * 10 * 4)
+    op('jrr_shape_disc_forward', r.e, b, sq, None, tag=t)
+    op('jrr_shape_disc_vjp_input', r.e, b, sq, b, None, tag=t)
+    op('jrr_shape_disc_backward_params', r.e, b, 1.0, dP, sq, None, tag=t)
+    op('jrr_shape_disc_vjp_params', r.e, b, sq, dP, None, tag=t)
+    op('jrr_refine_aux_losses', r.e, sq, buf(B * 4 + 4), None, tag=t)
+    if refuse:
+        op('jrr_engine_set_pose_disc', r.e, dP, None, tag=t); op('jrr_engine_set_shape_disc', r.e, dP, None, tag=t)
+        op('jrr_pose_disc_forward', r.e, None, o, None, tag=' null')
+def sil_ops(r, img, refuse):
+    """the silhouette operators on engine r (img: a (B,224,224) float32 buffer); refuse: an engine without JRR_FLAG_SILHOUETTE"""
+    B, t = r.B, ' refused' if refuse else ''
+    v, cam = buf(B * 6890 * 3 * 4), buf(B * 3 * 4)
+    op('jrr_silhouette_forward', r.e, v, cam, img, None, tag=t)
+    op('jrr_silhouette_backward', r.e, img, v, cam, None, tag=t)
+    op('jrr_silhouette_pix_to_face', r.e, img, None, tag=t)
+    op('jrr_silhouette_loss_grad', r.e, r.p(r.x), r.p(r.b), cam, img, buf(B * 4), v, buf(B * 3 * 4 + 4), None, tag=t)
+    op('jrr_engine_set_silhouette', r.e, img, None, None, None, tag=' refused')
 mh, mplain = model(True), model(False)
 for B in (64, 256, 1024, 4096):
     note('== support engine B=%d' % B)
@@ -123,15 +159,68 @@ for B in (64, 1024):
     r.run(2); r.hist_on(); r.run_j(5, 2); r.run_j(4, 2, 2); r.run_j(3, 3, 1); r.reproj(); r.run(2)
     g = np.zeros((17, 6890), np.float32)
     ck(lib.jrr_j_regressor_grad(r.e, r.p(r.x), r.p(r.b), r.p(r.gt), g.ctypes.data, None, None, None), 'j_regressor_grad'); r.run_after(2)
-    ck(lib.jrr_engine_set_profiling(r.e, 1), 'profiling'); r.run(2); r.close()
+    ck(lib.jrr_engine_set_profiling(r.e, 1), 'profiling'); r.run(2)
+    note('== operators: discriminators B=%d' % B); disc_ops(r, False); r.close()
     note('== chain engine with known support B=%d' % B)
     r = Run(mplain, B, POSE | KEEP, forge=True); r.run(2); r.run_j(5, 2); r.close()
     note('== plain engine B=%d' % B)
-    r = Run(mplain, B, 0); r.run(2); r.close()
+    r = Run(mplain, B, 0); r.run(2)
+    note('== operators: refused on a plain engine B=%d' % B); disc_ops(r, True); sil_ops(r, buf(16), True); r.close()
     note('== folded engine B=%d' % B)
     r = Run(mplain, B, POSE | SHAPE | KEEP | FOLDED); ck(lib.jrr_engine_set_folded(r.e, 1, None), 'set_folded'); r.hist_on(); r.run(2); r.run_j(4, 2); r.reproj(); r.run(1); r.close()
     note('== silhouette engine B=%d' % B)
     r = Run(mplain, B, POSE | KEEP | SIL)
     mask = np.zeros((B, 224, 224), np.float32)
-    ck(lib.jrr_engine_set_silhouette(r.e, mask.ctypes.data, r.p(r.cam), r.p(r.cm), r.p(r.cv)), 'set_silhouette'); r.hist_on(); r.run(3); r.reproj(); r.run_j(4, 2); r.close()
+    ck(lib.jrr_engine_set_silhouette(r.e, mask.ctypes.data, r.p(r.cam), r.p(r.cm), r.p(r.cv)), 'set_silhouette'); r.hist_on(); r.run(3); r.reproj(); r.run_j(4, 2)
+    note('== operators: silhouette B=%d' % B); sil_ops(r, mask.ctypes.data, False); r.close()
+note('== operators without an engine')
+B, S = 2, 8
+c3 = (ctypes.c_float * 3)(0.5, 0.5, 0.5)
+img, out, st = buf(B * 3 * S * S * 4), buf(B * 3 * S * S * 4 + 64), buf(64)
+op('jrr_image_crop', buf(1024), 1024, buf(B * 64), buf(B * 16), B, None, None, S, out, 4, img, st, None)
+op('jrr_image_crop', buf(1024), 1024, buf(B * 64), buf(B * 16), B, None, None, 6, out, 0, None, st, None, tag=' refused')
+op('jrr_mask_prepare', buf(1024), B, S, S, out, st, None)
+op('jrr_mask_prepare', buf(1024), B, 0, S, out, st, None, tag=' refused')
+op('jrr_silhouette_compare', img, out, B, S, S, 0.5, 0.8, st, None)
+op('jrr_silhouette_compare', img, out, B, 3, 3, 0.5, 0.8, st, None, tag=' refused')
+op('jrr_fit_overlay', img, out, None, None, None, None, 0, B, S, 0.5, 0.8, 2.0, buf(B * S * S * 3), None)
+op('jrr_fit_overlay', img, out, None, None, None, None, 0, B, 6, 0.5, 0.8, 2.0, buf(B * S * S * 3), None, tag=' refused')
+NF = int(np.asarray(m['faces']).shape[0])
+verts, nrm, faces, adj = buf(B * 6890 * 3 * 4), buf(B * 6890 * 3 * 4 + 64), buf(NF * 3 * 4), buf(NF * 3 * 4 + 64)
+op('jrr_vertex_normals', verts, faces, buf(6891 * 4), adj, B, 6890, NF, nrm, None)
+op('jrr_vertex_normals', verts, faces, buf(6891 * 4), adj, B, 0, NF, nrm, None, tag=' refused')
+op('jrr_mesh_shade', verts, nrm, faces, buf(B * 3 * 4), buf(B * S * S * 4), None, None, None, B, 6890, NF, S, c3, 1.0, 0.3, c3, 1.0, buf(B * S * S * 3), None, None, st, None)
+op('jrr_mesh_shade', verts, nrm, faces, buf(B * 3 * 4), buf(B * S * S * 4), None, None, None, B, 6890, NF, 260, c3, 1.0, 0.3, c3, 1.0, buf(B * S * S * 3), None, None, st, None, tag=' refused')
+op('jrr_rotmat_to_axis_angle', buf(B * 9 * 4), buf(B * 3 * 4), B, None)
+op('jrr_rotmat_to_axis_angle', buf(B * 9 * 4), buf(B * 3 * 4), -1, None, tag=' refused')
+table = buf(4 * 1024)
+op('jrr_pose_export', buf(B * 144 * 4), buf(B * 10 * 4), buf(B * 3 * 4), None, 0, buf(B * 8), table, 4, st, B, None)
+op('jrr_pose_export', buf(B * 144 * 4), buf(B * 10 * 4), buf(B * 3 * 4), None, 11, buf(B * 8), table, 4, st, B, None, tag=' refused')
+order, run_ = buf(B * 4), buf(B * 4 + 64)
+op('jrr_pose_smooth', table, 4, order, run_, B, buf(17 * 4), 1, 0, B, buf(B * 144 * 4), buf(B * 10 * 4), buf(B * 3 * 4), buf(B * 4 + 128), st, None)
+op('jrr_pose_smooth', table, 4, order, run_, B, buf(17 * 4), 17, 0, B, buf(B * 144 * 4), buf(B * 10 * 4), buf(B * 3 * 4), buf(B * 4 + 128), st, None, tag=' refused')
+op('jrr_pose_jitter', table, 4, order, run_, B, 0, B, buf(B * 4 + 128), st, None)
+op('jrr_pose_jitter', table, 4, order, run_, B, 1, B, buf(B * 4 + 128), st, None, tag=' refused')
+pred, tgt, ej, epa = buf(B * 51 * 4), buf(B * 51 * 4 + 64), buf(B * 17 * 4), buf(B * 17 * 4 + 64)
+op('jrr_evaluate', pred, tgt, buf(B * 4), buf(B * 4 + 64), B, None)
+op('jrr_evaluate', pred, tgt, buf(B * 4), buf(B * 4 + 64), 0, None, tag=' refused')
+op('jrr_evaluate_joints', pred, tgt, ej, epa, B, None)
+op('jrr_evaluate_joints', pred, tgt, buf(B * 17 * 4, 4), epa, B, None, tag=' refused')
+for n_reg in (1, 2):
+    need = lib.jrr_regress_joints_workspace_bytes(n_reg)
+    note('regress_joints_workspace_bytes %d -> %d' % (n_reg, need))
+    ws, Jr = buf(need), buf(n_reg * 17 * 6890 * 4 + 64)
+    op('jrr_regress_joints_prepare', Jr, n_reg, None, ws, need, None, tag=' n_reg=%d' % n_reg)
+    op('jrr_regress_joints', verts, B, ws, n_reg, buf(n_reg * B * 51 * 4 + 128), None, tag=' n_reg=%d' % n_reg)
+    op('jrr_regress_joints_prepare', Jr, n_reg, None, ws, need - 1, None, tag=' n_reg=%d refused' % n_reg)
+note('regress_joints_workspace_bytes 0 -> %d, 5 -> %d' % (lib.jrr_regress_joints_workspace_bytes(0), lib.jrr_regress_joints_workspace_bytes(5)))
+op('jrr_regress_joints', verts, B, buf(1024), 0, buf(B * 51 * 4 + 128), None, tag=' refused')
+acc = buf(1 << 16)
+op('jrr_eval_accumulate', ej, epa, buf(B * 4), B, 1, acc, None)
+op('jrr_eval_accumulate', ej, epa, buf(B * 4), B, 0, acc, None, tag=' refused')
+op('jrr_regressor_shift_accumulate', pred, tgt, None, B, 1, acc, None)
+op('jrr_regressor_shift_accumulate', pred, tgt, None, B, 0, acc, None, tag=' refused')
+col = (ctypes.c_uint8 * 3)(255, 0, 0)
+op('jrr_draw_discs', buf(B * S * S * 3), B, S, S, buf(B * 2 * 4), None, 2.0, col, 1, 1, None)
+op('jrr_draw_discs', buf(B * S * S * 3), B, S, S, buf(B * 2 * 4), None, 2.0, col, 0, 1, None, tag=' refused')
 note('done')
