@@ -483,7 +483,14 @@ int jrr_adam_step(float* p_dev, const float* g_dev, float* m_dev, float* v_dev, 
 
 /* evaluate, scripts/utils.py:117-145 + scripts/eval_utils.py:7-58 (row f3): per-pose mean joint error and
  * Procrustes-aligned mean joint error in METRES (pred in m, target in mm, both pelvis-centred inside);
- * MPJPE / PA-MPJPE in mm = 1000 * mean over poses.                                                    */
+ * MPJPE / PA-MPJPE in mm = 1000 * mean over poses.
+ * The alignment is the reference's torch.svd + det-sign fix, degenerate shapes included.  The 3x3 SVD of K = X1 X2^T is a
+ * one-sided (Hestenes) Jacobi iteration on K itself (K^T K is never formed), the rotation v1 u1^T + v2 u2^T + (v1 x v2)(u1 x u2)^T:
+ *   rank 3 and rank 2 (a flat pred and/or target, mirrored or not): the unique proper rotation of the reference;
+ *   rank 1 (a pred or a target on a line, sigma_2 <= 1e-6 sigma_1): the rotation about the line is free, the aligned distances are not;
+ *   rank 0: a constant target gives aligned distances of exactly 0, a constant pred NaN (the reference's 0/0) in its own aligned
+ *           values only, its plain distances stay finite.
+ * One pose per thread, no cross-lane arithmetic: a pose's result does not depend on the other poses of the batch.        */
 int jrr_evaluate(const float* pred_j3d_dev, const float* target_j3d_mm_dev, float* err_dev, float* err_pa_dev,
                  int batch, void* stream);
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/g10_eval_joints.npz by IMPORTING the reference's own modules (as tests/golden/make_golden.py does).
+"""Generate tests/golden/g10_eval_joints.npz and tests/golden/g11_eval_degenerate.npz by IMPORTING the reference's own modules (as tests/golden/make_golden.py does).
 
 Run only in the build container (needs /root/reference):  python tests/golden/make_golden_eval.py
 The reference's Python never travels; only the small .npz written here is committed.  The inputs are regenerated from the seeds of
@@ -9,6 +9,9 @@ tests/eval_report_cases.py; the pose inputs are stored as well (15 KB), the mesh
        and the two (65,17) per-joint error arrays formed from it
   (ii) the reference's find_joints with a stub smpl on 3 seeded meshes: the 62-positive H36M regressor with its mask, a dense seeded
        regressor without mask, and the dense one with one row zeroed (that row's joints are NaN)
+  (iii) g11: the reference's batch_compute_similarity_transform_torch on 8 poses each of the body, thin (0.002), target-flat,
+       both-flat-mirrored, pred-collinear and constant-target families of tests/eval_report_cases.py (48 poses): pred, target_mm and
+       the two (48,17) per-joint error arrays
 """
 import importlib
 import os
@@ -92,3 +95,33 @@ path = os.path.join(HERE, 'g10_eval_joints.npz')
 np.savez_compressed(path, **arrs)
 print('g10_eval_joints.npz', {k: v.shape for k, v in arrs.items()}, os.path.getsize(path), 'bytes')
 assert os.path.getsize(path) <= 512 * 1024
+
+
+# ---- (iii) ----
+preds, tgts = zip(*[ec.family_cases(name, ec.G11_POSES) for name in ec.G11_FAMILIES])
+pred11, tgt11 = np.concatenate(preds), np.concatenate(tgts)
+p = T(pred11).clone()
+t = T(tgt11).clone() / 1000
+p -= p[:, [0], :].clone()
+t -= t[:, [0], :].clone()
+s1hat11 = ref_eval.batch_compute_similarity_transform_torch(p, t)
+err_j11 = torch.sqrt(((p - t) ** 2).sum(dim=-1))
+err_pa_j11 = torch.sqrt(((s1hat11 - t) ** 2).sum(dim=-1))
+assert torch.isfinite(err_pa_j11).all() and torch.isfinite(err_j11).all()
+mpjpe11, pampjpe11 = ref_utils.evaluate(T(pred11), T(tgt11))
+np.testing.assert_allclose(err_pa_j11.mean(1).mean().item() * 1000, pampjpe11, rtol=1e-6)
+# the oracle port equals the reference bit for bit on them, and so do the restatement's inputs and values
+assert torch.equal(oracle.batch_compute_similarity_transform_torch(p, t), s1hat11)
+_, e32, pa32 = ec.evaluate_joints(pred11, tgt11, torch.float32)
+assert np.array_equal(e32, err_j11.numpy()) and np.array_equal(pa32, err_pa_j11.numpy())
+_, e64, pa64 = ec.evaluate_joints(pred11, tgt11, torch.float64)
+for k, name in enumerate(ec.G11_FAMILIES):
+    sl = slice(k * ec.G11_POSES, (k + 1) * ec.G11_POSES)
+    d = np.abs(err_pa_j11.numpy()[sl] - pa64[sl]).max()
+    print(f'g11 {name}: reference fp32 against float64 {d:.3e} m')
+    assert d <= ec.FAMILIES[name][1], f'{name}: pick another seed'
+arrs = dict(pred=pred11, target_mm=tgt11, err_j=err_j11.numpy(), err_pa_j=err_pa_j11.numpy())
+path = os.path.join(HERE, 'g11_eval_degenerate.npz')
+np.savez_compressed(path, **arrs)
+print('g11_eval_degenerate.npz', {k: v.shape for k, v in arrs.items()}, os.path.getsize(path), 'bytes')
+assert os.path.getsize(path) <= 64 * 1024

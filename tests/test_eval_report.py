@@ -75,6 +75,88 @@ def test_regress_restatement_on_g10():
         assert np.abs(j32 - j64)[~nan].max() <= ec.bound(d) and np.abs(j32 - g[key])[~nan].max() <= ec.bound(d)
 
 
+# ---- 1b. the kernel's statements, restated in float32, on body-shaped, flat, collinear and constant poses ----
+@pytest.fixture(scope='module')
+def family_references():
+    """per family: inputs (B = 65), the reference in float64 and float32 -- computed once"""
+    out = {}
+    for name in ec.FAMILIES:
+        pred, tgt = ec.family_cases(name, 65)
+        out[name] = (pred, tgt) + ec.evaluate_joints(pred, tgt, torch.float64)[1:] + ec.evaluate_joints(pred, tgt, torch.float32)[1:]
+    return out
+
+
+@pytest.mark.parametrize('name', list(ec.FAMILIES))
+def test_kernel_restatement_on_every_family(family_references, name):
+    """ec.kernel_evaluate_joints (csrc/evalk.h operation by operation in float32) against the float64 reference, all 17 values of all
+    65 poses, nothing masked; the condition on the inputs first: the reference's own float32 is a yardstick on them"""
+    pred, tgt, e64, pa64, e32, pa32 = family_references[name]
+    assert pred.dtype == F and tgt.dtype == F and pred.shape == (65, 17, 3) and tgt.shape == (65, 17, 3)
+    r_e, r_pa = ec.kernel_evaluate_joints(pred, tgt)
+    assert np.isfinite(e64).all() and np.isfinite(e32).all() and np.isfinite(r_e).all()
+    d_plain = np.abs(e32 - e64).max()
+    if name in ec.ALL_NAN_PA:                           # the reference's 0/0: compared by the pattern
+        assert np.isnan(pa64).all() and np.isnan(pa32).all() and np.isnan(r_pa).all()
+        print(f'{name}: all {r_pa.size} PA values NaN in float64, float32 and the restatement; plain {np.abs(r_e - e64).max():.3e} '
+              f'(reference {d_plain:.3e})')
+    else:
+        assert np.isfinite(pa64).all() and np.isfinite(pa32).all()
+        d_pa = np.abs(pa32 - pa64).max()
+        g_pa = np.abs(r_pa.astype(np.float64) - pa64).max()
+        print(f'{name}: reference fp32 against float64 {d_pa:.3e} m (cap {ec.FAMILIES[name][1]:.0e}), restatement {g_pa:.3e} '
+              f'(bound {ec.bound(d_pa):.3e}); plain {np.abs(r_e - e64).max():.3e} (reference {d_plain:.3e}); largest PA error {pa64.max():.4f} m')
+        assert d_pa <= ec.FAMILIES[name][1], 'pick another seed: the reference itself is too far from float64 on these poses'
+        assert np.isfinite(r_pa).all() and g_pa <= ec.bound(d_pa)
+    assert np.abs(r_e.astype(np.float64) - e64).max() <= ec.bound(d_plain)
+    if name == 'constant_target':
+        assert np.array_equal(r_pa, np.zeros((65, 17), dtype=F)) and not pa32.any() and not pa64.any()
+    if name == 'identical':
+        assert pa64.max() < 1e-6 and e64.max() < 1e-6                                       # pred * 1000 / 1000 rounds twice
+
+
+def test_families_are_what_they_say():
+    """singular values of K in float64: the flat families have rank 2, the collinear ones rank 1, the constant ones rank 0 -- to the
+    rounding of the float32 inputs -- and no family is axis-aligned"""
+    def sv(name):
+        pred, tgt = ec.family_cases(name, 65)
+        p, t = pred.astype(np.float64), tgt.astype(np.float64) / 1000
+        x1, x2 = p - p.mean(1, keepdims=True), t - t.mean(1, keepdims=True)
+        return np.linalg.svd(np.einsum('bir,bic->brc', x1, x2), compute_uv=False), x1
+    for name in ('flat_target', 'flat_pred', 'flat_both_mirrored'):
+        s, _ = sv(name)
+        assert (s[:, 2] < 1e-6 * s[:, 0]).all() and (s[:, 1] > 1e-3 * s[:, 0]).all(), name
+    for name in ('collinear_pred', 'collinear_target'):
+        s, _ = sv(name)
+        assert (s[:, 1] < 3e-7 * s[:, 0]).all() and (s[:, 0] > 0).all(), name
+    for name in ('constant_target', 'constant_pred'):
+        assert sv(name)[0].max() < 1e-12, name                                               # the float64 mean of 17 equal numbers rounds
+    s, x1 = sv('body')
+    assert (s[:, 2] > 1e-4 * s[:, 0]).all()
+    assert (np.abs(x1).max(1).min(1) > 0.02).all()                                         # rotated: every axis carries the body
+    for name in ec.G11_FAMILIES:
+        assert name in ec.FAMILIES
+    pred, tgt, fam, row = ec.mixed_cases(130)
+    assert pred.shape == (130, 17, 3) and fam[:15].tolist() == list(range(14)) + [0] and row[14] == 1
+    assert np.array_equal(pred[15], ec.family_cases(list(ec.FAMILIES)[1], 10)[0][1])
+
+
+def test_rank_fallbacks_do_not_depend_on_the_free_choice():
+    """rank 1: the rotation about the line is free; the restatement's 17 distances equal the float64 reference's whichever
+    orthogonal completion torch.svd happened to take (both collinear families, and a K of exactly rank 1 built by hand)"""
+    a = np.array([[0.3, -0.5, 0.8]], dtype=F)
+    b = np.array([[-0.2, 0.9, 0.4]], dtype=F)
+    K = (a[:, :, None] * b[:, None, :]).astype(F)                                           # u1 = a / |a|, v1 = b / |b|
+    R = ec.kernel_rotation(K).astype(np.float64)[0]
+    assert np.abs(R @ R.T - np.eye(3)).max() < 1e-6 and abs(np.linalg.det(R) - 1) < 1e-6
+    np.testing.assert_allclose(R @ (a[0] / np.linalg.norm(a[0])), b[0] / np.linalg.norm(b[0]), atol=1e-6)
+    R0 = ec.kernel_rotation(np.zeros((2, 3, 3), dtype=F))
+    assert np.array_equal(R0, np.broadcast_to(np.eye(3, dtype=F), (2, 3, 3)))
+    # a mirrored flat K: the proper rotation, det +1
+    K2 = np.diag([2.0, -1.0, 0.0]).astype(F)[None]
+    R2 = ec.kernel_rotation(K2).astype(np.float64)[0]
+    assert abs(np.linalg.det(R2) - 1) < 1e-6 and np.abs(np.abs(np.diag(R2)) - 1).max() < 1e-6 and R2[0, 0] > 0 and R2[1, 1] < 0
+
+
 # ---- 2. the accumulator's integers ----
 def test_accumulator_integers_by_hand():
     e0 = np.full((4, 17), 0.01, dtype=F)

@@ -6,6 +6,10 @@ Bounds: every comparison with float64 is held to `3 x (the reference's float32 d
 (eval_report_cases.bound); on float32 inputs oracle.reference_port equals the reference bit for bit (asserted by
 tests/golden/make_golden_eval.py), so it stands for the reference where no value is stored.
 
+Inputs: isotropic clouds (ec.pose_cases) and, since no skeleton looks like one, the families of ec.FAMILIES: body-shaped, thin, exactly
+flat, nearly and exactly collinear, scaled, identical and constant poses, alone (B = 65), mixed in one wave (B = 130) and as stored
+by the reference (tests/golden/g11_eval_degenerate.npz).
+
 Shapes: B = 1, 63, 65, 130 around the 64-pose workgroup of k_evaluate_joints and its ragged last piece (63 * 17 and 65 * 17 floats
 are no multiple of the 16-byte store); B = 3 and 70 meshes; the accumulator at B = 65 in one call and as 40 + 25.
 """
@@ -85,6 +89,163 @@ def test_evaluate_keeps_its_golden_values():
     print('jrr_evaluate on g6:', [v.hex() for v in err.cpu().numpy().astype(np.float64)], [v.hex() for v in err_pa.cpu().numpy().astype(np.float64)])
     np.testing.assert_allclose(float(err.mean()) * 1000, float(g['mpjpe']), rtol=1e-5)
     np.testing.assert_allclose(float(err_pa.mean()) * 1000, float(g['pampjpe']), rtol=1e-4)
+
+
+# ---- 1b. body-shaped, thin, flat, collinear, scaled, identical and constant poses (ec.FAMILIES) ----
+def _distance(a, ref):
+    """max |a - ref| over every value, float64; the NaN patterns must be equal, and an all-NaN pair is at distance 0"""
+    a, ref = np.asarray(a, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    nan = np.isnan(ref)
+    np.testing.assert_array_equal(np.isnan(a), nan)
+    return float(np.abs(a - ref)[~nan].max()) if not nan.all() else 0.0
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _device_errors(eng, pred, tgt):
+    """(err_j, err_pa_j, mean, mean_pa) of jrr_evaluate_joints and jrr_evaluate as numpy arrays"""
+    dp, dt = T(np.ascontiguousarray(pred)).to(DEV), T(np.ascontiguousarray(tgt)).to(DEV)
+    return tuple(x.cpu().numpy() for x in eng.evaluate_joints(dp, dt) + eng.evaluate(dp, dt))
+
+
+@pytest.fixture(scope='module')
+def family_inputs():
+    """per family its 65 poses (one full 64-pose workgroup and a ragged one), the reference in float64 and in float32 -- once"""
+    out = {}
+    for name in ec.FAMILIES:
+        pred, tgt = ec.family_cases(name, 65)
+        out[name] = (pred, tgt, _reference_errors(pred, tgt, torch.float64), _reference_errors(pred, tgt, torch.float32))
+    return out
+
+
+@pytest.mark.parametrize('name', list(ec.FAMILIES))
+def test_evaluate_joints_on_every_family(family_inputs, name):
+    """jrr_evaluate_joints and jrr_evaluate against float64 and against the float32 reference, every value of every pose, held to
+    3 x (the reference's float32 distance from float64 on this family's inputs) + 1e-7.  What the K^T K eigen-decomposition this kernel had before gave on these inputs is in DESIGN.md section 3d."""
+    eng = _mod('engine')
+    pred, tgt, (e64, pa64), (e32, pa32) = family_inputs[name]
+    assert np.isnan(pa64).all() == (name in ec.ALL_NAN_PA) and np.isnan(pa64).any() == (name in ec.ALL_NAN_PA)
+    d_plain, d_pa = _distance(e32, e64), _distance(pa32, pa64)
+    err_j, err_pa_j, m, m_pa = _device_errors(eng, pred, tgt)
+    assert err_j.shape == (65, 17) and err_pa_j.shape == (65, 17) and m.shape == (65,) and m_pa.shape == (65,)
+    with np.errstate(invalid='ignore'):
+        finite = int(np.isfinite(err_pa_j).sum())
+        worst = np.nanmax(np.where(np.isnan(pa64), 0, np.abs(err_pa_j.astype(np.float64) - pa64)))
+    r_e, r_pa = ec.kernel_evaluate_joints(pred, tgt)
+    print(f'{name}: PA worst {worst:.3e} (reference {d_pa:.3e}, bound {ec.bound(d_pa):.3e}), {finite} of {err_pa_j.size} finite; from the restatement: '
+          f'plain {np.nanmax(np.abs(err_j - r_e)):.3e}, PA {np.nanmax(np.abs(err_pa_j - r_pa)) if name not in ec.ALL_NAN_PA else 0.0:.3e}')
+    g_plain, g_pa = _distance(err_j, e64), _distance(err_pa_j, pa64)
+    print(f'{name}: plain {g_plain:.3e} (reference {d_plain:.3e}, bound {ec.bound(d_plain):.3e})  PA {g_pa:.3e}  '
+          f'from the float32 reference: plain {_distance(err_j, e32):.3e}, PA {_distance(err_pa_j, pa32):.3e}')
+    assert g_plain <= ec.bound(d_plain) and g_pa <= ec.bound(d_pa)
+    assert _distance(err_j, e32) <= ec.bound(d_plain) and _distance(err_pa_j, pa32) <= ec.bound(d_pa)
+    if name == 'constant_target':
+        assert not err_pa_j.any() and not m_pa.any()                                       # exactly 0, as the reference
+    # jrr_evaluate: its per-pose means re-formed on the host from the per-joint values, in k_evaluate's own order
+    h, h_pa = ec.pose_means(err_j, err_pa_j)
+    np.testing.assert_allclose(h, m, rtol=1e-6, atol=0)
+    g_mean = _distance(m_pa, h_pa)
+    print(f'{name}: jrr_evaluate PA means from the re-formed ones {g_mean:.3e}, bit-identical {np.array_equal(h_pa, m_pa, equal_nan=True)}')
+    assert g_mean <= ec.bound(d_pa)
+
+
+def test_evaluate_joints_on_the_references_stored_degenerate_poses():
+    """tests/golden/g11_eval_degenerate.npz: 8 poses each of six families with the reference's OWN float32 values; one launch of 48"""
+    eng = _mod('engine')
+    g = load_golden('g11_eval_degenerate.npz')
+    e64, pa64 = _reference_errors(g['pred'], g['target_mm'], torch.float64)
+    err_j, err_pa_j, m, m_pa = _device_errors(eng, g['pred'], g['target_mm'])
+    h, h_pa = ec.pose_means(err_j, err_pa_j)
+    n = ec.G11_POSES
+    for k, name in enumerate(ec.G11_FAMILIES):
+        sl = slice(k * n, (k + 1) * n)
+        d_plain, d_pa = _distance(g['err_j'][sl], e64[sl]), _distance(g['err_pa_j'][sl], pa64[sl])
+        got = _distance(err_j[sl], e64[sl]), _distance(err_pa_j[sl], pa64[sl]), _distance(err_j[sl], g['err_j'][sl]), _distance(err_pa_j[sl], g['err_pa_j'][sl])
+        print(f'g11 {name}: from float64 plain {got[0]:.3e} PA {got[1]:.3e}; from the stored values plain {got[2]:.3e} PA {got[3]:.3e} '
+              f'(reference {d_plain:.3e} / {d_pa:.3e}, bounds {ec.bound(d_plain):.3e} / {ec.bound(d_pa):.3e})')
+        assert got[0] <= ec.bound(d_plain) and got[2] <= ec.bound(d_plain) and got[1] <= ec.bound(d_pa) and got[3] <= ec.bound(d_pa)
+        assert _distance(m_pa[sl], h_pa[sl]) <= ec.bound(d_pa)
+    np.testing.assert_allclose(h, m, rtol=1e-6, atol=0)
+
+
+@pytest.fixture(scope='module')
+def mixed_batch():
+    """130 poses, pose b of family b mod 14: every wave holds every rank.  Each family's own batch of 10 and its references."""
+    names = list(ec.FAMILIES)
+    pred, tgt, fam, row = ec.mixed_cases(130)
+    own = {k: ec.family_cases(k, 10) for k in names}
+    return names, pred, tgt, fam, row, own
+
+
+def test_mixed_ranks_in_one_wave_equal_each_family_alone(mixed_batch):
+    """neither kernel has cross-lane arithmetic: a pose's values in the mixed batch have the BITS they have in a batch of their own
+    family; and every value lies within its family's bound of float64"""
+    eng = _mod('engine')
+    names, pred, tgt, fam, row, own = mixed_batch
+    mixed = _device_errors(eng, pred, tgt)
+    e64, pa64 = _reference_errors(pred, tgt, torch.float64)
+    e32, pa32 = _reference_errors(pred, tgt, torch.float32)
+    for k, name in enumerate(names):
+        alone = _device_errors(eng, *own[name])
+        rows = np.flatnonzero(fam == k)
+        assert np.array_equal(pred[rows], own[name][0][row[rows]])
+        for a, b, what in zip(mixed, alone, ('err_j', 'err_pa_j', 'mean', 'mean_pa')):
+            assert np.array_equal(_bits(a[rows]), _bits(b[row[rows]])), (name, what)
+        d_plain, d_pa = _distance(e32[rows], e64[rows]), _distance(pa32[rows], pa64[rows])
+        g_plain, g_pa = _distance(mixed[0][rows], e64[rows]), _distance(mixed[1][rows], pa64[rows])
+        print(f'mixed {name}: plain {g_plain:.3e} ({ec.bound(d_plain):.3e})  PA {g_pa:.3e} ({ec.bound(d_pa):.3e})')
+        assert g_plain <= ec.bound(d_plain) and g_pa <= ec.bound(d_pa), name
+    nan_rows = np.flatnonzero(np.isnan(mixed[1]).any(1))
+    assert nan_rows.tolist() == np.flatnonzero(fam == names.index('constant_pred')).tolist() and np.isfinite(mixed[0]).all()
+
+
+def test_a_defective_pose_leaves_its_neighbours_bits_alone():
+    """a constant pred gives NaN in its own 17 PA values and nowhere else; a pose with one NaN coordinate gives NaN in its own rows
+    only; every other pose has the bits of the run without the defect"""
+    eng = _mod('engine')
+    pred, tgt = ec.family_cases('body', 130)
+    clean = _device_errors(eng, pred, tgt)
+    assert all(np.isfinite(x).all() for x in clean)
+    constant = pred.copy()
+    for b in (0, 5, 63, 64, 129):
+        constant[b] = constant[b, 3]
+    poisoned_pred, poisoned_tgt = pred.copy(), tgt.copy()
+    poisoned_pred[7, 4, 1] = np.nan                     # one joint of a pred
+    poisoned_tgt[70, 0, 2] = np.nan                     # the pelvis of a target: every distance of that pose
+    for (p, t), bad in (((constant, tgt), [0, 5, 63, 64, 129]), ((poisoned_pred, poisoned_tgt), [7, 70])):
+        got = _device_errors(eng, p, t)
+        good = np.setdiff1d(np.arange(130), bad)
+        for a, b, what in zip(got, clean, ('err_j', 'err_pa_j', 'mean', 'mean_pa')):
+            assert np.array_equal(_bits(a[good]), _bits(b[good])), what
+        assert np.isnan(got[1][bad]).all() and np.isnan(got[3][bad]).all()
+    got = _device_errors(eng, constant, tgt)
+    assert np.isfinite(got[0]).all() and np.isfinite(got[2]).all()                          # a constant pred: the plain errors are finite
+    got = _device_errors(eng, poisoned_pred, poisoned_tgt)
+    assert np.isnan(got[0][7]).tolist() == [i == 4 for i in range(17)] and np.isnan(got[0][70]).all() and np.isnan(got[2][[7, 70]]).all()
+
+
+def test_accumulate_on_the_mixed_batch(mixed_batch):
+    """one jrr_eval_accumulate call over the mixed batch: the restatement word for word, the constant-pred poses in BAD only"""
+    eng = _mod('engine')
+    names, pred, tgt, fam, row, own = mixed_batch
+    err_j, err_pa_j = eng.evaluate_joints(T(pred).to(DEV), T(tgt).to(DEV))
+    group = (np.arange(130) % 3).astype(np.int32)
+    acc = _acc(3)
+    eng.eval_accumulate(err_j, err_pa_j, T(group).to(DEV), 3, acc)
+    want = ec.accumulate(err_j.cpu().numpy(), err_pa_j.cpu().numpy(), group, 3)
+    np.testing.assert_array_equal(acc.cpu().numpy(), want)
+    rows = want[:3 * ec.ROW].reshape(3, ec.ROW)
+    bad = fam == names.index('constant_pred')
+    assert bad.sum() == 9 and rows[:, ec.BAD].tolist() == [int((bad & (group == g)).sum()) for g in range(3)]
+    assert rows[:, ec.COUNT].tolist() == [int((~bad & (group == g)).sum()) for g in range(3)] and want[-2] == 0 and want[-1] == 0
+    assert rows[:, ec.HIST:ec.HIST + ec.BINS].sum() == 17 * 121 and rows[:, ec.HIST_PA:].sum() == 17 * 121
+    # without the constant-pred poses the table is the same: they touched nothing but BAD
+    keep = ~bad
+    less = ec.accumulate(err_j.cpu().numpy()[keep], err_pa_j.cpu().numpy()[keep], group[keep], 3)
+    less[:3 * ec.ROW].reshape(3, ec.ROW)[:, ec.BAD] = rows[:, ec.BAD]
+    np.testing.assert_array_equal(less, want)
 
 
 # ---- 2. jrr_regress_joints ----

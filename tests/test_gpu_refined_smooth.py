@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import eval_report_cases as ec
 import refined_cases as rc
 import refined_smooth_cases as sc
 from conftest import PKG_NAME
@@ -369,9 +370,10 @@ def test_the_smooth_refined_command_with_its_re_evaluation(driver_table, capsys)
     print(lines[0])
     # the same numbers from the operators themselves on the same joints: the initial regressor, the driver's body, the command's chunks
     # (rows 0 .. 23 and 24 .. 39).  The plain error is checked against the mean-error operator (jrr_evaluate, another kernel).  The
-    # Procrustes error is checked against jrr_evaluate_joints, the operator the command is defined by: these poses are unrelated to
-    # their targets, the 3 x 3 problem behind the alignment is then ill-conditioned, and two separately compiled instances of the
-    # same statements (k_evaluate, k_evaluate_joints) can differ there in the third digit -- printed below, not asserted.
+    # Procrustes error is checked against jrr_evaluate_joints, the operator the command is defined by, and BOTH operators' per-pose
+    # means are held to the float64 reference on those same joints, within 3 x (the reference's own float32 distance from float64
+    # there) + 1e-7 m: these poses are unrelated to their targets, which is where the K^T K eigen-decomposition the kernels once
+    # used came apart between its two compiled instances.
     from importlib import import_module
     smpl = import_module(f'{PKG_NAME}.smpl').SMPL('/nonexistent', batch_size=1, allow_synthetic=True).to(torch.device(DEV))
     J = T(_mod('smpl_model').default_h36m_regressor('/nonexistent', allow_default=True)).float().to(DEV)
@@ -379,16 +381,28 @@ def test_the_smooth_refined_command_with_its_re_evaluation(driver_table, capsys)
 
     def rescored(arrays):
         out = []
+        del host[:]
         for lo, hi in ((0, 24), (24, 40)):
             e = eng.RefineEngine(smpl.device_model, hi - lo)
             e.set_j_regressor(J, utils.find_j_reg_mask(J))
             joints = e.find_joints_forward(T(arrays['shape'][lo:hi]).to(DEV), x6d=T(arrays['pose6d'][lo:hi]).to(DEV))
             g = gt[lo:hi].contiguous()
             err_j, err_pa_j = eng.evaluate_joints(joints, g)
-            out.append(torch.stack(eng.evaluate(joints, g) + (err_j.mean(1), err_pa_j.mean(1))).cpu().numpy() * 1000)
+            means = eng.evaluate(joints, g)
+            out.append(torch.stack(means + (err_j.mean(1), err_pa_j.mean(1))).cpu().numpy() * 1000)
+            host.append((joints.cpu().numpy(), g.cpu().numpy(), means[1].cpu().numpy(), err_pa_j.cpu().numpy()))
         return np.concatenate(out, 1)
+    host = []                                           # per chunk: joints, targets (mm), jrr_evaluate's PA means, the (n,17) PA distances
     for arrays, (a, b) in ((raw, names[:2]), (back, names[2:])):
         err, err_pa, err_joints, err_pa_joints = rescored(arrays)
+        joints_h, gt_h = np.concatenate([h[0] for h in host]), np.concatenate([h[1] for h in host])
+        pa64, pa32 = ec.evaluate_joints(joints_h, gt_h, torch.float64)[2], ec.evaluate_joints(joints_h, gt_h, torch.float32)[2]
+        d = np.abs(pa32 - pa64).max()
+        g_mean = np.abs(np.concatenate([h[2] for h in host]).astype(np.float64) - pa64.mean(1)).max()
+        g_joints = np.abs(np.concatenate([h[3] for h in host]).astype(np.float64).mean(1) - pa64.mean(1)).max()
+        print(f'{b}: per-pose PA means against float64: jrr_evaluate {g_mean:.3e} m, jrr_evaluate_joints {g_joints:.3e} m '
+              f'(reference {d:.3e}, bound {ec.bound(d):.3e})')
+        assert g_mean <= ec.bound(d) and g_joints <= ec.bound(d)
         print(f'{a}: {np.abs(back[a] / err - 1).max():.3e} against jrr_evaluate, {np.abs(back[a] / err_joints - 1).max():.3e} against '
               f'jrr_evaluate_joints;  {b}: {np.abs(back[b] / err_pa - 1).max():.3e}, {np.abs(back[b] / err_pa_joints - 1).max():.3e} (relative)')
         np.testing.assert_allclose(back[a], err, rtol=1e-5)

@@ -99,6 +99,31 @@ def test_g6_evaluate():
     np.testing.assert_allclose(s1.numpy(), g['s1hat'], rtol=0, atol=1e-5)
 
 
+def test_g11_evaluate_on_body_shaped_flat_collinear_and_constant_poses():
+    """the reference's own per-joint errors on the degenerate families (tests/golden/make_golden_eval.py (iii)): the seeds regenerate the
+    stored inputs, and the oracle port lies within 3 x (the stored values' distance from float64) + 1e-7 of them, per family"""
+    import eval_report_cases as ec
+    g = load_golden('g11_eval_degenerate.npz')
+    n = ec.G11_POSES
+    assert g['pred'].shape == (n * len(ec.G11_FAMILIES), 17, 3) and np.isfinite(g['err_pa_j']).all()
+    for k, name in enumerate(ec.G11_FAMILIES):
+        sl = slice(k * n, (k + 1) * n)
+        pred, tgt = ec.family_cases(name, n)
+        assert np.array_equal(pred, g['pred'][sl]) and np.array_equal(tgt, g['target_mm'][sl]), name
+        err = {}
+        for dtype in (torch.float32, torch.float64):
+            p, t = T(pred).to(dtype), T(tgt).to(dtype) / 1000
+            p, t = oracle.move_pelvis(p), oracle.move_pelvis(t)
+            s1 = oracle.batch_compute_similarity_transform_torch(p, t)
+            err[dtype] = torch.sqrt(((p - t) ** 2).sum(dim=-1)).numpy(), torch.sqrt(((s1 - t) ** 2).sum(dim=-1)).numpy()
+        d_plain, d_pa = np.abs(g['err_j'][sl] - err[torch.float64][0]).max(), np.abs(g['err_pa_j'][sl] - err[torch.float64][1]).max()
+        assert d_pa <= ec.FAMILIES[name][1], name
+        assert np.abs(err[torch.float32][0] - g['err_j'][sl]).max() <= ec.bound(d_plain), name
+        assert np.abs(err[torch.float32][1] - g['err_pa_j'][sl]).max() <= ec.bound(d_pa), name
+        if name == 'constant_target':
+            assert not g['err_pa_j'][sl].any() and not err[torch.float32][1].any()
+
+
 def test_g7_inner_loop(smpl_model_np, j_h36m_np):
     g = load_golden('g7_inner_loop.npz')
     sm = importlib.import_module(PKG_NAME + '.smpl_model')

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Device-event times of the evaluation report's three launches at B = 4096:
+"""Device-event times of jrr_evaluate and of the evaluation report's three launches at B = 4096:
 
     python tools/eval_report_time.py [--batch 4096] [--reps 50] [--out profiles/eval_report_time.json]
 
-jrr_evaluate_joints, jrr_regress_joints (the shipped 62-entry regressor and a dense one, n_reg = 1 and 2) and jrr_eval_accumulate,
+jrr_evaluate, jrr_evaluate_joints, jrr_regress_joints (the shipped 62-entry regressor and a dense one, n_reg = 1 and 2) and jrr_eval_accumulate,
 each ALTERNATING with a torch device copy of as many bytes as the launch reads and writes (the copy reads and writes that many
 bytes each, so its time is an upper bound of the memory floor).  Bytes and FLOP are computed here from the shapes.  Needs a GPU: it
 fails without one."""
@@ -68,6 +68,7 @@ def main():
                       'GB_per_s': nbytes / ms / 1e6, 'GFLOP_per_s': flop / ms / 1e6}
         print(f'{name:<28s} {ms:9.4f} ms   copy of {nbytes} B {ms_copy:9.4f} ms')
 
+    add('evaluate', lambda: eng.evaluate(pred, tgt), B * (2 * NJ * 3 * 4 + 2 * 4), 0)
     add('evaluate_joints', lambda: eng.evaluate_joints(pred, tgt), B * (2 * NJ * 3 * 4 + 2 * NJ * 4), 0)
     add('eval_accumulate', lambda: eng.eval_accumulate(err_j, err_pa_j, group, 15, acc), B * (2 * NJ * 4 + 4), 0)
     for tag, J in (('sparse', J_sparse), ('dense', J_dense)):
