@@ -107,6 +107,18 @@ enum {
   JRR_SMOOTH_STATUS_MARKER = 2      /* status bit 1: a listed row whose marker is not 1.0f; that position is skipped */
 };
 
+/* jrr_view_relrot_accumulate / jrr_view_fuse: the camera views of one instant, over the refined-pose table. */
+enum {
+  JRR_FUSE_MAX_VIEWS = 8,           /* members of one group (one scene and frame); a member lies within 7 positions of every other */
+  JRR_FUSE_TILE = 32,               /* positions per workgroup (a result never depends on where its position falls in a tile) */
+  JRR_FUSE_ACC_ROW = 12,            /* int64 per pair: count, the upper triangle of q q^T (ww wx wy wz xx xy xz yy yz zz) in units of 2^-24, one spare */
+  JRR_FUSE_STATUS_INDEX = 1,        /* status bit 0: an entry of order outside [0, n_rows) */
+  JRR_FUSE_STATUS_MARKER = 2,       /* status bit 1: a listed row whose marker is not 1.0f */
+  JRR_FUSE_STATUS_WIDE = 4,         /* status bit 2: the position 8 places before or behind carries the same group id: the group continues
+                                       beyond the 7 positions the kernels look at on either side */
+  JRR_FUSE_STATUS_PAIR = 8          /* status bit 3: a pair id >= n_pairs (or a ref_pair entry outside [0, n_pairs)) */
+};
+
 /* row of the evaluation-report table (jrr_eval_accumulate): JRR_EVAL_ACC_ROW int64 per group, offsets in int64, then a trailer of
  * JRR_EVAL_ACC_TRAILER int64 behind the last row.  Layout version 1. */
 enum {
@@ -396,6 +408,49 @@ int jrr_pose_smooth(const float* table_dev, int64_t n_rows, const int32_t* order
                     float* cam_out_dev, float* delta_deg_dev, int32_t* status_dev, void* stream);
 int jrr_pose_jitter(const float* table_dev, int64_t n_rows, const int32_t* order_dev, const int32_t* run_dev, int m, int begin, int count,
                     float* jitter_deg_dev, int32_t* status_dev, void* stream);
+
+/* The refined poses of a table across the camera views of one instant (`--fuse_refined`).  table_dev as above, only read.  The host
+ * forms three lists from the frame paths: order_dev (m) int32, the table rows sorted by (scene, frame, camera); group_dev (m) int32, the
+ * (scene, frame) of each position, never decreasing, the members of a group contiguous; pair_dev (m) int32, the position's (scene,
+ * camera) in [0, n_pairs) or -1 (no key, or a duplicate).  A position is VALID when its order entry lies in [0, n_rows), the row's marker
+ * is 1.0f, its pair id is below n_pairs and neither position p - 8 nor p + 8 carries its group id; any other position raises its bit
+ * of JRR_FUSE_STATUS_* in status_dev (one int32 the CALLER zeroes), is nobody's member, and its own outputs are NaN (floats) or 0
+ * (counts); every other position is unaffected.  The MEMBERS of p's group: the valid positions within 7 places of p that carry its
+ * group id, ascending -- at most JRR_FUSE_MAX_VIEWS.  Unit quaternion q of a joint of a row: as for jrr_pose_smooth.
+ * a (x) b is the Hamilton product (w = aw bw - ax bx - ay by - az bz, x = aw bx + ax bw + ay bz - az by, y = aw by - ax bz + ay bw +
+ * az bx, z = aw bz + ax by - ay bx + az bw, each summed left to right); conj(a) (x) b as for jrr_pose_smooth.  Every operation after
+ * rot6d_to_rotmat is rounded once, in the order written.
+ *   jrr_view_relrot_accumulate, per position p in [begin, begin + count) with c = pair[p] >= 0 and ref_pair_dev[c] != c (ref_pair_dev
+ *   (n_pairs) int32: the pair of the scene's reference camera): the first member of p's group whose pair is ref_pair[c], if there is
+ *   one, gives e = q_ref(joint 0) (x) conj(q_p(joint 0)), the quaternion of R_ref R_p^T;  acc[c][0] += 1 and
+ *   acc[c][1 + t] += llrintf((e_i * e_j) * 2^24) for the ten pairs i <= j in the order ww wx wy wz xx xy xz yy yz zz (even in e: its sign
+ *   is immaterial).  A non-finite e is not counted.  Integer atomics only: acc_dev (n_pairs, JRR_FUSE_ACC_ROW) int64, zeroed ONCE by the
+ *   caller, is a function of the multiset of positions, whatever their order and the split into calls.
+ *   jrr_view_fuse, per position p in [begin, begin + count) and joint j, with rel_dev (n_pairs, 4) float32 the rotations d_c (w,x,y,z)
+ *   with R_ref ~ D_c R_c, all-zero = unknown (16-byte aligned):
+ *     candidates  j >= 1: every member k, with q_k.   j = 0: the members with pair >= 0 and rel[pair] non-zero, with
+ *                 q'_k = d_pair(k) (x) q_k.  If p itself is none, its six values are copied and delta_orient_deg[p] = NaN.
+ *     anchor a    cos_half_max <= 0 (the plain mean): the first candidate, and every candidate is taken.  Otherwise the candidate of least
+ *                 cost_k = sum over the candidates m != k, ascending, of (1 - |q_k . q_m|), a tie going to the lowest position; taken are
+ *                 the candidates with |q_k . q_a| >= cos_half_max (the caller passes (float)cos(max_deg / 2)).
+ *     s = sum over the taken k, ascending and starting from the first term, of (q_k . q_a < 0 ? -q_k : q_k);  f = s / |s|.
+ *     x6d_out[p][j] = the first two columns of R(f), for j = 0 of R(conj(d_pair(p)) (x) f), in the 6-D layout of jrr_pose_smooth -- but
+ *       when the only taken candidate is p itself, the row's six values bit for bit.
+ *     dropped_out[p] = the number of joints at which p is a candidate and not taken.
+ *     delta_orient_deg[p] = 2 atan2(|e_xyz|, |e_w|) 180 / pi of e = conj(q_p) (x) f at joint 0 (q'_p there);  delta_body_deg[p] = (the sum
+ *       of those angles over the joints 1 .. 23, in joint order) / 23.
+ *   betas_out[p] = (the sum over ALL members, ascending and starting from the first term) / (float)(number of members);
+ *   members_out[p] = that number.  The camera translation is no output: it belongs to the view.
+ *   A position's result depends on its group alone: not on m, the range or the launch's tiling.
+ *   x6d_out_dev (m,24,6) 16-byte aligned, betas_out_dev (m,10), delta_*_deg_dev (m) float32, members_out_dev, dropped_out_dev (m) int32;
+ *   rows outside the range are not touched.  Touches no engine.  No reference counterpart.                                      */
+int jrr_view_relrot_accumulate(const float* table_dev, int64_t n_rows, const int32_t* order_dev, const int32_t* group_dev,
+                               const int32_t* pair_dev, const int32_t* ref_pair_dev, int n_pairs, int m, int begin, int count,
+                               int64_t* acc_dev, int32_t* status_dev, void* stream);
+int jrr_view_fuse(const float* table_dev, int64_t n_rows, const int32_t* order_dev, const int32_t* group_dev, const int32_t* pair_dev,
+                  const float* rel_dev, int n_pairs, int m, float cos_half_max, int begin, int count, float* x6d_out_dev,
+                  float* betas_out_dev, float* delta_body_deg_dev, float* delta_orient_deg_dev, int32_t* members_out_dev,
+                  int32_t* dropped_out_dev, int32_t* status_dev, void* stream);
 
 /* find_joints, scripts/utils.py:85-103 (SMPL forward + J_regressor contraction).
  * Exactly one of x6d_dev (B,24,6) / R_dev (B,24,3,3) is non-NULL.  joints_dev (B,17,3).

@@ -52,6 +52,8 @@ SIGNATURES = {
     'jrr_pose_export': (c_int, [_P, _P, _P, _P, c_int, _P, _P, ctypes.c_int64, _P, c_int, _P]),
     'jrr_pose_smooth': (c_int, [_P, ctypes.c_int64, _P, _P, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     'jrr_pose_jitter': (c_int, [_P, ctypes.c_int64, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    'jrr_view_relrot_accumulate': (c_int, [_P, ctypes.c_int64, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    'jrr_view_fuse': (c_int, [_P, ctypes.c_int64, _P, _P, _P, _P, c_int, c_int, c_float, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     'jrr_find_joints_forward': (c_int, [_P, _P, _P, _P, _P, _P, _P]),
     'jrr_find_joints_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'jrr_smpl_vertices_backward': (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),

@@ -72,6 +72,12 @@ def build_parser() -> argparse.ArgumentParser:
                         help='with --data_root: filter the --save_refined table of DIR along time, per run of consecutive frames of one '
                              'camera (the frame paths of images.pkl), write DIR/refined_smooth.npz with the jitter before and after and the '
                              'joint error of both, print one line and exit (refined.smooth)')
+    parser.add_argument('--fuse_refined', type=str, default=None, metavar='PATH',
+                        help='fuse the table --save_refined wrote (DIR, or a named .npz of it such as DIR/refined_smooth.npz) across the camera '
+                             'views of each (scene, frame) of the frame paths: write DIR/refined_fused.npz with the fused records, how far each '
+                             'view disagreed and the joint error of both, print one line and exit (refined.fuse_views)')
+    parser.add_argument('--fuse_max_deg', type=float, default=30.0,
+                        help='--fuse_refined: a view further than this from the medoid view of a joint is left out of the mean; 0: the plain mean')
     parser.add_argument('--smooth_sigma', type=float, default=2.0, help='--smooth_refined: standard deviation of the Gaussian, in sampled frames')
     parser.add_argument('--smooth_radius', type=int, default=None,
                         help='--smooth_refined: the window reaches this many frames to either side, 0 .. 16 (default: min(16, ceil(3 sigma)))')

@@ -24,6 +24,7 @@
 //   nobody's neighbour and its own outputs are NaN.
 #include "jrr_common.h"
 #include "rot6.h"
+#include "quat.h"
 #include "../../include/jrr.h"
 
 namespace jrr {
@@ -33,12 +34,9 @@ constexpr int SM_THREADS = SM_TILE * JRR_NUM_JOINTS;          // 768: one thread
 constexpr int SM_SLOTS = SM_TILE + 2 * JRR_SMOOTH_MAX_RADIUS; // 64 rows a tile can see
 constexpr int SM_BC = JRR_NUM_BETAS + 3;                      // betas | cam: 13 contiguous floats of a row
 constexpr int SM_X4 = JRR_NUM_JOINTS * 6 / 4;                 // 36 float4 per 6-D output row
-constexpr float SM_DEG = 57.29577951308232f;                  // 180 / pi
 static_assert(JRR_EXPORT_CAM == JRR_EXPORT_BETAS + JRR_NUM_BETAS && JRR_EXPORT_MARKER == JRR_EXPORT_CAM + 3, "betas | cam | marker are contiguous");
 static_assert((JRR_EXPORT_ROW * 4) % 8 == 0 && (JRR_EXPORT_POSE6D * 4) % 8 == 0, "the 6-D values of a joint are 8-byte aligned");
 static_assert(SM_THREADS <= 1024 && JRR_NUM_JOINTS * 6 % 4 == 0, "tile shape");
-
-struct Quat { float w, x, y, z; };
 
 // slot i <-> position first + i: its table row (-1: outside [0, M), or refused with a status bit) and its run
 __device__ __forceinline__ void stage_slots(const float* __restrict__ table, long long n_rows, const int* __restrict__ order,
@@ -58,43 +56,7 @@ __device__ __forceinline__ void stage_slots(const float* __restrict__ table, lon
   }
 }
 
-// rot6d_fwd, included above, keeps the default contraction it has in the loop's kernels; everything below is rounded once per operation,
-// in the order written
-#pragma clang fp contract(off)
-
-__device__ __forceinline__ Quat unit_quat(const float R[9]) {
-  const float r00 = R[0], r11 = R[4], r22 = R[8];
-  const float tr = r00 + r11 + r22;
-  Quat q;
-  if (tr >= r00 && tr >= r11 && tr >= r22) {
-    q.w = 1.f + tr;             q.x = R[7] - R[5];            q.y = R[2] - R[6];            q.z = R[3] - R[1];
-  } else if (r00 >= r11 && r00 >= r22) {
-    q.w = R[7] - R[5];          q.x = 1.f + r00 - r11 - r22;  q.y = R[1] + R[3];            q.z = R[2] + R[6];
-  } else if (r11 >= r22) {
-    q.w = R[2] - R[6];          q.x = R[1] + R[3];            q.y = 1.f + r11 - r00 - r22;  q.z = R[5] + R[7];
-  } else {
-    q.w = R[3] - R[1];          q.x = R[2] + R[6];            q.y = R[5] + R[7];            q.z = 1.f + r22 - r00 - r11;
-  }
-  const float n = sqrtf(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
-  q.w = q.w / n; q.x = q.x / n; q.y = q.y / n; q.z = q.z / n;
-  return q;
-}
-
-__device__ __forceinline__ float qdot(const Quat& a, const Quat& b) { return a.w * b.w + a.x * b.x + a.y * b.y + a.z * b.z; }
-
-// conj(a) (x) b
-__device__ __forceinline__ Quat conj_mul(const Quat& a, const Quat& b) {
-  Quat e;
-  e.w = qdot(a, b);
-  e.x = a.w * b.x - b.w * a.x - (a.y * b.z - a.z * b.y);
-  e.y = a.w * b.y - b.w * a.y - (a.z * b.x - a.x * b.z);
-  e.z = a.w * b.z - b.w * a.z - (a.x * b.y - a.y * b.x);
-  return e;
-}
-
-__device__ __forceinline__ float angle_deg(const Quat& e) {
-  return 2.f * atan2f(sqrtf(e.x * e.x + e.y * e.y + e.z * e.z), fabsf(e.w)) * SM_DEG;
-}
+// quat.h switched contraction off: everything below is rounded once per operation, in the order written
 
 // the unit quaternions of the staged slots' rows: s_q[slot * 24 + joint] (untouched for a slot without row: never read)
 __device__ __forceinline__ void stage_quats(const float* __restrict__ table, int nslots, const int* s_row, float4* s_q) {

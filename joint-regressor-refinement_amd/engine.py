@@ -631,6 +631,53 @@ def pose_jitter(table, order, run, status, begin: int = 0, count: Optional[int] 
     return out
 
 
+def _view_lists(table, order, group, pair, status, begin, count):
+    M = int(order.shape[0])
+    assert table.dim() == 2 and table.shape[1] == 240 and table.dtype == torch.float32 and table.is_contiguous()
+    assert all(t.shape == (M,) and t.dtype == torch.int32 and t.is_contiguous() and t.device == table.device for t in (order, group, pair))
+    assert status.is_contiguous() and status.dtype == torch.int32 and status.device == table.device
+    begin = int(begin)
+    count = M - begin if count is None else int(count)
+    return M, begin, count
+
+
+def view_relrot_accumulate(table, order, group, pair, ref_pair, acc, status, begin: int = 0, count: Optional[int] = None):
+    """jrr_view_relrot_accumulate: positions [begin, begin + count) of `order` / `group` / `pair` (M, int32: table rows sorted by scene,
+    frame and camera, the (scene, frame) and the (scene, camera) of each) add the quaternion outer products of their orientation relative to
+    the scene's reference camera (`ref_pair` (n_pairs,) int32) to `acc` (n_pairs, 12) int64, which the caller zeroed once; returns acc"""
+    lib = _lib.load()
+    M, begin, count = _view_lists(table, order, group, pair, status, begin, count)
+    n_pairs = int(ref_pair.shape[0])
+    assert ref_pair.shape == (n_pairs,) and ref_pair.dtype == torch.int32 and ref_pair.is_contiguous() and ref_pair.device == table.device
+    assert acc.shape == (n_pairs, 12) and acc.dtype == torch.int64 and acc.is_contiguous() and acc.device == table.device
+    check(lib.jrr_view_relrot_accumulate(ptr(table), table.shape[0], ptr(order), ptr(group), ptr(pair), ptr(ref_pair), n_pairs, M, begin, count,
+                                         ptr(acc), ptr(status), stream_ptr(table.device)), 'view_relrot_accumulate')
+    return acc
+
+
+def view_fuse(table, order, group, pair, rel, cos_half_max: float, status, begin: int = 0, count: Optional[int] = None, out=None):
+    """jrr_view_fuse: the views of each group fused -- `rel` (n_pairs, 4) float32 the cameras' rotations to their reference camera,
+    `cos_half_max` = cos(max_deg / 2), 0 for the plain mean.  Computes positions [begin, begin + count) into `out` = (x6d (M,24,6), betas
+    (M,10), delta_body_deg (M,), delta_orient_deg (M,), members (M,) int32, dropped (M,) int32) -- allocated, NaN- / zero-filled, when
+    None -- and returns it; `status` (1,) int32 collects the error bits"""
+    lib = _lib.load()
+    M, begin, count = _view_lists(table, order, group, pair, status, begin, count)
+    dev = table.device
+    n_pairs = int(rel.shape[0])
+    assert rel.shape == (n_pairs, 4) and rel.dtype == torch.float32 and rel.is_contiguous() and rel.device == dev
+    if out is None:
+        out = tuple(torch.full(shape, float('nan'), device=dev) for shape in ((M, NUM_JOINTS, 6), (M, 10), (M,), (M,))) + \
+            tuple(torch.zeros(M, dtype=torch.int32, device=dev) for _ in range(2))
+    x6d, betas, d_body, d_orient, members, dropped = out
+    assert x6d.shape == (M, NUM_JOINTS, 6) and betas.shape == (M, 10) and all(t.shape == (M,) for t in out[2:])
+    assert all(t.dtype == torch.float32 for t in out[:4]) and all(t.dtype == torch.int32 for t in out[4:])
+    assert all(t.is_contiguous() and t.device == dev for t in out)
+    check(lib.jrr_view_fuse(ptr(table), table.shape[0], ptr(order), ptr(group), ptr(pair), ptr(rel), n_pairs, M, float(cos_half_max), begin, count,
+                            ptr(x6d), ptr(betas), ptr(d_body), ptr(d_orient), ptr(members), ptr(dropped), ptr(status), stream_ptr(dev)),
+          'view_fuse')
+    return out
+
+
 def evaluate_joints(pred_j3d: torch.Tensor, target_j3d_mm: torch.Tensor):
     """the per-joint distances behind `evaluate`: err_j, err_pa_j (B,17) in metres (jrr_evaluate_joints)"""
     lib = _lib.load()

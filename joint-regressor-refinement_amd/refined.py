@@ -14,6 +14,11 @@ its J step and at the end of the run.
 from the frame paths and cuts them into runs of consecutive frames; k_pose_jitter and k_pose_smooth (csrc/smooth.hip) measure and filter
 the rotations per run, the existing export writes the filtered records into a copy of the table, and one read-back later
 `refined_smooth.npz` holds every array of `refined.npz` plus the jitter before and after.  `refined.npz` is never rewritten.
+`fuse_views()` is `--fuse_refined DIR`: the table across the camera views of one instant.  `view_groups` orders the refined rows by
+(scene, frame, camera) from the frame paths; k_view_relrot (csrc/views.hip) accumulates each camera's orientation relative to its scene's
+reference camera, `relative_rotations` solves the 4x4 eigenproblems on the host, k_view_fuse averages the views of every frame (a
+medoid-trimmed quaternion mean per joint, the mean of the shapes), the existing export writes the fused records into a copy of the
+table, and `refined_fused.npz` holds every array of its input plus how far each view disagreed with the others.
 """
 from __future__ import annotations
 
@@ -324,8 +329,8 @@ def smooth(directory: str, paths, sigma: float = 2.0, radius: Optional[int] = No
     return out
 
 
-def _rescore_fn(gt_j3d_mm: torch.Tensor, device):
-    """the joint error of the raw and the smoothed rows through the EXISTING operators -- SMPL, find_joints, jrr_evaluate_joints -- in
+def _rescore_fn(gt_j3d_mm: torch.Tensor, device, tag: str = 'smooth'):
+    """the joint error of the raw and the smoothed (`tag`: the suffix of the second pair of names) rows through the EXISTING operators -- SMPL, find_joints, jrr_evaluate_joints -- in
     chunks of --batch_size under ONE regressor (--eval_j_regressor, else the initial one), the body as the driver resolves it"""
     from . import checkpoint, engine as _engine, smpl_model, utils
     from .smpl import SMPL
@@ -358,7 +363,7 @@ def _rescore_fn(gt_j3d_mm: torch.Tensor, device):
                     acc[2 * k, d_idx] = err_j.mean(1) * 1000
                     acc[2 * k + 1, d_idx] = err_pa_j.mean(1) * 1000
         host = acc.cpu().numpy()
-        names = ('mpjpe_eval_mm_raw', 'pampjpe_eval_mm_raw', 'mpjpe_eval_mm_smooth', 'pampjpe_eval_mm_smooth')
+        names = ('mpjpe_eval_mm_raw', 'pampjpe_eval_mm_raw', 'mpjpe_eval_mm_' + tag, 'pampjpe_eval_mm_' + tag)
         more = {name: host[k] for k, name in enumerate(names)}
         numbers = {name + '_mean': _nanmean(host[k]) for k, name in enumerate(names)}
         numbers['eval_j_regressor'] = args.eval_j_regressor or args.j_regressor_init
@@ -393,4 +398,219 @@ def smooth_command(log=print) -> Optional[dict]:
         f'{fmt(doc["jitter_deg_raw_mean"])} -> {fmt(doc["jitter_deg_mean"])} deg/frame^2, moved {fmt(doc["smooth_delta_deg_mean"])} deg, MPJPE '
         f'{fmt(doc["mpjpe_eval_mm_raw_mean"])} -> {fmt(doc["mpjpe_eval_mm_smooth_mean"])}, PAMPJPE {fmt(doc["pampjpe_eval_mm_raw_mean"])} -> '
         f'{fmt(doc["pampjpe_eval_mm_smooth_mean"])}; {os.path.join(args.smooth_refined, SMOOTH_NAME)}')
+    return out
+
+
+# ---- across the camera views of one instant (`--fuse_refined`) --------------------------------------------------------------
+FUSE_NAME = 'refined_fused.npz'
+FUSE_MAX_VIEWS = 8            # include/jrr.h: JRR_FUSE_MAX_VIEWS
+FUSE_ACC_ROW = 12             # include/jrr.h: JRR_FUSE_ACC_ROW
+FUSE_STATUS_BITS = {1: 'bit 0: an entry of the view order lies outside the table', 2: 'bit 1: a listed row holds no refined pose',
+                    4: 'bit 2: a group continues beyond the 7 positions on either side', 8: 'bit 3: a pair id outside [0, n_pairs)'}
+
+
+def view_key(path) -> Tuple[Optional[str], Optional[str], int]:
+    """(scene, camera, frame) of a frame path `<scene>/imageSequence/<camera>/img_%06d.jpg`: the scene is everything before
+    `imageSequence`, the camera the directory below it, the frame as sequence_key reads it.  (None, None, -1) for a path sequence_key
+    refuses."""
+    key, frame = sequence_key(path)
+    if key is None:
+        return None, None, -1
+    parts = key.split('/')
+    return '/'.join(parts[:-2]), parts[-1], frame
+
+
+def view_groups(paths, has_refined):
+    """(order (M,) int32, group (M,) int32, pair (M,) int32, ref_pair (n_pairs,) int32, names, duplicates): the table rows with
+    has_refined == 1 ordered by (scene, frame, camera, dataset index) and cut into groups -- one per (scene, frame), its members
+    contiguous and in camera order; group ids start at 0 and never decrease.  A second row with the (scene, frame, camera) of an earlier
+    one is a DUPLICATE: a group of one directly behind the group of its frame, counted in `duplicates`.  A row without key (view_key)
+    is a group of one behind all keyed rows, in dataset order.  pair: the id of the position's (scene, camera) in [0, n_pairs) -- the
+    pairs that occur, sorted by (scene, camera); `names[c]` is that (scene, camera) -- or -1 for keyless rows and duplicates.
+    ref_pair[c]: the pair of the scene's reference camera, its first camera in sorted order (ref_pair[c] == c for that camera).
+    A group of more than 8 members raises ValueError.  `paths`: one frame path per row, or arrays (scenes, cameras, frames) -- or
+    (cameras, frames) for a single scene -- where a negative frame marks a row without key."""
+    has = np.asarray(has_refined).astype(bool)
+    N = has.shape[0]
+    if isinstance(paths, tuple) and len(paths) in (2, 3) and not isinstance(paths[0], str) and len(paths[0]) == N:
+        cols = [np.asarray(a).tolist() for a in paths]
+        scenes, cams, frames = ([0] * N, cols[0], cols[1]) if len(paths) == 2 else cols
+        parsed = [(None, None, -1) if f < 0 else (sc, c, int(f)) for sc, c, f in zip(scenes, cams, frames)]
+    else:
+        parsed = [view_key(p) for p in paths]
+    if len(parsed) != N:
+        raise ValueError(f'view_groups: {len(parsed)} paths for a table of {N} rows')
+    idx = np.nonzero(has)[0]
+    keyed = [int(i) for i in idx if parsed[i][0] is not None]
+    stray = [int(i) for i in idx if parsed[i][0] is None]
+    keyed.sort(key=lambda i: (parsed[i][0], parsed[i][2], parsed[i][1], i))
+    dup = [k > 0 and parsed[keyed[k]] == parsed[keyed[k - 1]] for k in range(len(keyed))]
+    names = sorted({(parsed[i][0], parsed[i][1]) for i in keyed})
+    lut = {n: c for c, n in enumerate(names)}
+    first = {}
+    for c, (scene, _) in enumerate(names):
+        first.setdefault(scene, c)
+    ref_pair = np.array([first[scene] for scene, _ in names], dtype=np.int32).reshape(-1)
+    order, group, pair = [], [], []
+    g, at = -1, 0
+    while at < len(keyed):
+        end = at
+        while end < len(keyed) and parsed[keyed[end]][0] == parsed[keyed[at]][0] and parsed[keyed[end]][2] == parsed[keyed[at]][2]:
+            end += 1
+        members = [k for k in range(at, end) if not dup[k]]
+        if len(members) > FUSE_MAX_VIEWS:
+            raise ValueError(f'view_groups: {len(members)} views of frame {parsed[keyed[at]][2]} of {parsed[keyed[at]][0]!r}: at most {FUSE_MAX_VIEWS}')
+        g += 1
+        for k in members:
+            order.append(keyed[k]); group.append(g); pair.append(lut[parsed[keyed[k]][:2]])
+        for k in range(at, end):
+            if dup[k]:
+                g += 1
+                order.append(keyed[k]); group.append(g); pair.append(-1)
+        at = end
+    for i in stray:
+        g += 1
+        order.append(i); group.append(g); pair.append(-1)
+    as32 = lambda a: np.array(a, dtype=np.int32).reshape(-1)
+    return as32(order), as32(group), as32(pair), ref_pair, names, int(sum(dup))
+
+
+def relative_rotations(acc, ref_pair=None) -> Tuple[np.ndarray, np.ndarray]:
+    """(rel (n_pairs, 4) float32, residual_deg (n_pairs,) float64) of the table jrr_view_relrot_accumulate filled: per pair the 4x4
+    symmetric matrix acc / (2^24 count) in float64, the eigenvector of its largest eigenvalue lambda (numpy.linalg.eigh) with w >= 0 --
+    the rotation d_c with R_ref ~ D_c R_c -- and 2 acos(sqrt(min(1, lambda))) in degrees, the RMS-like spread of the per-frame relative
+    rotations about d_c.  A reference camera (ref_pair[c] == c) gets (1, 0, 0, 0) and residual 0; a pair with count 0 gets (0, 0, 0, 0),
+    meaning unknown, and residual NaN."""
+    acc = np.asarray(acc, dtype=np.int64).reshape(-1, FUSE_ACC_ROW)
+    n = acc.shape[0]
+    rel, res = np.zeros((n, 4), dtype=np.float64), np.full(n, np.nan)
+    iu = np.triu_indices(4)
+    for c in range(n):
+        if ref_pair is not None and int(ref_pair[c]) == c:
+            rel[c], res[c] = (1.0, 0.0, 0.0, 0.0), 0.0
+            continue
+        if acc[c, 0] <= 0:
+            continue
+        A = np.zeros((4, 4))
+        A[iu] = acc[c, 1:11].astype(np.float64) / (2.0 ** 24 * float(acc[c, 0]))
+        A = A + np.triu(A, 1).T
+        lam, U = np.linalg.eigh(A)
+        d = U[:, -1]
+        rel[c] = -d if d[0] < 0 else d
+        res[c] = np.degrees(2.0 * np.arccos(np.sqrt(min(1.0, max(0.0, float(lam[-1]))))))
+    return rel.astype(np.float32), res
+
+
+def _axis_angle_deg(q) -> list:
+    q = np.asarray(q, dtype=np.float64)
+    n = float(np.linalg.norm(q[1:]))
+    if n == 0.0:
+        return [0.0, 0.0, 0.0]
+    return (q[1:] / n * np.degrees(2.0 * np.arctan2(n, abs(q[0]))) * (1.0 if q[0] >= 0 else -1.0)).tolist()
+
+
+def fuse_views(directory_or_npz: str, paths, max_deg: float = 30.0, device=None, rescore=None) -> Dict[str, np.ndarray]:
+    """`--fuse_refined DIR`: the table of DIR/refined.npz -- or of the named `.npz` of its directory, as load_path reads it -- fused across
+    the camera views of each (scene, frame).  Uploads the table, accumulates every camera's orientation relative to its scene's reference
+    camera (jrr_view_relrot_accumulate), reads that small table back and solves it (relative_rotations), fuses the views
+    (jrr_view_fuse; max_deg 0 selects the plain mean) and writes the fused records -- with each row's OWN cam and extras -- into a COPY of
+    the table with the existing pose_export operator, so the fused `pose` is the same log map of the same 6-D map; one more read-back.
+    Writes DIR/refined_fused.npz (every array of the input + view_group / n_views / view_pair, -1 outside the order, fuse_delta_body_deg /
+    fuse_delta_orient_deg, NaN there, and fuse_dropped) and adds `fuse` to DIR/meta.json; the input file is not rewritten.  `paths` as
+    view_groups takes them, `rescore` as in smooth().  Returns the arrays."""
+    from . import engine as _engine
+    max_deg = float(max_deg)
+    if not (0.0 <= max_deg <= 360.0):
+        raise ValueError(f'fuse_views: max_deg {max_deg}: 0 (the plain mean) .. 360')
+    directory = (os.path.dirname(directory_or_npz) or '.') if str(directory_or_npz).endswith('.npz') else directory_or_npz
+    raw = load_path(directory_or_npz)
+    meta = raw.pop('meta')
+    N = raw['has_refined'].shape[0]
+    order, group, pair, ref_pair, names, duplicates = view_groups(paths, raw['has_refined'])
+    M, n_pairs = order.shape[0], ref_pair.shape[0]
+    cos_half_max = float(np.float32(np.cos(np.radians(max_deg) / 2.0))) if max_deg > 0 else 0.0
+    device = torch.device(args.device if device is None else device)
+    host_table = pack(raw)
+    acc = np.zeros((n_pairs, FUSE_ACC_ROW), dtype=np.int64)
+    if M:
+        table = torch.from_numpy(host_table).to(device)
+        d_order, d_group, d_pair, d_ref = (torch.from_numpy(a).to(device) for a in (order, group, pair, ref_pair))
+        status, status_x = torch.zeros(1, dtype=torch.int32, device=device), torch.zeros(1, dtype=torch.int32, device=device)
+        d_acc = torch.zeros((n_pairs, FUSE_ACC_ROW), dtype=torch.int64, device=device)
+        _engine.view_relrot_accumulate(table, d_order, d_group, d_pair, d_ref, d_acc, status)
+        acc = d_acc.cpu().numpy()                                  # the 4x4 solves need it
+    rel, residual = relative_rotations(acc, ref_pair)
+    if M:
+        x6d, betas, d_body, d_orient, members, dropped = _engine.view_fuse(table, d_order, d_group, d_pair, torch.from_numpy(rel).to(device),
+                                                                           cos_half_max, status)
+        rows = d_order.long()
+        copy = table.clone()
+        copy[rows, MARKER] = 0                                     # the export claims the rows it writes
+        _engine.pose_export(x6d, betas, table[rows, CAM:MARKER].contiguous(), rows, copy, status_x,
+                            extra=table[rows, EXTRA:EXTRA + len(EXTRA_NAMES)].contiguous())
+        flat = torch.cat([copy.reshape(-1), d_body, d_orient, members.float(), dropped.float(), status.float(), status_x.float()]).cpu().numpy()
+        st, st_x = int(flat[-2]), int(flat[-1])                    # ... the one read-back behind the last launch
+        if st:
+            raise RuntimeError('fuse_views: status ' + '; '.join(msg for bit, msg in FUSE_STATUS_BITS.items() if st & bit))
+        host_table = flat[:N * ROW].reshape(N, ROW)
+        per_pos = flat[N * ROW:N * ROW + 4 * M].reshape(4, M)
+    else:
+        st_x, per_pos = 0, np.zeros((4, 0), dtype=np.float32)
+    out = dict(raw)
+    out.update(unpack(host_table, status=st_x))
+    for k, name in enumerate(('fuse_delta_body_deg', 'fuse_delta_orient_deg')):
+        out[name] = np.full(N, np.nan, dtype=np.float32)
+        out[name][order] = per_pos[k]
+    out['view_group'], out['n_views'], out['view_pair'] = (np.full(N, -1, np.int32) for _ in range(3))
+    out['view_group'][order], out['n_views'][order], out['view_pair'][order] = group, per_pos[2].astype(np.int32), pair
+    out['fuse_dropped'] = np.zeros(N, np.int32)
+    out['fuse_dropped'][order] = per_pos[3].astype(np.int32)
+    n_groups = int(group[-1]) + 1 if M else 0
+    hist = np.bincount(np.bincount(group, minlength=n_groups)) if M else np.zeros(0, dtype=np.int64)
+    doc = {'max_deg': max_deg, 'positions': int(M), 'groups': n_groups, 'duplicates': int(duplicates),
+           'views_per_group_histogram': {str(n): int(c) for n, c in enumerate(hist) if c},
+           'pairs': [{'scene': str(scene), 'camera': str(camera), 'count': int(acc[c, 0]), 'reference': bool(ref_pair[c] == c),
+                      'd_axis_angle_deg': _axis_angle_deg(rel[c]), 'residual_deg': None if np.isnan(residual[c]) else float(residual[c])}
+                     for c, (scene, camera) in enumerate(names)],
+           'fuse_delta_body_deg_mean': _nanmean(out['fuse_delta_body_deg']), 'fuse_delta_orient_deg_mean': _nanmean(out['fuse_delta_orient_deg']),
+           'dropped_share': float(out['fuse_dropped'].sum()) / (24.0 * M) if M else None}
+    if rescore is not None:
+        more, numbers = rescore(raw, out)
+        out.update(more)
+        doc.update(numbers)
+    np.savez(os.path.join(directory, FUSE_NAME), **out)
+    with open(os.path.join(directory, 'meta.json'), 'w') as f:
+        json.dump(dict(meta, fuse=doc), f, indent=1, sort_keys=True, default=str)
+    out['meta'] = dict(meta, fuse=doc)
+    return out
+
+
+def fuse_command(log=print) -> Optional[dict]:
+    """`python main.py --fuse_refined DIR --data_root ROOT [--fuse_max_deg 30]`: refined.fuse_views on the split the table was written
+    from, the frame paths from its images.pkl, plus the joint error of the raw and the fused rows -- each row in its own camera's frame,
+    the frame of its gt_j3d.  One process: under torchrun rank 0 works and the other ranks return.  Prints one summary line."""
+    from . import data as jdata
+    if jdist.env_rank_world()[0] != 0:                      # the command joins no process group: the launcher's rank decides
+        return None
+    if not args.data_root:
+        raise ValueError('--fuse_refined needs --data_root (the frame paths and the ground truth of the split the table was written from)')
+    location = jdata.split_location('validation', args.data_root)
+    paths = jdata.split_image_paths(location)
+    if paths is None:
+        raise FileNotFoundError(f'--fuse_refined: {os.path.join(location, "images.pkl")} is missing: the frame paths say which samples show the same instant')
+    ds = jdata.data_set('validation', root=args.data_root)
+    n_table = load_path(args.fuse_refined)['has_refined'].shape[0]
+    if not (len(paths) == len(ds) == n_table):
+        raise ValueError(f'--fuse_refined: the table holds {n_table} samples, the split {len(ds)} with {len(paths)} frame paths')
+    device = torch.device(args.device)
+    torch.cuda.set_device(device)
+    out = fuse_views(args.fuse_refined, paths, max_deg=args.fuse_max_deg, device=device, rescore=_rescore_fn(ds.gt_j3d, device, tag='fused'))
+    doc = out['meta']['fuse']
+    fmt = lambda v, spec='.4f': '-' if v is None else format(v, spec)
+    directory = (os.path.dirname(args.fuse_refined) or '.') if str(args.fuse_refined).endswith('.npz') else args.fuse_refined
+    log(f'fused {doc["positions"]} poses in {doc["groups"]} groups over {len(doc["pairs"])} cameras (max {doc["max_deg"]:g} deg, '
+        f'{doc["duplicates"]} duplicates): body moved {fmt(doc["fuse_delta_body_deg_mean"])} deg, orientation '
+        f'{fmt(doc["fuse_delta_orient_deg_mean"])} deg, dropped {fmt(doc["dropped_share"])}, MPJPE {fmt(doc["mpjpe_eval_mm_raw_mean"])} -> '
+        f'{fmt(doc["mpjpe_eval_mm_fused_mean"])}, PAMPJPE {fmt(doc["pampjpe_eval_mm_raw_mean"])} -> {fmt(doc["pampjpe_eval_mm_fused_mean"])}; '
+        f'{os.path.join(directory, FUSE_NAME)}')
     return out

@@ -6,7 +6,8 @@ Runs set_seed(0), optimize_pose_refiner() and then the evaluation report test_po
 main.py:26-27) need the external VIBE / MEVA checkouts: the networks are out of scope, what those functions do with the
 networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evaluate_vertices), which runs alone and exits.
 `--regressor_report DIR` (regressor_report.py) adds to either evaluation what the retrained regressor did to each joint, with pictures.
-`--smooth_refined DIR` (refined.smooth_command) filters a `--save_refined` table along time and exits as well."""
+`--smooth_refined DIR` (refined.smooth_command) filters a `--save_refined` table along time and exits as well;
+`--fuse_refined DIR` (refined.fuse_command) fuses its camera views of each frame and exits."""
 import importlib
 import os
 import sys
@@ -38,6 +39,9 @@ if __name__ == '__main__':
         sys.exit(0)
     if args.smooth_refined:                                                  # a --save_refined table along the time axis; no training
         importlib.import_module(PKG + '.refined').smooth_command()
+        sys.exit(0)
+    if args.fuse_refined:                                                    # ... across the camera views of each frame; no training
+        importlib.import_module(PKG + '.refined').fuse_command()
         sys.exit(0)
     res = optimize.optimize_pose_refiner()                                   # main.py:23
     if args.save_refined and int(os.environ.get('RANK', '0')) == 0:
