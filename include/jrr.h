@@ -161,6 +161,25 @@ enum {
   JRR_DISCS_MAX_POINTS = 256
 };
 
+/* jrr_accel_error: the acceleration error along each video sequence, and the row of its table: JRR_ACCEL_ACC_ROW int64 per group,
+ * offsets in int64, then the trailer of the evaluation table behind the last row.  Layout version 1.
+ * Overflow: a value below the cap 1.0e3f gives llrintf(v * 2^24) < 2^34, so a sum stays below 2^63 for 5e8 triples in one word. */
+enum {
+  JRR_ACCEL_ACC_LAYOUT_VERSION = 1,
+  JRR_ACCEL_TILE = 32,              /* positions per workgroup (a result never depends on where its position falls in a tile) */
+  JRR_ACCEL_STATUS_INDEX = 1,       /* status bit 0: an entry of order outside [0, n_rows); that position is absent */
+  JRR_ACCEL_ACC_ROW = 205,
+  JRR_ACCEL_ACC_COUNT = 0,          /* triples scored */
+  JRR_ACCEL_ACC_BAD = 1,            /* triples of this group left out: one of their 51 values e_j, s_j, g_j fails v < 1.0e3f (NaN, inf, absurd) */
+  JRR_ACCEL_ACC_NO_TRIPLE = 2,      /* positions of this group without a triple */
+  JRR_ACCEL_ACC_SUM_ERR = 3,        /* 17: sum over the triples of llrintf(e_j * 2^24), per joint (units of 2^-24 m per sampled frame^2) */
+  JRR_ACCEL_ACC_SUM_PRED = 20,      /* 17: the same for s_j = |a_pred| */
+  JRR_ACCEL_ACC_SUM_GT = 37,        /* 17: the same for g_j = |a_gt| */
+  JRR_ACCEL_ACC_HIST = 54,          /* 151: histogram of e_j over all 17 joints, bin min((int)floorf(e * 1000.f), 150): the bins of JRR_EVAL_ACC_HIST */
+  JRR_ACCEL_ACC_BINS = 151,
+  JRR_ACCEL_ACC_TRAILER = 2         /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
+};
+
 #define JRR_FLAG_SIL_SIZE(size) ((((size) / 32) & 15) << 16)
 
 typedef struct jrr_model jrr_model_t;   /* device-resident, re-laid-out SMPL constants */
@@ -579,6 +598,40 @@ int jrr_regress_joints(const float* verts_dev, int batch, const void* workspace_
  * calls or on the sharding over ranks (sum the ranks' tables).                                                              */
 int jrr_eval_accumulate(const float* err_j_dev, const float* err_pa_j_dev, const int32_t* group_dev, int batch, int n_groups,
                         int64_t* acc_dev, void* stream);
+
+/* The acceleration error along each video sequence (`--eval_accel`; the HMMR / VIBE convention, no reference counterpart in code:
+ * this text is the specification).  pred_dev (n_rows,17,3) fp32 metres and gt_mm_dev (n_rows,17,3) fp32 millimetres are tables whose
+ * row is the dataset index; both are only read.  order_dev (m) int32 lists table rows in time order and run_dev (m) int32 gives each
+ * position's run of consecutive frames of one camera (the host forms both from the frame paths, as for jrr_pose_smooth); group_dev
+ * (m) int32 or NULL (every position in group 0) is each position's group.  A position p has a TRIPLE when 0 <= p - 1, p + 1 < m,
+ * run[p - 1] == run[p] == run[p + 1] and none of the three is absent (below): not the first or last of its run, no run shorter than 3.
+ * The neighbours are looked up in the whole list [0, m), whatever the range.  Per frame of the triple, as jrr_evaluate centres its
+ * inputs: x = P - P[0], y = G / 1000 - (G / 1000)[0].  Per joint j and component:
+ *   a_pred = (x[p-1] - 2 x[p]) + x[p+1], a_gt the same expression on y;  e_j = |a_pred - a_gt|, s_j = |a_pred|, g_j = |a_gt|,
+ *   |v| = sqrtf((v0 v0 + v1 v1) + v2 v2): metres per sampled frame^2.
+ * Every operation is rounded once in fp32, in the order written; no product is fused into a sum.
+ *   begin, count   the positions [begin, begin + count) the call computes.  The per-position outputs err_j_dev, acc_pred_j_dev,
+ *                  acc_gt_j_dev (m,17) fp32 -- e_j, s_j, g_j; each may be NULL -- are indexed by position and the other rows are not
+ *                  touched.  A position without a triple gets 17 NaN in each.  A result depends on its triple alone: not on m, the
+ *                  range or the launch's tiling (JRR_ACCEL_TILE positions per workgroup).
+ *   acc_dev        NULL, or int64 [n_groups][JRR_ACCEL_ACC_ROW] + JRR_ACCEL_ACC_TRAILER words, layout above, to which the call ADDS
+ *                  its positions; the caller zeroes it once per report.  1 <= n_groups <= JRR_EVAL_ACC_MAX_GROUPS.  A position adds
+ *                  to exactly one word class: group < 0 to trailer word 0 only; group >= n_groups to trailer word 1 only (the caller's
+ *                  error); otherwise, in row group[p]: without a triple NO_TRIPLE += 1 only; with one of the 51 values e_j, s_j, g_j
+ *                  failing v < 1.0e3f (NaN, inf; a guard against overflow, no tolerance) BAD += 1 only -- its per-position outputs
+ *                  still hold what was computed --; else COUNT += 1 and per joint SUM_ERR += llrintf(e_j * 2^24), SUM_PRED +=
+ *                  llrintf(s_j * 2^24), SUM_GT += llrintf(g_j * 2^24), HIST[min((int)floorf(e_j * 1000.f), 150)] += 1.
+ *                  Integer atomics only: the table is a function of the multiset of positions -- not of the order, the split into
+ *                  calls or the sharding over ranks (sum the ranks' tables).
+ *   status_dev     one int32 the CALLER zeroes and reads when it next synchronises: bit 0 (JRR_ACCEL_STATUS_INDEX) an entry of order
+ *                  outside [0, n_rows).  Such a position is ABSENT: it forms no triple (NaN outputs, NO_TRIPLE) and is nobody's
+ *                  neighbour; every other position is unaffected.
+ * count == 0 returns JRR_OK without a launch.  JRR_ERR_ARG with a message: a NULL pred / gt_mm / order / run / status, a negative
+ * size, a range outside [0, m), all four outputs NULL, n_groups out of range with acc_dev given, a misaligned array (4 bytes, acc_dev 8).
+ * Touches no engine.                                                                                                         */
+int jrr_accel_error(const float* pred_dev, const float* gt_mm_dev, int64_t n_rows, const int32_t* order_dev, const int32_t* run_dev,
+                    const int32_t* group_dev, int m, int begin, int count, int n_groups, float* err_j_dev, float* acc_pred_j_dev,
+                    float* acc_gt_j_dev, int64_t* acc_dev, int32_t* status_dev, void* stream);
 
 /* ---- regressor report (`--regressor_report`): how far the retrained regressor moved each joint, and discs on a picture ------
  * No reference counterpart in code: the reference's teaser.png shows the joints of the accepted regressor, of the retrained one and

@@ -94,6 +94,11 @@ def build_parser() -> argparse.ArgumentParser:
                              'scripts/test.py:141-301 does with the vertices of other models; no SMPL model file is read.  The regressors '
                              'are multiplied by find_j_reg_mask of the initial one as at scripts/test.py:108 (the convention of '
                              'test_pose_refiner_model; :206-212 applies no mask -- the reference\'s mask is all ones, so the two agree)')
+    parser.add_argument('--eval_accel', action='store_true',
+                        help='with --eval_report DIR (the evaluation, --eval_vertices): also write DIR/accel.json and DIR/accel.md, the '
+                             'acceleration error of both regressors\' joints along each video sequence -- per run of consecutive frames of '
+                             'one camera, from the frame paths (images.pkl; paths.txt) -- in mm per sampled frame^2 (accel_report.py); with '
+                             '--smooth_refined / --fuse_refined: the per-sample accel_err_mm_* arrays of the raw and the processed rows')
     parser.add_argument('--regressor_report', type=str, default=None, metavar='DIR',
                         help='regressor report: DIR/regressor.json and DIR/regressor.md -- per H36M joint the support of the initial and '
                              'the retrained regressor and how far, in a frame fixed to the body, the retrained one moves the joint on the '

@@ -1,6 +1,6 @@
 // Internal launcher interface: the launch_* functions that cross a translation unit, i.e. the kernels of prep / lbs / gemm / sup / fold
 // and the few of disc / sil that the engine (api.hip) and the fused loop (refine.hip) launch.  A launcher with no caller outside the file
-// of its kernel is static there and is not listed; the feature files (image, report, shade, export, eval, evalrep, regrep, smooth) keep
+// of its kernel is static there and is not listed; the feature files (image, report, shade, export, eval, evalrep, regrep, smooth, views, accel) keep
 // their include/jrr.h entry points beside their kernels and declare nothing here.
 #pragma once
 #include "jrr_common.h"

@@ -738,6 +738,45 @@ def eval_accumulate(err_j: torch.Tensor, err_pa_j: torch.Tensor, group: torch.Te
           'eval_accumulate')
 
 
+ACCEL_ACC_ROW, ACCEL_ACC_TRAILER, ACCEL_TILE = 205, 2, 32      # include/jrr.h: JRR_ACCEL_ACC_ROW, JRR_ACCEL_ACC_TRAILER, JRR_ACCEL_TILE
+
+
+def accel_error(pred: torch.Tensor, gt_mm: torch.Tensor, order: torch.Tensor, run: torch.Tensor, status: torch.Tensor,
+                group: Optional[torch.Tensor] = None, n_groups: int = 1, acc: Optional[torch.Tensor] = None, begin: int = 0,
+                count: Optional[int] = None, out=None, rows: bool = True):
+    """jrr_accel_error: the acceleration error of positions [begin, begin + count) of `order` / `run` (M, int32: rows of the tables
+    `pred` (n_rows,17,3) m and `gt_mm` (n_rows,17,3) mm in time order, and each position's run).  rows: the per-position outputs
+    `out` = (err_j, acc_pred_j, acc_gt_j), (M,17) each -- allocated, NaN-filled, when None -- are written and returned (rows=False:
+    none, None is returned).  acc: the int64 table (n_groups * 205 + 2 words, include/jrr.h JRR_ACCEL_ACC_*) the positions are ADDED to
+    by `group` (M, int32; None: group 0).  `status` (1,) int32 collects the error bit."""
+    lib = _lib.load()
+    M = int(order.shape[0])
+    dev = pred.device
+    n_rows = int(pred.shape[0])
+    assert pred.shape == (n_rows, 17, 3) and gt_mm.shape == (n_rows, 17, 3) and pred.dtype == torch.float32 and gt_mm.dtype == torch.float32
+    assert pred.is_contiguous() and gt_mm.is_contiguous()
+    assert order.shape == (M,) and run.shape == (M,) and order.dtype == torch.int32 and run.dtype == torch.int32
+    assert order.is_contiguous() and run.is_contiguous() and status.is_contiguous() and status.dtype == torch.int32
+    assert all(t.device == dev for t in (gt_mm, order, run, status))
+    if group is not None:
+        assert group.shape == (M,) and group.dtype == torch.int32 and group.is_contiguous() and group.device == dev
+    if acc is not None:
+        assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.device == dev
+        assert acc.numel() == int(n_groups) * ACCEL_ACC_ROW + ACCEL_ACC_TRAILER
+    begin = int(begin)
+    count = M - begin if count is None else int(count)
+    if rows:
+        if out is None:
+            out = tuple(torch.full((M, 17), float('nan'), device=dev) for _ in range(3))
+        assert len(out) == 3 and all(t.shape == (M, 17) and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in out)
+    else:
+        out = None
+    e, s, g = out if out is not None else (None, None, None)
+    check(lib.jrr_accel_error(ptr(pred), ptr(gt_mm), n_rows, ptr(order), ptr(run), ptr(group), M, begin, count, int(n_groups), ptr(e), ptr(s),
+                              ptr(g), ptr(acc), ptr(status), stream_ptr(dev)), 'accel_error')
+    return out
+
+
 SHIFT_ACC_ROW, SHIFT_ACC_TRAILER = 1277, 2      # include/jrr.h: JRR_SHIFT_ACC_ROW, JRR_SHIFT_ACC_TRAILER
 DISCS_MAX_SETS, DISCS_MAX_POINTS = 8, 256       # include/jrr.h: JRR_DISCS_MAX_SETS, JRR_DISCS_MAX_POINTS
 

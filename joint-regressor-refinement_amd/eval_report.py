@@ -274,13 +274,15 @@ def open_vertices_dir(directory: str, kind: str = 'action'):
 def evaluate_vertices(log=print) -> Optional[dict]:
     """`--eval_vertices DIR --eval_report OUT`: rank r takes shard_bounds(N, r, world) of the meshes in chunks of --batch_size
     (pinned uploads), both regressors on one read of the vertices, one all-reduce per report at the end."""
-    from . import checkpoint, engine as _engine, regressor_report, smpl_model, utils
+    from . import accel_report, checkpoint, engine as _engine, regressor_report, smpl_model, utils
     from .args import args
     if not args.eval_report and not args.regressor_report:
         raise ValueError('--eval_vertices needs --eval_report or --regressor_report DIR (where eval.json / eval.md, regressor.json / '
                          'regressor.md go)')
     regressor_report.check_flags(args._get())
+    accel_report.check_flags(args._get())
     verts, gt, names, ids = open_vertices_dir(args.eval_vertices, args.eval_groups)          # before any launch
+    accel_paths = accel_report.read_paths(args.eval_vertices, verts.shape[0]) if args.eval_accel else None
     jdist.init(args.dist_backend)
     rank, local_rank, world = jdist.env_rank_world()
     device = torch.device(args.device if (world == 1 or args.single_device) else f'cuda:{local_rank}')
@@ -296,6 +298,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     mask_np = utils.find_j_reg_mask(J_before).numpy()
     shift = regressor_report.Run(args._get(), names, device, J_np, J_after.cpu().numpy(), mask_np, 'vertices') if args.regressor_report else None
     N = verts.shape[0]
+    track = accel_report.JointTrack(N, 2, device) if accel_paths is not None else None
     lo, hi = jdist.shard_bounds(N, rank, world)
     bs = max(1, int(args.batch_size))
     stage = [(torch.empty((bs, 6890, 3), dtype=torch.float32).pin_memory(), torch.empty((bs, NJ, 3), dtype=torch.float32).pin_memory(),
@@ -319,6 +322,8 @@ def evaluate_vertices(log=print) -> Optional[dict]:
             if reports is not None:
                 reports['before'].add(joints[0], gtc, di)
                 reports['after'].add(joints[1], gtc, di)
+            if track is not None:
+                track.add(np.arange(a, b), (joints[0], joints[1]), gtc)
             if shift is not None:
                 shift.add(dv, joints[0], joints[1], gtc, di, ids[a:b] >= 0)
     initial, retrained = (args.j_regressor_init, sha16(args.j_regressor_init, J_np)), (path, sha16(path))
@@ -328,10 +333,16 @@ def evaluate_vertices(log=print) -> Optional[dict]:
         if reports is None:
             return shift_doc
     results = {k: r.finish() for k, r in reports.items()}
-    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', dict(vars(args._get())), initial, retrained)
+    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', accel_report.flags_doc(args._get()), initial, retrained)
+    accel_doc = None
+    if track is not None:      # every mesh is present and every rank knows it: the float all-reduce, the launches, the integer all-reduce
+        accel_doc = accel_report.write(args.eval_report, track.finish(accel_paths, ids, names, ('before', 'after'), present=np.ones(N, dtype=bool)),
+                                       args.eval_groups, 'vertices')
     if rank == 0:
         for k in ('before', 'after'):
             r = results[k][ALL]
             log(f'{k}: n {r["n"]} (bad {r["n_bad"]})  MPJPE {_fmt(r["mpjpe_mm"], ".4f")}  PAMPJPE {_fmt(r["pampjpe_mm"], ".4f")}')
+        if accel_doc is not None:
+            log(accel_report.summary_line(accel_doc))
         log(f'evaluation report: {os.path.join(args.eval_report, "eval.md")}')
     return doc

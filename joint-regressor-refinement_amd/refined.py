@@ -119,7 +119,7 @@ class RefinedExport:
     def finish(self):
         if self.table is None:
             raise RuntimeError('--save_refined: no batch was refined, there is nothing to save')
-        flags_doc = {k: v for k, v in vars(args._get()).items() if isinstance(v, (bool, int, float, str, type(None)))}
+        flags_doc = {k: v for k, v in vars(args._get()).items() if isinstance(v, (bool, int, float, str, type(None))) and k != 'eval_accel'}
         self.table.finish(self.directory, {'flags': flags_doc, 'body_model': self.body_model, 'j_regressor_sha256_16': self.j_hash,
                                            'inner_iters': int(args.inner_iters), 'data': 'dataset' if args.data_root else 'synthetic'})
 
@@ -329,9 +329,11 @@ def smooth(directory: str, paths, sigma: float = 2.0, radius: Optional[int] = No
     return out
 
 
-def _rescore_fn(gt_j3d_mm: torch.Tensor, device, tag: str = 'smooth'):
+def _rescore_fn(gt_j3d_mm: torch.Tensor, device, tag: str = 'smooth', accel_paths=None):
     """the joint error of the raw and the smoothed (`tag`: the suffix of the second pair of names) rows through the EXISTING operators -- SMPL, find_joints, jrr_evaluate_joints -- in
-    chunks of --batch_size under ONE regressor (--eval_j_regressor, else the initial one), the body as the driver resolves it"""
+    chunks of --batch_size under ONE regressor (--eval_j_regressor, else the initial one), the body as the driver resolves it.
+    `accel_paths` (the split's frame paths, under --eval_accel): the joints of both passes are kept in device tables at their
+    dataset indices, and jrr_accel_error gives accel_err_mm_raw / accel_err_mm_<tag> along the runs of the table's refined rows."""
     from . import checkpoint, engine as _engine, smpl_model, utils
     from .smpl import SMPL
 
@@ -345,6 +347,7 @@ def _rescore_fn(gt_j3d_mm: torch.Tensor, device, tag: str = 'smooth'):
         rows = np.nonzero(raw['has_refined'])[0]
         N, bs = raw['has_refined'].shape[0], max(1, int(args.batch_size))
         acc = torch.full((4, N), float('nan'), device=device)
+        kept = torch.zeros((3, N, 17, 3), device=device) if accel_paths is not None else None        # raw | processed | ground truth
         engines: Dict[int, object] = {}
         with torch.no_grad():
             for a in range(0, rows.size, bs):
@@ -355,6 +358,8 @@ def _rescore_fn(gt_j3d_mm: torch.Tensor, device, tag: str = 'smooth'):
                     engines[B].set_j_regressor(J, mask)
                 gt = utils.move_pelvis(gt_j3d_mm[idx].to(device).float())
                 d_idx = idx.to(device)
+                if kept is not None:
+                    kept[2, d_idx] = gt
                 for k, arrays in enumerate((raw, smoothed)):
                     x6d = torch.from_numpy(arrays['pose6d'][rows[a:a + bs]]).to(device).float().contiguous()
                     betas = torch.from_numpy(arrays['shape'][rows[a:a + bs]]).to(device).float().contiguous()
@@ -362,10 +367,17 @@ def _rescore_fn(gt_j3d_mm: torch.Tensor, device, tag: str = 'smooth'):
                     err_j, err_pa_j = _engine.evaluate_joints(joints.float().contiguous(), gt.contiguous())
                     acc[2 * k, d_idx] = err_j.mean(1) * 1000
                     acc[2 * k + 1, d_idx] = err_pa_j.mean(1) * 1000
+                    if kept is not None:
+                        kept[k, d_idx] = joints.float()
         host = acc.cpu().numpy()
         names = ('mpjpe_eval_mm_raw', 'pampjpe_eval_mm_raw', 'mpjpe_eval_mm_' + tag, 'pampjpe_eval_mm_' + tag)
         more = {name: host[k] for k, name in enumerate(names)}
         numbers = {name + '_mean': _nanmean(host[k]) for k, name in enumerate(names)}
+        if kept is not None:
+            from . import accel_report
+            for name, values in zip(('accel_err_mm_raw', 'accel_err_mm_' + tag),
+                                    accel_report.per_sample_mm((kept[0], kept[1]), kept[2], accel_paths, raw['has_refined'])):
+                more[name], numbers[name + '_mean'] = values, _nanmean(values)
         numbers['eval_j_regressor'] = args.eval_j_regressor or args.j_regressor_init
         return more, numbers
     return rescore
@@ -391,13 +403,14 @@ def smooth_command(log=print) -> Optional[dict]:
     device = torch.device(args.device)
     torch.cuda.set_device(device)
     out = smooth(args.smooth_refined, paths, sigma=args.smooth_sigma, radius=args.smooth_radius, device=device,
-                 rescore=_rescore_fn(ds.gt_j3d, device))
+                 rescore=_rescore_fn(ds.gt_j3d, device, accel_paths=paths if args.eval_accel else None))
     doc = out['meta']['smooth']
     fmt = lambda v, spec='.4f': '-' if v is None else format(v, spec)
+    accel = f', accel error {fmt(doc["accel_err_mm_raw_mean"])} -> {fmt(doc["accel_err_mm_smooth_mean"])} mm/frame^2' if args.eval_accel else ''
     log(f'smoothed {doc["positions"]} poses in {doc["runs"]} runs (sigma {doc["sigma"]:g}, radius {doc["radius"]}): jitter '
         f'{fmt(doc["jitter_deg_raw_mean"])} -> {fmt(doc["jitter_deg_mean"])} deg/frame^2, moved {fmt(doc["smooth_delta_deg_mean"])} deg, MPJPE '
         f'{fmt(doc["mpjpe_eval_mm_raw_mean"])} -> {fmt(doc["mpjpe_eval_mm_smooth_mean"])}, PAMPJPE {fmt(doc["pampjpe_eval_mm_raw_mean"])} -> '
-        f'{fmt(doc["pampjpe_eval_mm_smooth_mean"])}; {os.path.join(args.smooth_refined, SMOOTH_NAME)}')
+        f'{fmt(doc["pampjpe_eval_mm_smooth_mean"])}{accel}; {os.path.join(args.smooth_refined, SMOOTH_NAME)}')
     return out
 
 
@@ -604,13 +617,14 @@ def fuse_command(log=print) -> Optional[dict]:
         raise ValueError(f'--fuse_refined: the table holds {n_table} samples, the split {len(ds)} with {len(paths)} frame paths')
     device = torch.device(args.device)
     torch.cuda.set_device(device)
-    out = fuse_views(args.fuse_refined, paths, max_deg=args.fuse_max_deg, device=device, rescore=_rescore_fn(ds.gt_j3d, device, tag='fused'))
+    out = fuse_views(args.fuse_refined, paths, max_deg=args.fuse_max_deg, device=device, rescore=_rescore_fn(ds.gt_j3d, device, tag='fused', accel_paths=paths if args.eval_accel else None))
     doc = out['meta']['fuse']
     fmt = lambda v, spec='.4f': '-' if v is None else format(v, spec)
+    accel = f', accel error {fmt(doc["accel_err_mm_raw_mean"])} -> {fmt(doc["accel_err_mm_fused_mean"])} mm/frame^2' if args.eval_accel else ''
     directory = (os.path.dirname(args.fuse_refined) or '.') if str(args.fuse_refined).endswith('.npz') else args.fuse_refined
     log(f'fused {doc["positions"]} poses in {doc["groups"]} groups over {len(doc["pairs"])} cameras (max {doc["max_deg"]:g} deg, '
         f'{doc["duplicates"]} duplicates): body moved {fmt(doc["fuse_delta_body_deg_mean"])} deg, orientation '
         f'{fmt(doc["fuse_delta_orient_deg_mean"])} deg, dropped {fmt(doc["dropped_share"])}, MPJPE {fmt(doc["mpjpe_eval_mm_raw_mean"])} -> '
-        f'{fmt(doc["mpjpe_eval_mm_fused_mean"])}, PAMPJPE {fmt(doc["pampjpe_eval_mm_raw_mean"])} -> {fmt(doc["pampjpe_eval_mm_fused_mean"])}; '
+        f'{fmt(doc["mpjpe_eval_mm_fused_mean"])}, PAMPJPE {fmt(doc["pampjpe_eval_mm_raw_mean"])} -> {fmt(doc["pampjpe_eval_mm_fused_mean"])}{accel}; '
         f'{os.path.join(directory, FUSE_NAME)}')
     return out

@@ -13,11 +13,12 @@ not depend on the regressor); `evaluate` is the on-device Procrustes kernel (k_e
 """
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import torch
 
-from . import batches, checkpoint, engine as _engine, eval_report, regressor_report, smpl_model, utils
+from . import accel_report, batches, checkpoint, engine as _engine, eval_report, regressor_report, smpl_model, utils
 from .args import args
 from .smpl import SMPL
 
@@ -43,6 +44,19 @@ def _groups():
     return eval_report.assign_groups(paths, args.eval_groups)
 
 
+def _accel_paths():
+    """the whole split's frame paths `--eval_accel` orders the samples by; ValueError naming what is missing"""
+    accel_report.check_flags(args._get())
+    if not args.data_root:
+        raise ValueError('--eval_accel needs --data_root (a dataset whose images.pkl holds the frame paths: they say which samples follow each other)')
+    from . import data as jdata
+    location = jdata.split_location('validation', args.data_root)
+    paths = jdata.split_image_paths(location)
+    if paths is None:
+        raise ValueError(f'--eval_accel: {os.path.join(location, "images.pkl")} is missing: the frame paths say which samples follow each other')
+    return paths
+
+
 def _batch_groups(batch, group_ids, B: int, device) -> torch.Tensor:
     """the batch's group ids on the device; samples the batch marks `valid == 0` get -1 (not scored)"""
     gid = torch.zeros(B, dtype=torch.int32)
@@ -54,6 +68,7 @@ def _batch_groups(batch, group_ids, B: int, device) -> torch.Tensor:
 
 
 def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> Dict[str, float]:
+    accel_paths = _accel_paths() if args.eval_accel else None                                            # refuses before any launch
     device = torch.device(args.device)
     torch.cuda.set_device(device)
     smpl = SMPL(args.smpl_dir, batch_size=1, allow_synthetic=args.synthetic or args.smpl_dir == 'SPIN/data/smpl').to(device)   # :40-43
@@ -64,7 +79,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     J_regressor_initial = torch.from_numpy(J_np).float().to(device)                                      # :48-49
     j_reg_mask = utils.find_j_reg_mask(J_regressor_initial)                                              # :51-53
 
-    source = validation_batches(smpl.model_np, J_np, device, with_index=bool(args.eval_report or args.regressor_report))
+    source = validation_batches(smpl.model_np, J_np, device, with_index=bool(args.eval_report or args.regressor_report or args.eval_accel))
     reports, group_ids = None, None
     shift = None
     if args.regressor_report:  # what the retrained regressor did to each joint: one more launch per batch, the vertices of its forward kept
@@ -73,6 +88,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     if args.eval_report:       # per group / per joint / PCK next to the four printed means: two more launches per evaluate, no read-back
         names, group_ids = _groups()
         reports = {'before': eval_report.EvalReport(names, device), 'after': eval_report.EvalReport(names, device)}
+    track = accel_report.JointTrack(len(accel_paths), 2, device) if accel_paths is not None else None
 
     mpjpe_before, pampjpe_before, mpjpe_after, pampjpe_after = [], [], [], []
     engines: Dict[int, _engine.RefineEngine] = {}
@@ -93,6 +109,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
             else:
                 joints = eng.find_joints_forward(betas, x6d=x6d)                                         # :107-108
             mb, pb = utils.evaluate(joints, gt)                                                         # :110-111
+            joints_before = joints
             if reports is not None or shift is not None:
                 gid = _batch_groups(batch, group_ids, B, device)
             if reports is not None:
@@ -103,6 +120,8 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
             mpjpe_before.append(mb); pampjpe_before.append(pb); mpjpe_after.append(ma); pampjpe_after.append(pa)
             if reports is not None:
                 reports['after'].add(joints, gt, gid)
+            if track is not None:
+                track.add(batch['index'], (joints_before, joints), gt, batch.get('valid'))
             if shift is not None:
                 shift.add(verts, joints_initial, joints, gt, gid, None if 'valid' not in batch else batch['valid'].cpu().bool().numpy())
     if not mpjpe_before:
@@ -114,8 +133,11 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     if reports is not None:    # this function runs in ONE process (main.py: rank 0) on whole batches: nothing to reduce
         results = {k: r.finish(reduce=False) for k, r in reports.items()}
         rep['eval_report'] = eval_report.write(args.eval_report, results, names, args.eval_groups if group_ids is not None else 'none', 'parameters',
-                                               dict(vars(args._get())), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
+                                               accel_report.flags_doc(args._get()), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
                                                (path, eval_report.sha16(path)))
+    if track is not None:      # one launch per regressor over the whole split's time order, one read-back
+        rep['accel_report'] = accel_report.write(args.eval_report, track.finish(accel_paths, group_ids, names, ('before', 'after'), reduce=False),
+                                                 args.eval_groups, 'parameters')
     if shift is not None:
         rep['regressor_report'] = shift.finish((args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
                                                (path, eval_report.sha16(path)), smpl.model_np, smpl.device_model, reduce=False)
@@ -129,6 +151,8 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     log(f"{rep['mpjpe_after']:.4f}")
     log('PAMPJPE')
     log(f"{rep['pampjpe_after']:.4f}")
+    if track is not None:
+        log(accel_report.summary_line(rep['accel_report']))
     return rep
 
 

@@ -7,7 +7,8 @@ main.py:26-27) need the external VIBE / MEVA checkouts: the networks are out of 
 networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evaluate_vertices), which runs alone and exits.
 `--regressor_report DIR` (regressor_report.py) adds to either evaluation what the retrained regressor did to each joint, with pictures.
 `--smooth_refined DIR` (refined.smooth_command) filters a `--save_refined` table along time and exits as well;
-`--fuse_refined DIR` (refined.fuse_command) fuses its camera views of each frame and exits."""
+`--fuse_refined DIR` (refined.fuse_command) fuses its camera views of each frame and exits.
+`--eval_accel` (accel_report.py) adds the acceleration error along each video sequence to the evaluations and to those two commands."""
 import importlib
 import os
 import sys
@@ -30,6 +31,7 @@ if __name__ == '__main__':
             print('wandb is not installed; logging to stdout')
     utils.set_seed(0)
     importlib.import_module(PKG + '.regressor_report').check_flags(args._get())   # --regressor_report: refused before anything runs
+    importlib.import_module(PKG + '.accel_report').check_flags(args._get())       # --eval_accel: likewise
     if args.eval_vertices:                                                   # scripts/test.py:141-301 on the meshes of a directory
         importlib.import_module(PKG + '.eval_report').evaluate_vertices()
         import torch.distributed as dist
