@@ -854,6 +854,63 @@ int jrr_engine_profile_read(jrr_engine_t* e, float* ms_host, int32_t* counts_hos
  * the occupancy formula, which prices every instruction at out[3] = 64 clocks, reads ~5 % high for it.)               */
 int jrr_engine_probe_read(jrr_engine_t* e, int64_t* out_host);
 
+/* The regressor fit (`--fit_regressor`): Adam steps of the J_regressor on a table of FIXED meshes, scripts/optimize.py:300-312 with
+ * the SMPL forward taken out of the loop.  ReLU' zeroes the gradient outside the positive entries of J*mask, and an entry whose
+ * gradient is always zero keeps m = v = 0 under torch.optim.Adam and never moves: a step needs, per sample, the vertices of those
+ * entries and the ground truth.  No engine, no body model.
+ *
+ * STATE (state_dev: caller-owned, 16-byte aligned, jrr_jfit_state_bytes bytes; opaque).  jrr_jfit_prepare builds it from J_init_dev
+ * (17,6890) raw and mask_dev (17,6890) or NULL:
+ *   cols[NS]   the union of the columns where J_init*mask > 0 in any row, ascending vertex index, 1 <= NS <= 17 * 128;
+ *   per row i  the list of its positive entries in ascending vertex order, at most JRR_JFIT_ROW_CAP = 128 of them: each entry's
+ *              position in cols, its raw value, its mask value, Adam's m = v = 0; the Adam step counter 0.
+ * A row with more than 128 positive entries, or no positive entry in any row: JRR_ERR_ARG.  A row without a positive entry is
+ * accepted: it has no parameters and stays as it is; jrr_jfit_joints gives NaN for its joint (the reference's 0/0), and jrr_jfit_run
+ * leaves that joint out of the loss and of the adjoint (the mean still divides by count * 17 * 3; an empty PELVIS row centres the
+ * other joints on the origin) instead of letting the NaN reach every other row through the centring.  The call synchronises the
+ * stream and fills info_host[JRR_JFIT_INFO] (nullable): {NS, listed entries, Adam steps taken, 0, entries of row 0 .. 16}.
+ * jrr_jfit_info reads the same words of a prepared state back (synchronises).
+ *
+ * CACHE (cache_dev: caller-owned, 16-byte aligned, jrr_jfit_cache_bytes(n_rows, ns) bytes).  Sample-major rows of
+ *   RL = (3 ns + 51) | 1 floats:  [0, 3 ns) the support vertices, x y z of cols[0], cols[1], ...;  [3 ns, 3 ns + 51) the ground truth
+ *   (17,3), pelvis-centred, in mm;  one float of padding (zero) when 3 ns + 51 is even.
+ * Row r starts at float r * RL: a minibatch of consecutive rows is ONE contiguous run of bytes, which the step kernel streams into
+ * LDS with coalesced loads, and a row permutation is an index copy of a (n_rows, RL) fp32 array (the odd stride keeps the samples of
+ * a workgroup on different LDS banks).  `ns` of every call must be the prepared NS: a mismatch found on the device sets the error
+ * word of the state (the one thing gather and joints write there: their state pointer is not const) that the next jrr_jfit_info
+ * reports as JRR_ERR_ARG, and the launch writes nothing but NaN losses / NaN joints.
+ *
+ * jrr_jfit_gather  verts_dev (batch,6890,3), gt_mm_dev (batch,17,3) -> cache rows [row0, row0 + batch).
+ * jrr_jfit_joints  joints_dev (count,17,3) of cache rows [begin, begin + count) under the CURRENT entries: x = relu(raw * mask),
+ *                  Jn = x / rowsum(x), joints = Jn @ verts; NOT pelvis-centred; each sum in double, in list order, one rounding.
+ * jrr_jfit_run     n_steps consecutive Adam steps, all enqueued without a host synchronisation; step k uses cache rows
+ *                  [(first + k) * batch, min((first + k + 1) * batch, n_rows)); 0 <= first, first + n_steps <= ceil(n_rows / batch)
+ *                  (else JRR_ERR_ARG; n_steps = 0 does nothing).  One step: joints as above, minus joint 0;
+ *                  loss = mean over count * 17 * 3 of (joints - gt / 1000)^2 -> loss_dev[k] (the loss BEFORE the update); backward
+ *                  through the centring (joint 0 receives minus the sum of all joint adjoints) and the normalisation,
+ *                  mask * relu'(raw * mask) * (dJn - sum(dJn * Jn)) / rowsum; torch.optim.Adam(lr) on EVERY listed entry (one that has
+ *                  gone non-positive coasts on its moments).  A short last minibatch divides by its own count.  grad_dev (nullable)
+ *                  [17][128] receives the gradient of the LAST step with respect to the raw entries, entry e of row i at
+ *                  i * 128 + e, zeros behind a row's count.  ONE launch per step: workgroup w of min(ceil(count / JRR_JFIT_SPW),
+ *                  JRR_JFIT_MAX_WG) sums the samples of its 32-sample chunks w, w + grid, ... in double into a slab of the state;
+ *                  the workgroup that arrives last (integer atomic counter) adds the slabs in workgroup order and updates.  No
+ *                  floating-point atomics: results are bitwise reproducible.
+ * jrr_jfit_scatter the listed entries' raw values, m and v into dense (17,6890) arrays (each nullable); other elements are not
+ *                  written: the caller fills them with J_init and zeros.                                                      */
+enum { JRR_JFIT_ROW_CAP = 128, JRR_JFIT_SPW = 32, JRR_JFIT_MAX_WG = 256, JRR_JFIT_INFO = 24 };
+size_t jrr_jfit_state_bytes(void);
+size_t jrr_jfit_cache_bytes(int64_t n_rows, int ns);
+int jrr_jfit_prepare(const float* J_init_dev, const float* mask_dev, void* state_dev, size_t state_bytes, int32_t* info_host,
+                     void* stream);
+int jrr_jfit_info(const void* state_dev, int32_t* info_host, void* stream);
+int jrr_jfit_gather(void* state_dev, const float* verts_dev, const float* gt_mm_dev, int batch, void* cache_dev, int64_t n_rows,
+                    int64_t row0, int ns, void* stream);
+int jrr_jfit_joints(void* state_dev, const void* cache_dev, int64_t n_rows, int64_t begin, int count, int ns, float* joints_dev,
+                    void* stream);
+int jrr_jfit_run(void* state_dev, const void* cache_dev, int64_t n_rows, int ns, int batch, int64_t first, int n_steps, float lr,
+                 float* loss_dev, float* grad_dev, void* stream);
+int jrr_jfit_scatter(const void* state_dev, float* J_dev, float* m_dev, float* v_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -105,6 +105,14 @@ SIGNATURES = {
     'jrr_engine_set_profiling': (c_int, [_P, c_int]),
     'jrr_engine_profile_read': (c_int, [_P, POINTER(c_float), POINTER(c_int32)]),
     'jrr_engine_probe_read': (c_int, [_P, POINTER(ctypes.c_int64)]),
+    'jrr_jfit_state_bytes': (c_size_t, []),
+    'jrr_jfit_cache_bytes': (c_size_t, [ctypes.c_int64, c_int]),
+    'jrr_jfit_prepare': (c_int, [_P, _P, _P, c_size_t, POINTER(c_int32), _P]),
+    'jrr_jfit_info': (c_int, [_P, POINTER(c_int32), _P]),
+    'jrr_jfit_gather': (c_int, [_P, _P, _P, c_int, _P, ctypes.c_int64, ctypes.c_int64, c_int, _P]),
+    'jrr_jfit_joints': (c_int, [_P, _P, ctypes.c_int64, ctypes.c_int64, c_int, c_int, _P, _P]),
+    'jrr_jfit_run': (c_int, [_P, _P, ctypes.c_int64, c_int, c_int, ctypes.c_int64, c_int, c_float, _P, _P, _P]),
+    'jrr_jfit_scatter': (c_int, [_P, _P, _P, _P, _P]),
 }
 
 _lib = None

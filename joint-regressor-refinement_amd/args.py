@@ -81,6 +81,18 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--smooth_sigma', type=float, default=2.0, help='--smooth_refined: standard deviation of the Gaussian, in sampled frames')
     parser.add_argument('--smooth_radius', type=int, default=None,
                         help='--smooth_refined: the window reaches this many frames to either side, 0 .. 16 (default: min(16, ceil(3 sigma)))')
+    parser.add_argument('--fit_regressor', type=str, default=None, metavar='OUT',
+                        help='with --fit_from: fit the J_regressor on a table of fixed meshes -- Adam steps (--j_reg_lr, minibatches of '
+                             '--batch_size) over the support vertices of --j_regressor_init alone, no SMPL forward in the loop -- write '
+                             'OUT/retrained_J_Regressor.pt (or --save_j_regressor) and OUT/fit.json, print one line and exit (regressor_fit.py)')
+    parser.add_argument('--fit_from', type=str, default=None, metavar='PATH',
+                        help='--fit_regressor: a --save_refined directory or a named .npz of it (refined_smooth.npz, refined_fused.npz; '
+                             'needs --data_root for the ground truth), or a directory in the --eval_vertices format (no body model is read)')
+    parser.add_argument('--fit_epochs', type=int, default=10, help='--fit_regressor: passes over the training rows')
+    parser.add_argument('--fit_shuffle', action='store_true', help='--fit_regressor: permute the training rows between epochs (seeded by --seed)')
+    parser.add_argument('--fit_holdout', type=float, default=0.1,
+                        help='--fit_regressor: fraction F kept out of training and scored beside it: every round(1/F)-th sequence of the '
+                             'frame paths in sorted order, without paths the last F of the rows; 0: train on everything')
     parser.add_argument('--eval_report', type=str, default=None, metavar='DIR',
                         help='evaluation report: DIR/eval.json and DIR/eval.md with MPJPE / PA-MPJPE per group and per joint, PCK and AUC, '
                              'initial against retrained regressor (eval_report.py); the printed lines of scripts/test.py:125-138 stay as they are')

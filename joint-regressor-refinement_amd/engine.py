@@ -721,6 +721,84 @@ class JointRegressorTable:
         return joints
 
 
+JFIT_ROW_CAP, JFIT_SPW, JFIT_MAX_WG, JFIT_INFO = 128, 32, 256, 24      # include/jrr.h: JRR_JFIT_*
+
+
+class RegressorFit:
+    """jrr_jfit_*: Adam steps of the J_regressor on a cache of fixed meshes (include/jrr.h).  The object owns the device state
+    (support lists, raw entries, Adam moments, step counter) prepared from J_init (17,6890) and mask (17,6890) or None, and a cache of
+    `n_rows` samples: `gather` fills rows of it from (B,6890,3) vertices and (B,17,3) pelvis-centred ground truth in mm, `run` enqueues
+    Adam steps over consecutive minibatches, `joints` is the forward half, `dense` brings J, m and v back as (17,6890) tensors.  No
+    engine, no body model."""
+
+    def __init__(self, J_init: torch.Tensor, mask: Optional[torch.Tensor], n_rows: int):
+        self.lib = _lib.load()
+        J_init = J_init.detach().float().contiguous()
+        assert J_init.shape == (NUM_H36M, NUM_VERTS) and J_init.is_cuda, tuple(J_init.shape)
+        self.device, self.J_init = J_init.device, J_init
+        if mask is not None:
+            mask = mask.detach().float().contiguous()
+            assert mask.shape == (NUM_H36M, NUM_VERTS) and mask.device == self.device
+        self.mask = mask
+        nbytes = int(self.lib.jrr_jfit_state_bytes())
+        self.state = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=self.device)
+        info = (c_int32 * JFIT_INFO)()
+        check(self.lib.jrr_jfit_prepare(ptr(J_init), ptr(mask), ptr(self.state), self.state.numel() * 8, info, stream_ptr(self.device)),
+              'jfit_prepare')
+        self.ns, self.entries, self.counts = int(info[0]), int(info[1]), [int(info[4 + i]) for i in range(NUM_H36M)]
+        self.n_rows = int(n_rows)
+        self.row_floats = (3 * self.ns + 3 * NUM_H36M) | 1
+        assert int(self.lib.jrr_jfit_cache_bytes(self.n_rows, self.ns)) == self.n_rows * self.row_floats * 4
+        self.cache = torch.zeros((max(self.n_rows, 1), self.row_floats), dtype=torch.float32, device=self.device)
+
+    def info(self):
+        """(NS, listed entries, Adam steps taken, entries per row); SYNCHRONOUS; raises when a call passed a foreign ns"""
+        info = (c_int32 * JFIT_INFO)()
+        check(self.lib.jrr_jfit_info(ptr(self.state), info, stream_ptr(self.device)), 'jfit_info')
+        return int(info[0]), int(info[1]), int(info[2]), [int(info[4 + i]) for i in range(NUM_H36M)]
+
+    def gather(self, verts: torch.Tensor, gt_centred_mm: torch.Tensor, row0: int) -> None:
+        B = int(verts.shape[0])
+        verts, gt = verts.contiguous(), gt_centred_mm.contiguous()
+        assert verts.shape == (B, NUM_VERTS, 3) and gt.shape == (B, NUM_H36M, 3) and verts.dtype == gt.dtype == torch.float32
+        assert verts.device == self.device and gt.device == self.device
+        check(self.lib.jrr_jfit_gather(ptr(self.state), ptr(verts), ptr(gt), B, ptr(self.cache), self.n_rows, int(row0), self.ns,
+                                       stream_ptr(self.device)), 'jfit_gather')
+
+    def joints(self, begin: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        count = self.n_rows - int(begin) if count is None else int(count)
+        out = torch.empty(count, NUM_H36M, 3, device=self.device)
+        check(self.lib.jrr_jfit_joints(ptr(self.state), ptr(self.cache), self.n_rows, int(begin), count, self.ns, ptr(out),
+                                       stream_ptr(self.device)), 'jfit_joints')
+        return out
+
+    def ground_truth_mm(self, begin: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """the pelvis-centred ground truth (count,17,3) mm of cache rows [begin, begin + count)"""
+        count = self.n_rows - int(begin) if count is None else int(count)
+        return self.cache[begin:begin + count, 3 * self.ns:3 * self.ns + 3 * NUM_H36M].reshape(count, NUM_H36M, 3).contiguous()
+
+    def run(self, batch: int, first: int, n_steps: int, lr: float, loss: Optional[torch.Tensor] = None, grad: Optional[torch.Tensor] = None,
+            n_rows: Optional[int] = None) -> torch.Tensor:
+        """n_steps Adam steps over minibatches first .. first + n_steps - 1 of the first `n_rows` cache rows (default: all); returns the
+        device tensor of the steps' losses.  Nothing is read back."""
+        n_rows = self.n_rows if n_rows is None else int(n_rows)
+        assert 0 <= n_rows <= self.n_rows
+        if loss is None:
+            loss = torch.empty(max(int(n_steps), 1), device=self.device)
+        assert loss.dtype == torch.float32 and loss.is_contiguous() and loss.numel() >= n_steps and loss.device == self.device
+        if grad is not None:
+            assert grad.shape == (NUM_H36M, JFIT_ROW_CAP) and grad.dtype == torch.float32 and grad.is_contiguous() and grad.device == self.device
+        check(self.lib.jrr_jfit_run(ptr(self.state), ptr(self.cache), n_rows, self.ns, int(batch), int(first), int(n_steps), float(lr),
+                                    ptr(loss), ptr(grad), stream_ptr(self.device)), 'jfit_run')
+        return loss
+
+    def dense(self):
+        """(J, m, v): (17,6890) each -- the listed entries' current values over J_init and zeros"""
+        J, m, v = self.J_init.clone(), torch.zeros_like(self.J_init), torch.zeros_like(self.J_init)
+        check(self.lib.jrr_jfit_scatter(ptr(self.state), ptr(J), ptr(m), ptr(v), stream_ptr(self.device)), 'jfit_scatter')
+        return J, m, v
+
+
 EVAL_ACC_ROW, EVAL_ACC_TRAILER = 338, 2         # include/jrr.h: JRR_EVAL_ACC_ROW, JRR_EVAL_ACC_TRAILER
 
 

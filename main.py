@@ -8,6 +8,7 @@ networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evalu
 `--regressor_report DIR` (regressor_report.py) adds to either evaluation what the retrained regressor did to each joint, with pictures.
 `--smooth_refined DIR` (refined.smooth_command) filters a `--save_refined` table along time and exits as well;
 `--fuse_refined DIR` (refined.fuse_command) fuses its camera views of each frame and exits.
+`--fit_regressor OUT --fit_from PATH` (regressor_fit.py) fits the regressor on a table of fixed meshes and exits.
 `--eval_accel` (accel_report.py) adds the acceleration error along each video sequence to the evaluations and to those two commands."""
 import importlib
 import os
@@ -32,6 +33,10 @@ if __name__ == '__main__':
     utils.set_seed(0)
     importlib.import_module(PKG + '.regressor_report').check_flags(args._get())   # --regressor_report: refused before anything runs
     importlib.import_module(PKG + '.accel_report').check_flags(args._get())       # --eval_accel: likewise
+    importlib.import_module(PKG + '.regressor_fit').check_flags(args._get())      # --fit_regressor: likewise
+    if args.fit_regressor:                                                   # Adam steps of the regressor on fixed meshes; no inner loop
+        importlib.import_module(PKG + '.regressor_fit').fit_command()
+        sys.exit(0)
     if args.eval_vertices:                                                   # scripts/test.py:141-301 on the meshes of a directory
         importlib.import_module(PKG + '.eval_report').evaluate_vertices()
         import torch.distributed as dist
