@@ -911,6 +911,42 @@ int jrr_jfit_run(void* state_dev, const void* cache_dev, int64_t n_rows, int ns,
                  float* loss_dev, float* grad_dev, void* stream);
 int jrr_jfit_scatter(const void* state_dev, float* J_dev, float* m_dev, float* v_dev, void* stream);
 
+/* The exact solve of the regressor fit (`--fit_solve`): with the meshes fixed, the loss of jrr_jfit_run is a convex quadratic in the
+ * normalised weights, and its data enter only through the second moments of the cache rows.  Two entry points on the state and the
+ * cache above; the solver itself runs on the host (regressor_solve.py).
+ *
+ * MOMENTS.  A cache row is W = ns + 17 points of 3 floats: the ns support vertices (m), then the 17 pelvis-centred ground-truth
+ * joints (mm).  For cache rows [begin, begin + count)
+ *     M[w][w'] = sum over the rows and the axes c < 3 of row[3 w + c] * row[3 w' + c]            (W x W doubles, row-major, symmetric)
+ * with the blocks G = M[:ns,:ns] (m^2), C = M[ns:,:ns] (mm m) and the diagonal of M[ns:,ns:] (mm^2: its sum is sum gt^2).  Every
+ * product of two fp32 values is formed exactly in fp64 and summed in fp64 (v_mfma_f64_16x16x4_f64; an fp32 Gram would round G by
+ * more than the optimality gap the solve certifies: the loss is about 1e-4 of the scale of G).  The rows are cut into equal chunks of
+ * at most JRR_JFIT_MOM_CHUNK rows, or longer ones where that would take more than JRR_JFIT_MOM_MAX_CHUNKS (fewer for a wide support: the chunks' partial sums, one
+ * slab of doubles each, must fit the scratch); a second launch adds the slabs in a fixed order (four consecutive quarters of the
+ * chunks, each in chunk order, then the quarters) and writes both triangles of M from the same sum.  No floating-point atomics: two calls give the same bits and M equals its transpose bitwise.
+ *
+ * jrr_jfit_moments_bytes  the bytes of M (W * W * 8) for this ns; *scratch_bytes (nullable) receives the bytes of the caller-owned
+ *                  scratch, a function of ns alone.  ns outside 1 .. 2176: both 0.
+ * jrr_jfit_moments  M_dev (8-byte aligned, jrr_jfit_moments_bytes bytes) of cache rows [begin, begin + count); count == 0 zeroes M.
+ *                  scratch_dev: 8-byte aligned, scratch_bytes of it; nothing is kept there between calls.  NULL pointers,
+ *                  misalignment, a range outside [0, n_rows] or an ns outside 1 .. 2176: JRR_ERR_ARG; a scratch below
+ *                  jrr_jfit_moments_bytes: JRR_ERR_WORKSPACE.  An ns that is not the prepared NS is found on the device: the error
+ *                  word of the state is set as by gather / joints (the next jrr_jfit_info reports it) and M is filled with NaN.
+ *                  Enqueued on the stream, nothing is read back.
+ * jrr_jfit_set_entries  loads the raw value of every LISTED entry from the dense J_dev (17,6890); zeros and negative values are
+ *                  allowed and elements outside the lists are not read.  Adam's m and v of every entry and the step counter are
+ *                  reset to 0, and the normalised weights and row sums are recomputed as a step leaves them (relu(raw * mask) over
+ *                  its row sum, the sum in double).  A listed row whose relu(raw * mask) sums to 0 (or is not finite) sets the
+ *                  error word, which the next jrr_jfit_info reports as JRR_ERR_ARG until a later jrr_jfit_set_entries leaves no
+ *                  such row; its weights are NaN.  It is how the solved weights reach jrr_jfit_joints / jrr_evaluate, and how a
+ *                  state prepared from a pattern of candidate entries (ones on the pattern) receives the true initial values: a
+ *                  listed entry at zero has relu' = 0 and does not move under jrr_jfit_run.                                      */
+enum { JRR_JFIT_MOM_CHUNK = 64, JRR_JFIT_MOM_MAX_CHUNKS = 1024 };
+size_t jrr_jfit_moments_bytes(int ns, size_t* scratch_bytes);
+int jrr_jfit_moments(void* state_dev, const void* cache_dev, int64_t n_rows, int64_t begin, int64_t count, int ns, double* M_dev,
+                     void* scratch_dev, size_t scratch_bytes, void* stream);
+int jrr_jfit_set_entries(void* state_dev, const float* J_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,20 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--fit_holdout', type=float, default=0.1,
                         help='--fit_regressor: fraction F kept out of training and scored beside it: every round(1/F)-th sequence of the '
                              'frame paths in sorted order, without paths the last F of the rows; 0: train on everything')
+    parser.add_argument('--fit_solve', action='store_true',
+                        help='--fit_regressor: instead of Adam epochs, solve the fit exactly -- with the meshes fixed the loss is a convex '
+                             'quadratic in the normalised weights, each row on the simplex over its listed entries; one fp64 pass over the '
+                             'table gives its moments (jrr_jfit_moments) and a projected Newton method the minimiser, with the Frank-Wolfe '
+                             'gap as the certificate 0 <= loss - optimum <= gap.  Writes OUT/solve.json (not fit.json) and the checkpoint; the '
+                             'normalised weights become the raw values (regressor_solve.py)')
+    parser.add_argument('--fit_rings', type=int, default=0, metavar='K',
+                        help='--fit_solve: let each row\'s support grow over the mesh -- every vertex within K edges of one of its positive '
+                             'entries is a candidate (at most 128 per row), which Adam cannot do (relu\'(0) = 0); needs the faces of the '
+                             'body model: --smpl_dir or --synthetic')
+    parser.add_argument('--fit_solve_tol', type=float, default=1e-6,
+                        help='--fit_solve: stop when the Frank-Wolfe gap is at most this fraction of the initial loss')
+    parser.add_argument('--fit_solve_iters', type=int, default=1000,
+                        help='--fit_solve: most Newton steps; solve.json says `converged: false` when they end the solve')
     parser.add_argument('--eval_report', type=str, default=None, metavar='DIR',
                         help='evaluation report: DIR/eval.json and DIR/eval.md with MPJPE / PA-MPJPE per group and per joint, PCK and AUC, '
                              'initial against retrained regressor (eval_report.py); the printed lines of scripts/test.py:125-138 stay as they are')

@@ -1,12 +1,10 @@
 // The regressor fit (`--fit_regressor`): Adam steps of the J_regressor on a table of fixed meshes (scripts/optimize.py:300-312 with the
 // SMPL forward taken out of the loop).  No engine, no body model; include/jrr.h (jrr_jfit_*) is the specification.
 //
-// State (one caller-owned buffer, JF_* word offsets below): the union cols[NS] of the positive columns of J_init*mask, and the listed
-// entries of all rows FLATTENED in row order -- entry idx of row i lives at off[i] <= idx < off[i + 1] -- with, per entry, its row and
-// its position in cols (one packed word), its vertex, raw value, mask value, Adam m / v and its current normalised weight.
-// Cache: sample-major rows of RL = (3 NS + 51) | 1 floats (support vertices | ground truth in mm | padding).
+// State and cache: jfitk.h.
 //
 // k_jfit_prepare  one workgroup: the union by an LDS flag per vertex and a scan, the rows' lists by ballots in ascending vertex order.
+// k_jfit_set_entries  one workgroup: the raw values of the listed entries from a dense array, Adam's moments and step counter to zero.
 // k_jfit_gather   one workgroup per sample: the NS vertices and the ground truth into the sample's cache row.
 // k_jfit_joints   one thread per (sample, joint): the forward half alone, sums in double.
 // k_jfit_step     ONE launch per Adam step.  A workgroup owns chunks of JF_SPW = 32 consecutive samples of the minibatch (chunk w,
@@ -23,55 +21,16 @@
 //   (k_jreg_bwd's formula) and torch's Adam (adam_scalars / adam_update) to every listed entry, and publishes the new raw values,
 //   moments, normalised weights, the step counter and the loss.  No floating-point atomics: a result is a function of the inputs
 //   and the minibatch size alone.
-#include "jrr_common.h"
-#include "kernels.h"
-#include "../../include/jrr.h"
+#include "jfitk.h"
 
 namespace jrr {
 
-constexpr int JF_CAP = NH * JSUP_CAP;                 // 2176: most listed entries, and most union columns
-constexpr int JF_THREADS = 256;
-constexpr int JF_SPW = JRR_JFIT_SPW;                  // samples per chunk
-constexpr int JF_MAX_WG = JRR_JFIT_MAX_WG;
 constexpr int JF_STAGE = 7680;                        // floats of staged cache rows: 32 rows of the shipped support (237 floats each)
 constexpr int JF_K = (JF_CAP + JF_THREADS - 1) / JF_THREADS;   // 9 entries per thread at most
-constexpr int JF_GT = NH * 3;                         // 51
 constexpr int JF_PREP_THREADS = 1024;
 
-static_assert(JSUP_CAP == JRR_JFIT_ROW_CAP, "row capacity");
 static_assert(JF_STAGE >= 3 * JF_CAP + JF_GT + 1, "one cache row of the widest support must fit the staging area");
 static_assert(JF_STAGE >= JF_CAP, "the last workgroup keeps dJn in the staging area");
-
-// header words (int32)
-enum { JF_H_NS = 0, JF_H_E = 1, JF_H_STEP = 2, JF_H_ERR = 3, JF_H_ARRIVE = 4, JF_H_CNT = 8, JF_H_OFF = 32, JF_H_RS = 52, JF_HEAD = 96 };
-// JF_H_RS: 17 floats, the rows' current sums of relu(raw * mask)
-
-struct JfState {
-  int* head; int* pk; int* vtx; int* cols;
-  float* raw; float* mk; float* m; float* v; float* jn;
-  double* lpart; double* slab;
-};
-static size_t jf_state_bytes() {
-  return (size_t)JF_HEAD * 4 + (size_t)8 * JF_CAP * 4 + (size_t)JF_MAX_WG * 8 + (size_t)JF_MAX_WG * JF_CAP * 8;
-}
-__host__ __device__ static inline JfState jf_carve(void* base) {
-  JfState s;
-  s.head = reinterpret_cast<int*>(base);
-  s.pk = s.head + JF_HEAD;
-  s.vtx = s.pk + JF_CAP;
-  s.cols = s.vtx + JF_CAP;
-  s.raw = reinterpret_cast<float*>(s.cols + JF_CAP);
-  s.mk = s.raw + JF_CAP;
-  s.m = s.mk + JF_CAP;
-  s.v = s.m + JF_CAP;
-  s.jn = s.v + JF_CAP;
-  s.lpart = reinterpret_cast<double*>(s.jn + JF_CAP);      // (96 + 8 * 2176) * 4 bytes: a multiple of 8
-  s.slab = s.lpart + JF_MAX_WG;
-  return s;
-}
-static_assert(((JF_HEAD + 8 * JF_CAP) * 4) % 8 == 0, "the doubles of the state are 8-byte aligned");
-
-__host__ __device__ static inline int jf_row_floats(int ns) { return (3 * ns + JF_GT) | 1; }
 
 // ---- prepare ----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(JF_PREP_THREADS) void k_jfit_prepare(const float* __restrict__ J, const float* __restrict__ mask, void* state) {
@@ -177,6 +136,55 @@ __global__ __launch_bounds__(JF_THREADS) void k_jfit_normalise(void* state) {
   for (int idx = blockIdx.x * JF_THREADS + threadIdx.x; idx < E; idx += gridDim.x * JF_THREADS) {
     const int i = st.pk[idx] >> 16;
     st.jn[idx] = fmaxf(st.raw[idx] * st.mk[idx], 0.f) / rs[i];
+  }
+}
+
+// ---- set_entries ------------------------------------------------------------------------------------------------------------------
+// one workgroup, a wave per row, two entries per lane: the raw value of every listed entry from the dense array (zeros allowed), Adam's
+// m = v = 0 and step 0, the rows' sums and the normalised weights as k_jfit_step's last workgroup leaves them
+__global__ __launch_bounds__(JF_THREADS) void k_jfit_set_entries(void* state, const float* __restrict__ J) {
+  __shared__ int s_bad;
+  const JfState st = jf_carve(state);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int E = st.head[JF_H_E];
+  if (E < 1 || E > JF_CAP) return;                    // not a prepared state: jrr_jfit_info reports it
+  if (tid == 0) s_bad = 0;
+  __syncthreads();
+  float* rowsum = reinterpret_cast<float*>(st.head) + JF_H_RS;
+  for (int i = wave; i < NH; i += JF_THREADS / 64) {
+    const int b = min(max(st.head[JF_H_OFF + i], 0), E), n = min(min(st.head[JF_H_OFF + i + 1], E) - b, JSUP_CAP);
+    if (n <= 0) continue;
+    float xn[2] = {0.f, 0.f};
+    double sum = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int e = lane + 64 * h;
+      if (e < n) {
+        const int idx = b + e;
+        const float raw = J[(size_t)i * V + min((unsigned)st.vtx[idx], (unsigned)(V - 1))];
+        st.raw[idx] = raw; st.m[idx] = 0.f; st.v[idx] = 0.f;
+        xn[h] = fmaxf(raw * st.mk[idx], 0.f);
+        sum += (double)xn[h];
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    const float rs = (float)sum;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int e = lane + 64 * h;
+      if (e < n) st.jn[b + e] = xn[h] / rs;           // (a row that sums to zero: NaN, the reference's 0/0, and the error word)
+    }
+    if (lane == 0) {
+      rowsum[i] = rs;
+      if (!(rs > 0.f)) s_bad = 1;                     // every writer stores the same value
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    st.head[JF_H_STEP] = 0;
+    st.head[JF_H_ARRIVE] = 0;
+    st.head[JF_H_ERR] = (st.head[JF_H_ERR] & ~JF_ERR_ROWSUM) | (s_bad ? JF_ERR_ROWSUM : 0);
   }
 }
 
@@ -505,19 +513,12 @@ extern "C" int jrr_jfit_info(const void* state, int32_t* info_host, void* stream
   const int rc = jf_read_info(state, info_host, (hipStream_t)stream, &err);
   if (rc != JRR_OK) return rc;
   if (err) {
-    jrr_set_error(err & 2 ? "jrr_jfit_info: a call passed an ns that is not the prepared one" : "jrr_jfit_info: the state is not a prepared one");
+    jrr_set_error(err & JF_ERR_NS       ? "jrr_jfit_info: a call passed an ns that is not the prepared one"
+                  : err & JF_ERR_ROWSUM ? "jrr_jfit_info: jrr_jfit_set_entries left a listed row without a positive entry"
+                                        : "jrr_jfit_info: the state is not a prepared one");
     return JRR_ERR_ARG;
   }
   return JRR_OK;
-}
-
-// the checks every call on a cache shares; NULL: fine
-static const char* jf_check_cache(const void* state, const void* cache, int64_t n_rows, int ns) {
-  if (!state || !cache) return "state and cache are required";
-  if ((((uintptr_t)state | (uintptr_t)cache) & 15) != 0) return "state and cache must be 16-byte aligned";
-  if (ns < 1 || ns > JF_CAP) return "ns must lie in 1 .. 2176";
-  if (n_rows < 0 || n_rows > INT32_MAX) return "n_rows must lie in 0 .. 2^31 - 1";
-  return nullptr;
 }
 
 extern "C" int jrr_jfit_gather(void* state, const float* verts, const float* gt_mm, int batch, void* cache, int64_t n_rows, int64_t row0,
@@ -572,6 +573,15 @@ extern "C" int jrr_jfit_run(void* state, const void* cache, int64_t n_rows, int 
                        reinterpret_cast<const float*>(cache), (long long)row0, count, ns, lr, loss + k,
                        (k == n_steps - 1) ? grad : (float*)nullptr);
   }
+  CHECK_LAUNCH();
+  return JRR_OK;
+}
+extern "C" int jrr_jfit_set_entries(void* state, const float* J, void* stream) {
+  if (!state || !J || ((uintptr_t)state & 15) != 0 || ((uintptr_t)J & 3) != 0) {
+    jrr_set_error("jrr_jfit_set_entries: bad argument (state 16-byte aligned and J are required)");
+    return JRR_ERR_ARG;
+  }
+  hipLaunchKernelGGL(k_jfit_set_entries, dim3(1), dim3(JF_THREADS), 0, (hipStream_t)stream, state, J);
   CHECK_LAUNCH();
   return JRR_OK;
 }

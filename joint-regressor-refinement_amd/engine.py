@@ -750,6 +750,7 @@ class RegressorFit:
         self.row_floats = (3 * self.ns + 3 * NUM_H36M) | 1
         assert int(self.lib.jrr_jfit_cache_bytes(self.n_rows, self.ns)) == self.n_rows * self.row_floats * 4
         self.cache = torch.zeros((max(self.n_rows, 1), self.row_floats), dtype=torch.float32, device=self.device)
+        self._mom_scratch = None                                   # the scratch of jrr_jfit_moments, allocated by the first call
 
     def info(self):
         """(NS, listed entries, Adam steps taken, entries per row); SYNCHRONOUS; raises when a call passed a foreign ns"""
@@ -797,6 +798,27 @@ class RegressorFit:
         J, m, v = self.J_init.clone(), torch.zeros_like(self.J_init), torch.zeros_like(self.J_init)
         check(self.lib.jrr_jfit_scatter(ptr(self.state), ptr(J), ptr(m), ptr(v), stream_ptr(self.device)), 'jfit_scatter')
         return J, m, v
+
+    def moments(self, begin: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """jrr_jfit_moments: the (W, W) float64 second moments, W = ns + 17, of cache rows [begin, begin + count) -- the sum over rows
+        and axes of point w times point w' (support vertices in m, then the ground truth in mm).  Nothing is read back."""
+        count = self.n_rows - int(begin) if count is None else int(count)
+        W = self.ns + NUM_H36M
+        if self._mom_scratch is None:
+            need = ctypes.c_size_t(0)
+            assert int(self.lib.jrr_jfit_moments_bytes(self.ns, ctypes.byref(need))) == W * W * 8
+            self._mom_scratch = torch.empty((int(need.value) + 7) // 8, dtype=torch.float64, device=self.device)
+        M = torch.empty(W, W, dtype=torch.float64, device=self.device)
+        check(self.lib.jrr_jfit_moments(ptr(self.state), ptr(self.cache), self.n_rows, int(begin), count, self.ns, ptr(M),
+                                        ptr(self._mom_scratch), self._mom_scratch.numel() * 8, stream_ptr(self.device)), 'jfit_moments')
+        return M
+
+    def set_entries(self, J: torch.Tensor) -> None:
+        """jrr_jfit_set_entries: the raw value of every listed entry from the dense J (17,6890), zeros allowed; Adam's moments and the
+        step counter start again at 0.  A listed row left without a positive entry is reported by the next info()."""
+        J = J.detach().float().contiguous()
+        assert J.shape == (NUM_H36M, NUM_VERTS) and J.device == self.device, tuple(J.shape)
+        check(self.lib.jrr_jfit_set_entries(ptr(self.state), ptr(J), stream_ptr(self.device)), 'jfit_set_entries')
 
 
 EVAL_ACC_ROW, EVAL_ACC_TRAILER = 338, 2         # include/jrr.h: JRR_EVAL_ACC_ROW, JRR_EVAL_ACC_TRAILER

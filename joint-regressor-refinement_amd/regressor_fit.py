@@ -12,6 +12,9 @@ read-back: the steps' losses and MPJPE / PA-MPJPE of the training and the held-o
 The regressor, the mask, the learning rate, the batch and the seed are the driver's: --j_regressor_init, utils.find_j_reg_mask,
 --j_reg_lr, --batch_size, --seed.  The cache holds the training rows first, the held-out rows behind them; `--fit_shuffle` permutes
 the training rows between epochs with an index copy (a seeded torch.randperm): the kernel always reads contiguous row ranges.
+
+`--fit_solve` replaces the epochs by the exact solve of the same loss from the second moments of the cache rows (regressor_solve.py;
+OUT/solve.json instead of fit.json); sources, hold-out split, cache fill, scores and checkpoint are the ones below.
 """
 from __future__ import annotations
 
@@ -45,6 +48,8 @@ def check_flags(ns) -> None:
     if ns.fit_regressor is None:
         if ns.fit_from is not None:
             raise ValueError('--fit_from belongs to --fit_regressor OUT')
+        if getattr(ns, 'fit_solve', False) or int(getattr(ns, 'fit_rings', 0) or 0):
+            raise ValueError('--fit_solve / --fit_rings belong to --fit_regressor OUT')
         return
     if not ns.fit_from:
         raise ValueError('--fit_regressor needs --fit_from PATH: a --save_refined table or a directory in the --eval_vertices format')
@@ -61,6 +66,18 @@ def check_flags(ns) -> None:
         raise ValueError(f'--j_reg_lr {ns.j_reg_lr}: a positive number')
     if not is_vertices_dir(ns.fit_from) and not ns.data_root:
         raise ValueError('--fit_from a --save_refined table needs --data_root (the ground truth of the split the table was written from)')
+    rings = int(getattr(ns, 'fit_rings', 0) or 0)
+    if rings < 0:
+        raise ValueError(f'--fit_rings {rings}: 0 or more')
+    if rings > 0 and not getattr(ns, 'fit_solve', False):
+        raise ValueError('--fit_rings needs --fit_solve: Adam cannot move an entry that starts at zero (relu\'(0) = 0)')
+    if getattr(ns, 'fit_solve', False):
+        if not float(ns.fit_solve_tol) > 0.0:
+            raise ValueError(f'--fit_solve_tol {ns.fit_solve_tol}: a positive number')
+        if int(ns.fit_solve_iters) < 1:
+            raise ValueError(f'--fit_solve_iters {ns.fit_solve_iters}: 1 or more')
+        if rings > 0 and is_vertices_dir(ns.fit_from) and not ns.synthetic and ns.smpl_dir == 'SPIN/data/smpl':
+            raise ValueError('--fit_rings on meshes in the --eval_vertices format needs the faces of their body model: --smpl_dir or --synthetic')
 
 
 def schedule(n_rows: int, batch: int) -> List[Tuple[int, int]]:
@@ -253,6 +270,9 @@ def fit_command(log=print) -> Optional[dict]:
     from .args import args
     ns = args._get()
     check_flags(ns)
+    if ns.fit_solve:                                               # the exact solve in place of the epochs: OUT/solve.json
+        from . import regressor_solve
+        return regressor_solve.solve_command(log)
     if jdist.env_rank_world()[0] != 0:
         return None
     device = torch.device(ns.device)

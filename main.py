@@ -8,7 +8,8 @@ networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evalu
 `--regressor_report DIR` (regressor_report.py) adds to either evaluation what the retrained regressor did to each joint, with pictures.
 `--smooth_refined DIR` (refined.smooth_command) filters a `--save_refined` table along time and exits as well;
 `--fuse_refined DIR` (refined.fuse_command) fuses its camera views of each frame and exits.
-`--fit_regressor OUT --fit_from PATH` (regressor_fit.py) fits the regressor on a table of fixed meshes and exits.
+`--fit_regressor OUT --fit_from PATH` (regressor_fit.py) fits the regressor on a table of fixed meshes and exits; with `--fit_solve`
+(regressor_solve.py) it solves that fit exactly from the table's second moments instead of taking Adam epochs.
 `--eval_accel` (accel_report.py) adds the acceleration error along each video sequence to the evaluations and to those two commands."""
 import importlib
 import os
