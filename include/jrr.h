@@ -947,6 +947,52 @@ int jrr_jfit_moments(void* state_dev, const void* cache_dev, int64_t n_rows, int
                      void* scratch_dev, size_t scratch_bytes, void* stream);
 int jrr_jfit_set_entries(void* state_dev, const float* J_dev, void* stream);
 
+/* The MPJPE solve of the regressor fit (`--fit_solve --fit_solve_loss mpjpe`): every figure the project reports for a regressor is the
+ * mean Euclidean distance per joint, and with the meshes fixed that is a convex function of the normalised weights too -- a mean of
+ * norms of affine maps -- on the same product of simplices.  One entry point on the state and the cache above gives, per pass, the
+ * objective, its exact gradient and the quadratic majoriser the host minimises (regressor_solve.py, solve_norm).
+ *
+ * Per cache row s and joint i = 1 .. 16 whose row has entries (x: the caller's weights, v: the row's support vertices):
+ *     q_i = sum_e x_i[e] v[col_i[e]],  q_0 likewise (0 when the pelvis row is empty)
+ *     r   = q_i - q_0 - gt_i / 1000                      3 doubles, m; everything in double from the fp32 cache values
+ *     rho = sqrt(r.r + delta^2), delta > 0               L_delta(x) = sum_{s,i} rho / (n 17)
+ *     L(x) = sum |r| / (n 17)                            1000 L is the training MPJPE in mm: the pelvis term is zero and the mean still
+ *                                                        divides by 17, as jrr_evaluate does;  L <= L_delta <= L + delta.
+ * A row without entries is left out of the sums, exactly as jrr_jfit_run leaves it out.  L_delta is smooth and convex; on the product of
+ * simplices 0 <= L_delta(x) - min L_delta <= gap(x), the Frank-Wolfe gap with the gradient of L_delta, hence L(x) - min L <= gap(x) + delta.
+ * Majoriser at x^k:  rho(r) <= rho_k + (|r|^2 - |r_k|^2) / (2 rho_k).  The points p_a of joint i are the vertices of row i's entries in
+ * list order, then those of row 0's entries in list order: K_i = cnt_i + cnt_0 <= 256.  With D_i = (x_i - x_i^k ; -(x_0 - x_0^k)),
+ *     Q(x) = L_delta(x^k) + (1 / (n 17)) sum_i [ b_i . D_i + 1/2 D_i^T A_i D_i ]
+ *     A_i[a][b] = sum_s w sum_c p_a,c p_b,c      b_i[a] = sum_s w sum_c r_c p_a,c      w = 1 / rho_k
+ * and any x with Q(x) <= Q(x^k) has L_delta(x) <= L_delta(x^k).  b_i is also the exact gradient of (n 17) L_delta at x^k (the pelvis row
+ * collects minus each joint's second half).  Forming r directly in double avoids the cancellation that forced fp64 on jrr_jfit_moments.
+ *
+ * jrr_jfit_norm_bytes   the bytes of the output for the rows' counts (counts[17], as jrr_jfit_info reports them); *scratch_bytes
+ *                  (nullable) receives the bytes of the caller-owned scratch.  Both are functions of the counts alone; a count outside
+ *                  0 .. 128 or a NULL counts: both 0.
+ * jrr_jfit_norm_moments  of cache rows [begin, begin + count).  The state supplies only the LISTS (each row's entries and counts); the
+ *                  weights are x_dev [17][128] doubles, entry e of row i at i * 128 + e (entries behind a row's count are not read): the
+ *                  certificate is about exactly the point the host holds, not about the state's fp32 copy of it.
+ *                  out_dev holds, for i = 1 .. 16 in order, a block of K_i^2 + K_i + 4 doubles: A_i row-major, b_i, then
+ *                  sum rho, sum |r|, sum w and the number of samples counted.  K_i = 0 when row i is empty: only the four scalars,
+ *                  zeros.  JRR_JFIT_NORM_UNIT: w = 1 and delta_m >= 0 enters rho alone (rho = sqrt(r.r + delta^2), which is |r| at
+ *                  delta = 0); A_i is then the gathered sub-block of jrr_jfit_moments' M and the quadratic is the `--fit_solve`
+ *                  problem.  JRR_JFIT_NORM_INV: w = 1 / rho, and delta_m must be finite and > 0.
+ *                  The rows are cut into chunks as by jrr_jfit_moments; a second launch adds the chunks' slabs in a fixed order and
+ *                  writes both triangles of A_i from the same sum.  No floating-point atomics: two calls give the same bits,
+ *                  A_i == A_i^T bitwise, count == 0 zeroes the output.  The call reads the 17 counts of the state back before it
+ *                  launches (it synchronises the stream once); the results are enqueued, not read back.
+ *                  NULL pointers, misalignment (state and cache 16 bytes; x, out, scratch 8), a range outside [0, n_rows], an ns
+ *                  outside 1 .. 2176, an unknown mode, a delta_m that is negative or not finite, or not positive in INV mode, a state
+ *                  that is not a prepared one: JRR_ERR_ARG, before anything is launched.  A scratch below jrr_jfit_norm_bytes:
+ *                  JRR_ERR_WORKSPACE.  An ns that is not the prepared NS is found on the device: the error word of the state is set
+ *                  (the next jrr_jfit_info reports it) and the output is filled with NaN.                                         */
+enum { JRR_JFIT_NORM_UNIT = 0, JRR_JFIT_NORM_INV = 1 };
+size_t jrr_jfit_norm_bytes(const int32_t counts[17], size_t* scratch_bytes);
+int jrr_jfit_norm_moments(void* state_dev, const void* cache_dev, int64_t n_rows, int64_t begin, int64_t count, int ns,
+                          const double* x_dev /* [17][128] */, int mode, double delta_m, double* out_dev, void* scratch_dev,
+                          size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

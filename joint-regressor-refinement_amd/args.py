@@ -107,6 +107,13 @@ def build_parser() -> argparse.ArgumentParser:
                         help='--fit_solve: stop when the Frank-Wolfe gap is at most this fraction of the initial loss')
     parser.add_argument('--fit_solve_iters', type=int, default=1000,
                         help='--fit_solve: most Newton steps; solve.json says `converged: false` when they end the solve')
+    parser.add_argument('--fit_solve_loss', type=str, default='mse', choices=['mse', 'mpjpe'],
+                        help='--fit_solve: what the solve minimises.  mse: the mean squared joint error the Adam epochs train with.  mpjpe: '
+                             'the mean Euclidean distance per joint, the figure every report states -- convex too, solved by reweighted '
+                             'fp64 moment passes (jrr_jfit_norm_moments) with the certificate MPJPE - optimum <= gap + delta; solve.json '
+                             'gains the key `norm`')
+    parser.add_argument('--fit_solve_delta_mm', type=float, default=0.01,
+                        help='--fit_solve_loss mpjpe: the smoothing of the norm, sqrt(|r|^2 + delta^2), in mm; finite and > 0')
     parser.add_argument('--eval_report', type=str, default=None, metavar='DIR',
                         help='evaluation report: DIR/eval.json and DIR/eval.md with MPJPE / PA-MPJPE per group and per joint, PCK and AUC, '
                              'initial against retrained regressor (eval_report.py); the printed lines of scripts/test.py:125-138 stay as they are')

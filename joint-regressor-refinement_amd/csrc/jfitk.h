@@ -1,5 +1,5 @@
 // The state and the cache of the regressor fit (include/jrr.h, jrr_jfit_*), shared by jfit.hip (prepare, gather, joints, step, scatter,
-// set_entries) and jmom.hip (the moments of a cache range).
+// set_entries), jmom.hip (the moments of a cache range) and jnorm.hip (the reweighted moments of the MPJPE solve).
 //
 // State (one caller-owned buffer, JF_* word offsets below): the union cols[NS] of the positive columns of J_init*mask, and the listed
 // entries of all rows FLATTENED in row order -- entry idx of row i lives at off[i] <= idx < off[i + 1] -- with, per entry, its row and

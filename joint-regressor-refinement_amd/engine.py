@@ -722,6 +722,7 @@ class JointRegressorTable:
 
 
 JFIT_ROW_CAP, JFIT_SPW, JFIT_MAX_WG, JFIT_INFO = 128, 32, 256, 24      # include/jrr.h: JRR_JFIT_*
+NORM_UNIT, NORM_INV = 0, 1                                              # include/jrr.h: JRR_JFIT_NORM_*
 
 
 class RegressorFit:
@@ -751,6 +752,7 @@ class RegressorFit:
         assert int(self.lib.jrr_jfit_cache_bytes(self.n_rows, self.ns)) == self.n_rows * self.row_floats * 4
         self.cache = torch.zeros((max(self.n_rows, 1), self.row_floats), dtype=torch.float32, device=self.device)
         self._mom_scratch = None                                   # the scratch of jrr_jfit_moments, allocated by the first call
+        self._norm_scratch = None                                  # the same of jrr_jfit_norm_moments
 
     def info(self):
         """(NS, listed entries, Adam steps taken, entries per row); SYNCHRONOUS; raises when a call passed a foreign ns"""
@@ -812,6 +814,32 @@ class RegressorFit:
         check(self.lib.jrr_jfit_moments(ptr(self.state), ptr(self.cache), self.n_rows, int(begin), count, self.ns, ptr(M),
                                         ptr(self._mom_scratch), self._mom_scratch.numel() * 8, stream_ptr(self.device)), 'jfit_moments')
         return M
+
+    def norm_moments(self, x, mode: int, delta_m: float, begin: int = 0, count: Optional[int] = None) -> torch.Tensor:
+        """jrr_jfit_norm_moments: the blocks (A_i, b_i, sum rho, sum |r|, sum w, samples; i = 1 .. 16) of cache rows
+        [begin, begin + count) at the weights x as one float64 device tensor (regressor_solve.parse_norm_blocks reads it).  x: 17 rows of
+        float64 weights, row i as long as the state's list of row i, or a (17,128) float64 tensor.  mode: NORM_UNIT or NORM_INV."""
+        count = self.n_rows - int(begin) if count is None else int(count)
+        if torch.is_tensor(x):
+            xd = x.to(device=self.device, dtype=torch.float64).contiguous()
+        else:
+            xh = np.zeros((NUM_H36M, JFIT_ROW_CAP), dtype=np.float64)
+            assert len(x) == NUM_H36M and [len(r) for r in x] == self.counts, 'x: one row of weights per list, of the list\'s length'
+            for i, r in enumerate(x):
+                xh[i, :len(r)] = np.asarray(r, dtype=np.float64)
+            xd = torch.from_numpy(xh).to(self.device)
+        assert xd.shape == (NUM_H36M, JFIT_ROW_CAP)
+        if self._norm_scratch is None:
+            counts = (c_int32 * NUM_H36M)(*self.counts)
+            need = ctypes.c_size_t(0)
+            self._norm_doubles = int(self.lib.jrr_jfit_norm_bytes(counts, ctypes.byref(need))) // 8
+            assert self._norm_doubles >= 4 * (NUM_H36M - 1)
+            self._norm_scratch = torch.empty((int(need.value) + 7) // 8, dtype=torch.float64, device=self.device)
+        out = torch.empty(self._norm_doubles, dtype=torch.float64, device=self.device)
+        check(self.lib.jrr_jfit_norm_moments(ptr(self.state), ptr(self.cache), self.n_rows, int(begin), count, self.ns, ptr(xd), int(mode),
+                                             float(delta_m), ptr(out), ptr(self._norm_scratch), self._norm_scratch.numel() * 8,
+                                             stream_ptr(self.device)), 'jfit_norm_moments')
+        return out
 
     def set_entries(self, J: torch.Tensor) -> None:
         """jrr_jfit_set_entries: the raw value of every listed entry from the dense J (17,6890), zeros allowed; Adam's moments and the

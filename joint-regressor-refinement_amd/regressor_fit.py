@@ -45,6 +45,13 @@ def is_vertices_dir(path: str) -> bool:
 
 def check_flags(ns) -> None:
     """what the flags of the fit must satisfy, before anything is launched"""
+    loss_kind, delta_mm = getattr(ns, 'fit_solve_loss', 'mse'), float(getattr(ns, 'fit_solve_delta_mm', 0.01))
+    if loss_kind not in ('mse', 'mpjpe'):
+        raise ValueError(f'--fit_solve_loss {loss_kind}: mse or mpjpe')
+    if not (np.isfinite(delta_mm) and delta_mm > 0.0):
+        raise ValueError(f'--fit_solve_delta_mm {delta_mm}: a finite positive number of millimetres')
+    if (loss_kind != 'mse' or delta_mm != 0.01) and not getattr(ns, 'fit_solve', False):
+        raise ValueError('--fit_solve_loss / --fit_solve_delta_mm need --fit_solve')
     if ns.fit_regressor is None:
         if ns.fit_from is not None:
             raise ValueError('--fit_from belongs to --fit_regressor OUT')

@@ -12,6 +12,9 @@ jrr_jfit_moments: one pass over the table, fp64).  This module is the host side,
                       active, which Adam on relu(J * mask) can never do (relu'(0) = 0)
   solve_command       the command: moments of the training and the held-out rows, the solve, the weights into the state
                       (jrr_jfit_set_entries), scores, checkpoint, OUT/solve.json
+  solve_norm          `--fit_solve_loss mpjpe`: the minimiser of the smoothed MPJPE L_delta (include/jrr.h, jrr_jfit_norm_moments) by
+                      majorise-minimise -- each pass (the device's, or norm_blocks_reference) gives the objective, its gradient, the gap
+                      and a quadratic majoriser, which solve_quadratic_blocks minimises; certificate L(x) - min L <= gap + delta
 
 The solver is a projected Newton method on the faces of the simplices.  At x the free set is the entries with x > 0 and the entries
 at zero whose gradient lies below their row's multiplier grad_i . x_i (they want to enter).  On the free set the sum constraints are
@@ -219,6 +222,232 @@ def solve(M, n: int, lists, x0, tol: float = 1e-6, max_iter: int = 1000, ridge: 
     return {'x': split(xf), 'loss': loss, 'loss0': loss0, 'gap': gap, 'iterations': it, 'converged': bool(gap <= tol * loss0)}
 
 
+# ---- the MPJPE solve (`--fit_solve_loss mpjpe`; include/jrr.h, jrr_jfit_norm_moments) ---------------------------------------------------
+NORM_UNIT, NORM_INV = 0, 1            # include/jrr.h: JRR_JFIT_NORM_*
+NORM_KEYS = ('delta_mm', 'objective_mm', 'gap_mm', 'bound_mm', 'passes', 'inner_iterations')
+NORM_OBJECTIVE_KEYS = ('start', 'mse', 'final', 'holdout_start', 'holdout_mse', 'holdout_final')
+INNER_FRACTION = 0.1                  # a surrogate QP stops at a Frank-Wolfe gap of this fraction of the outer gap it was built at
+
+
+def norm_block_offsets(counts) -> List[int]:
+    """the first double of joint i's block in the output of jrr_jfit_norm_moments, i = 1 .. 16, then the total: entry i - 1 of the list
+    (K_i = counts[i] + counts[0], or 0 for an empty row; a block is K_i^2 + K_i + 4 doubles)"""
+    counts = [int(c) for c in counts]
+    if len(counts) != NJ or min(counts) < 0 or max(counts) > ROW_CAP:
+        raise ValueError(f'counts: {NJ} numbers in 0 .. {ROW_CAP}')
+    out, o = [], 0
+    for i in range(1, NJ):
+        K = counts[i] + counts[0] if counts[i] else 0
+        out.append(o)
+        o += K * K + K + 4
+    return out + [o]
+
+
+def parse_norm_blocks(flat, counts) -> list:
+    """the output of jrr_jfit_norm_moments as a list of 17: None for the pelvis, else {'A' (K, K), 'b' (K,), 'rho', 'abs', 'w', 'n',
+    'cnt': the joint's own entries -- the first cnt of the K points; the rest are the pelvis row's}"""
+    flat = np.asarray(flat, dtype=np.float64).reshape(-1)
+    offs = norm_block_offsets(counts)
+    if flat.size != offs[-1]:
+        raise ValueError(f'{flat.size} doubles for counts that need {offs[-1]}')
+    blocks = [None]
+    for i in range(1, NJ):
+        K = int(counts[i]) + int(counts[0]) if counts[i] else 0
+        o = offs[i - 1]
+        s = flat[o + K * K + K:o + K * K + K + 4]
+        blocks.append({'A': flat[o:o + K * K].reshape(K, K), 'b': flat[o + K * K:o + K * K + K], 'rho': float(s[0]), 'abs': float(s[1]),
+                       'w': float(s[2]), 'n': float(s[3]), 'cnt': int(counts[i])})
+    return blocks
+
+
+def norm_blocks_reference(rows, lists, x, mode: int, delta: float, dtype=np.float64) -> list:
+    """the pass of jrr_jfit_norm_moments restated in numpy (parse_norm_blocks' form): rows (n, ns + 17, 3) the cache rows as points (the
+    union's vertices in m, then the ground truth in mm), lists / x as for loss_from_moments, delta in m.  dtype: the arithmetic."""
+    lists = _lists(lists)
+    x = _rows(x, lists)
+    if mode not in (NORM_UNIT, NORM_INV) or not (np.isfinite(delta) and delta >= 0.0) or (mode == NORM_INV and not delta > 0.0):
+        raise ValueError(f'mode {mode} with delta {delta}')
+    R = np.asarray(rows).astype(dtype)
+    n, W = R.shape[0], R.shape[1]
+    ns = W - NJ
+    d = dtype(delta)
+    thousand = dtype(1000.0)
+    blocks = [None]
+    P0 = R[:, lists[0]]
+    x0 = x[0].astype(dtype)
+    for i in range(1, NJ):
+        ci = lists[i].size
+        if ci == 0:
+            blocks.append({'A': np.zeros((0, 0)), 'b': np.zeros(0), 'rho': 0.0, 'abs': 0.0, 'w': 0.0, 'n': 0.0, 'cnt': 0})
+            continue
+        P = np.concatenate([R[:, lists[i]], P0], axis=1)                      # (n, K, 3)
+        wt = np.concatenate([x[i].astype(dtype), -x0])
+        r = np.einsum('e,nec->nc', wt, P) - R[:, ns + i] / thousand
+        rr = (r * r).sum(1)
+        rho = np.sqrt(rr + d * d)
+        w = 1.0 / rho if mode == NORM_INV else np.ones(n, dtype=dtype)
+        A = np.einsum('n,nac,nbc->ab', w, P, P)
+        b = np.einsum('n,nc,nac->a', w, r, P)
+        blocks.append({'A': A, 'b': b, 'rho': rho.sum(), 'abs': np.sqrt(rr).sum(), 'w': w.sum(), 'n': float(n), 'cnt': ci})
+    return blocks
+
+
+def norm_objective(blocks, n: int):
+    """(L_delta, L): sum rho / (n 17) and sum |r| / (n 17) over the joints' blocks -- 1000 L is the MPJPE in mm of the n rows"""
+    c = 1.0 / (float(n) * NJ)
+    return c * float(sum(b['rho'] for b in blocks[1:])), c * float(sum(b['abs'] for b in blocks[1:]))
+
+
+def norm_gradient(blocks, n: int, lists) -> List[np.ndarray]:
+    """the gradient of L_delta per row from the b_i of an INV pass: row i takes b_i's first cnt_i elements, the pelvis row minus the sum
+    of every joint's second half, all over n 17"""
+    lists = _lists(lists)
+    c = 1.0 / (float(n) * NJ)
+    grads = [np.zeros(l.size) for l in lists]
+    for i in range(1, NJ):
+        ci = lists[i].size
+        if ci == 0:
+            continue
+        b = np.asarray(blocks[i]['b'], dtype=np.float64)
+        if b.size != ci + lists[0].size:
+            raise ValueError(f'block {i} has {b.size} points for lists of {ci} + {lists[0].size}')
+        grads[i] = c * b[:ci]
+        if lists[0].size:
+            grads[0] = grads[0] - c * b[ci:]
+    return grads
+
+
+def _block_hessian(blocks, n, lists):
+    """the Hessian of the surrogate over the flattened entries: joint x joint A_i[:c, :c], joint x pelvis -A_i[:c, c:], pelvis x pelvis
+    the sum of A_i[c:, c:], over n 17"""
+    sizes = [l.size for l in lists]
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    E = int(off[-1])
+    H = np.zeros((E, E))
+    c0 = sizes[0]
+    for i in range(1, NJ):
+        ci = sizes[i]
+        if ci == 0:
+            continue
+        A = np.asarray(blocks[i]['A'], dtype=np.float64)
+        a, e = int(off[i]), int(off[i]) + ci
+        H[a:e, a:e] += A[:ci, :ci]
+        if c0:
+            H[a:e, :c0] -= A[:ci, ci:]
+            H[:c0, a:e] -= A[ci:, :ci]
+            H[:c0, :c0] += A[ci:, ci:]
+    row = np.concatenate([np.full(s, i, dtype=np.int64) for i, s in enumerate(sizes)])
+    return H / (float(n) * NJ), row
+
+
+def solve_quadratic_blocks(blocks, n: int, lists, x_k, gap_stop: float, max_iter: int = 1000, ridge: float = 1e-9) -> dict:
+    """minimise the surrogate Q(x) = const + sum_i [b_i . D_i + 1/2 D_i^T A_i D_i] / (n 17), D_i = (x_i - x_k_i ; -(x_0 - x_k_0)), over the
+    product of the rows' simplices from x_k, by the projected Newton method of `solve`; ends at a Frank-Wolfe gap OF THE SURROGATE of
+    at most gap_stop.  Every step lowers Q, so the result has Q(x) <= Q(x_k).  Returns {'x', 'gap', 'iterations', 'decrease': Q(x_k) - Q(x)}."""
+    lists = _lists(lists)
+    x_k = _rows(x_k, lists)
+    cuts = np.cumsum([l.size for l in lists])[:-1]
+    split = lambda xf: np.split(xf, cuts)
+    H, row = _block_hessian(blocks, n, lists)
+    g0 = np.concatenate(norm_gradient(blocks, n, lists))
+    xk = np.concatenate(x_k)
+    xf = xk.copy()
+    it = 0
+    while True:
+        g = g0 + H @ (xf - xk)
+        lam = np.bincount(row, weights=xf * g, minlength=NJ)
+        gap = fw_gap(split(xf), split(g))
+        if gap <= gap_stop or it >= max_iter:
+            break
+        it += 1
+        free = (xf > 0.0) | (g < lam[row])
+        while True:
+            p = _newton_direction(H, g, free, row, ridge)
+            blocked = free & (xf <= 0.0) & (p < 0.0)
+            if not blocked.any():
+                break
+            free &= ~blocked
+        slope = float(g @ p)
+        if not slope < 0.0:
+            break                                      # no descent direction is left at this precision
+        curv = float(p @ (H @ p))
+        alpha = -slope / curv if curv > 0.0 else np.inf
+        neg = p < 0.0
+        room = np.full(xf.size, np.inf)
+        room[neg] = xf[neg] / -p[neg]
+        amax = float(room.min()) if neg.any() else np.inf
+        if not np.isfinite(min(alpha, amax)):
+            break
+        if amax <= alpha:
+            hit = room <= amax
+            xf = xf + amax * p
+            xf[hit] = 0.0
+        else:
+            xf = xf + alpha * p
+        xf = _normalised(xf, row)
+    D = xf - xk
+    return {'x': split(xf), 'gap': gap, 'iterations': it, 'decrease': -float(g0 @ D + 0.5 * D @ (H @ D))}
+
+
+def solve_norm(pass_fn, n: int, lists, x0, delta: float, tol: float = 1e-6, max_iter: int = 1000, ridge: float = 1e-9) -> dict:
+    """minimise L_delta (include/jrr.h) over the product of the rows' simplices.  pass_fn(x, mode, delta) -> blocks (parse_norm_blocks'
+    form) of the n training rows: the device pass, or norm_blocks_reference.  Pass 0 is UNIT at x0: its quadratic is the `--fit_solve`
+    problem and its minimiser x_mse the first iterate.  Then INV passes, each followed by the minimisation of its majoriser down to
+    INNER_FRACTION of the pass's gap, until gap(L_delta) <= tol * L_delta(x0) or max_iter INV passes.
+
+    Returns {'x', 'x_mse', 'objective': {'start', 'mse', 'final'} (L, m), 'smoothed': the same of L_delta, 'gap' (of L_delta at x),
+    'bound': gap + delta >= L(x) - min L, 'passes' (all, the UNIT one included), 'inner_iterations', 'converged',
+    'sequence': L_delta at the INV passes -- never rising}."""
+    lists = _lists(lists)
+    x0 = _rows(x0, lists)
+    if not (np.isfinite(delta) and delta > 0.0):
+        raise ValueError(f'solve_norm: delta {delta}: finite and positive')
+    row = np.concatenate([np.full(l.size, i, dtype=np.int64) for i, l in enumerate(lists)])
+    if row.size == 0:
+        raise ValueError('solve_norm: no listed entry')
+    cuts = np.cumsum([l.size for l in lists])[:-1]
+    xf = np.concatenate(x0)
+    if (xf < 0).any() or (np.bincount(row, weights=xf, minlength=NJ)[np.unique(row)] <= 0).any():
+        raise ValueError('solve_norm: x0 needs non-negative rows with a positive sum')
+    x = np.split(_normalised(xf, row), cuts)
+    blocks = pass_fn(x, NORM_UNIT, delta)
+    Ld0, L0 = norm_objective(blocks, n)
+    g = norm_gradient(blocks, n, lists)                             # UNIT: the gradient of the quadratic, not of L_delta
+    inner = solve_quadratic_blocks(blocks, n, lists, x, 1e-9 * max(fw_gap(x, g), 0.0), max_iter, ridge)
+    x_mse = x = inner['x']
+    inner_total, passes, seq = inner['iterations'], 1, []
+    mse = None
+    while True:
+        blocks = pass_fn(x, NORM_INV, delta)
+        passes += 1
+        Ld, L = norm_objective(blocks, n)
+        seq.append(Ld)
+        if mse is None:
+            mse = (Ld, L)
+        g = norm_gradient(blocks, n, lists)
+        gap = fw_gap(x, g)
+        if gap <= tol * Ld0 or len(seq) >= max_iter:
+            break
+        inner = solve_quadratic_blocks(blocks, n, lists, x, INNER_FRACTION * gap, max_iter, ridge)
+        inner_total += inner['iterations']
+        if not inner['decrease'] > 0.0:
+            break                                      # the majoriser cannot be lowered at this precision
+        x = inner['x']
+    return {'x': x, 'x_mse': x_mse, 'objective': {'start': L0, 'mse': mse[1], 'final': L},
+            'smoothed': {'start': Ld0, 'mse': mse[0], 'final': Ld}, 'gap': gap, 'bound': gap + float(delta), 'passes': passes,
+            'inner_iterations': inner_total, 'converged': bool(gap <= tol * Ld0), 'sequence': seq}
+
+
+def build_norm_doc(result: dict, delta_mm: float, holdout: Optional[dict]) -> dict:
+    """the `norm` key of solve.json from what solve_norm returned; holdout: {'start', 'mse', 'final'} (L, m) of the held-out rows or None"""
+    mm = lambda v: None if v is None else 1000.0 * float(v)
+    obj = {k: mm(result['objective'][k]) for k in ('start', 'mse', 'final')}
+    for k in ('start', 'mse', 'final'):
+        obj['holdout_' + k] = mm(holdout[k]) if holdout else None
+    return {'delta_mm': float(delta_mm), 'objective_mm': obj, 'gap_mm': mm(result['gap']), 'bound_mm': mm(result['bound']),
+            'passes': int(result['passes']), 'inner_iterations': int(result['inner_iterations'])}
+
+
 def ring_candidates(J_masked, faces, k: int) -> List[np.ndarray]:
     """per row of J_masked (17, V) = J_init * mask: the vertices of its positive entries plus every vertex within k mesh edges of one
     of them, ascending.  faces (F, 3): the triangles of the mesh.  A row above JRR_JFIT_ROW_CAP = 128 candidates raises ValueError."""
@@ -326,8 +555,26 @@ def solve_command(log=print) -> Optional[dict]:
         r = np.maximum(Jm[i, v].astype(np.float64), 0.0)
         x0.append(r / r.sum() if v.size else r)
     tol = float(ns.fit_solve_tol)
-    res = solve(M_train, n_train, lists, x0, tol=tol, max_iter=int(ns.fit_solve_iters))
-    losses = {'train_before': res['loss0'], 'train_after': res['loss'], 'holdout_before': None, 'holdout_after': None}
+    norm_doc = None
+    if getattr(ns, 'fit_solve_loss', 'mse') == 'mpjpe':
+        # the MPJPE itself: reweighted moment passes on the device, the quadratics on the host; the MSE loss block below then says
+        # what the switch costs in MSE; `gap` is the gap of the smoothed MPJPE in m, `iterations` the Newton steps of all quadratics
+        delta = float(ns.fit_solve_delta_mm) / 1000.0
+        blocks_of = lambda x, mode, d, a, c: parse_norm_blocks(jf.norm_moments(x, mode, d, a, c).cpu().numpy(), jf.counts)
+        nres = solve_norm(lambda x, mode, d: blocks_of(x, mode, d, 0, n_train), n_train, lists, x0, delta, tol=tol,
+                          max_iter=int(ns.fit_solve_iters))
+        held_obj = None
+        if n_hold:
+            held_obj = {k: norm_objective(blocks_of(xs, NORM_INV, delta, n_train, n_hold), n_hold)[1]
+                        for k, xs in (('start', x0), ('mse', nres['x_mse']), ('final', nres['x']))}
+        jf.info()
+        norm_doc = build_norm_doc(nres, float(ns.fit_solve_delta_mm), held_obj)
+        res = {'x': nres['x'], 'loss0': loss_from_moments(M_train, n_train, lists, x0)[0],
+               'loss': loss_from_moments(M_train, n_train, lists, nres['x'])[0], 'gap': nres['gap'], 'iterations': nres['inner_iterations'],
+               'converged': nres['converged']}
+    else:
+        res = solve(M_train, n_train, lists, x0, tol=tol, max_iter=int(ns.fit_solve_iters))
+    losses ={'train_before': res['loss0'], 'train_after': res['loss'], 'holdout_before': None, 'holdout_after': None}
     if n_hold:
         losses['holdout_before'] = loss_from_moments(M_hold, n_hold, lists, x0)[0]
         losses['holdout_after'] = loss_from_moments(M_hold, n_hold, lists, res['x'])[0]
@@ -344,13 +591,20 @@ def solve_command(log=print) -> Optional[dict]:
     checkpoint.save_j_regressor(J, path)
     doc = build_doc(source.kind, rf.flags_doc(ns), n_train, n_hold, rings, rf.support_counts(J_np, mask_np), [v.size for v in cands],
                     rf.support_counts(J.cpu().numpy(), mask_np), losses, res, tol, before, after, path, ns.j_regressor_init)
+    if norm_doc is not None:
+        doc['norm'] = norm_doc
     with open(os.path.join(ns.fit_regressor, 'solve.json'), 'w') as f:
         json.dump(doc, f, indent=1, sort_keys=True, default=str)
     fmt = lambda d, k: '-' if d is None or d[k] is None else format(d[k], '.4f')
+    extra = ''
+    if norm_doc is not None:
+        o = norm_doc['objective_mm']
+        extra = (f', objective MPJPE in {norm_doc["passes"]} passes: {o["start"]:.4f} mm at the start, {o["mse"]:.4f} mm at the MSE optimum, '
+                 f'{o["final"]:.4f} mm at the end, at most {norm_doc["bound_mm"]:.3e} mm above the optimum (delta {norm_doc["delta_mm"]:g} mm)')
     log(f'solved the regressor on {n_train} rows ({n_hold} held out, {jf.entries} entries on {jf.ns} vertices, {rings} rings) in '
         f'{res["iterations"]} steps: loss {res["loss0"]:.6e} -> {res["loss"]:.6e}, gap {res["gap"]:.3e} '
         f'({"converged" if res["converged"] else "NOT converged"} at tol {tol:g}), support {sum(doc["support"]["before"])} -> '
         f'{sum(doc["support"]["after"])}, MPJPE {fmt(before["train"], "mpjpe_mm")} -> {fmt(after["train"], "mpjpe_mm")} (held out '
         f'{fmt(before["holdout"], "mpjpe_mm")} -> {fmt(after["holdout"], "mpjpe_mm")}), PAMPJPE {fmt(before["train"], "pampjpe_mm")} -> '
-        f'{fmt(after["train"], "pampjpe_mm")} (held out {fmt(before["holdout"], "pampjpe_mm")} -> {fmt(after["holdout"], "pampjpe_mm")}); {path}')
+        f'{fmt(after["train"], "pampjpe_mm")} (held out {fmt(before["holdout"], "pampjpe_mm")} -> {fmt(after["holdout"], "pampjpe_mm")}){extra}; {path}')
     return doc
