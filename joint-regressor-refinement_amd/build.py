@@ -79,6 +79,211 @@ def _parse(out: str):
     return [r for r in rows if 'vgpr' in r]
 
 
+def waitcnt_rows(sources=None, asm=None):
+    """The s_waitcnt instructions THE COMPILER inserted, per kernel, of the CURRENT sources (device assembly compiled into a scratch
+    directory; `asm`: a dict {source name: assembly text} to parse instead).  Waits written in inline asm (between ;;#ASMSTART and
+    ;;#ASMEND) are ours and are left out.  One dict per wait:
+        name    demangled kernel name with its template arguments (no parameter list)
+        loop    label of the header of the innermost loop around the wait's basic block, None outside every loop
+        depth   nesting depth of that loop (0 outside)
+        block   the basic block: its label, or `label+k` for the k-th block behind a branch that has no label of its own
+        text    the instruction
+        vmcnt   the vmcnt it waits for, None if it has no vmcnt field (vmcnt 0 = a full drain of loads, stores and LDS-DMA)
+        mfma    matrix instructions in the same basic block
+        loads   global / buffer loads in the same basic block
+    A kernel that prefetches into registers wants COUNTED waits (vmcnt(N), N > 0) in the blocks of its main loop that do the matrix
+    work: tests/test_waitcnt_codegen.py."""
+    import re
+    import tempfile
+    import shutil
+    if asm is None:
+        tmp = tempfile.mkdtemp(prefix='jrr_asm_')
+        names = list(sources or SOURCES)
+        jobs = [[_hipcc()] + FLAGS + ['--cuda-device-only', '-S', os.path.join(CSRC, src), '-o', os.path.join(tmp, src.replace('.hip', '.s'))]
+                for src in names]
+        with ThreadPoolExecutor(max_workers=min(len(jobs), 8)) as ex:
+            outs = list(ex.map(lambda cmd: subprocess.run(cmd, capture_output=True, text=True), jobs))
+        asm = {}
+        try:
+            for src, p in zip(names, outs):
+                if p.returncode != 0:
+                    raise RuntimeError('hipcc failed:\n' + p.stderr[-2000:])
+                with open(os.path.join(tmp, src.replace('.hip', '.s'))) as f:
+                    asm[src] = f.read()
+        finally:
+            shutil.rmtree(tmp, ignore_errors=True)
+    rows = []
+    for text in asm.values():
+        rows += _waitcnt_parse(text)
+    mangled = sorted({r['name'] for r in rows})
+    if mangled:
+        try:
+            dem = subprocess.run(['c++filt'], input='\n'.join(mangled), capture_output=True, text=True).stdout.splitlines()
+        except OSError:
+            dem = []
+        if len(dem) == len(mangled):
+            table = dict(zip(mangled, dem))
+            for r in rows:
+                full = table[r['name']]
+                # cut the parameter list, keep the template arguments: `void jrr::k<0, 8, false>(float const*, ...)`
+                depth, cut = 0, len(full)
+                for i, ch in enumerate(full):
+                    if ch == '<':
+                        depth += 1
+                    elif ch == '>':
+                        depth -= 1
+                    elif ch == '(' and depth == 0:
+                        cut = i
+                        break
+                r['name'] = full[:cut].replace('void ', '', 1)
+    return rows
+
+
+def _waitcnt_parse(text: str):
+    import re
+    rows = []
+    lines = text.splitlines()
+    i = 0
+    fn_re = re.compile(r'^(_Z\w+):')
+    lab_re = re.compile(r'^(\.LBB\d+_\d+):(.*)$')
+    while i < len(lines):
+        m = fn_re.match(lines[i])
+        if not m:
+            i += 1
+            continue
+        name = m.group(1)
+        i += 1
+        # basic blocks of the function: a label opens one, a branch closes one
+        blocks, cur = [], {'label': 'entry', 'loop': None, 'depth': 0, 'ins': []}
+        last_label, sub, in_asm, hdr_depth = 'entry', 0, False, {}
+        while i < len(lines) and not lines[i].startswith('.Lfunc_end'):
+            ln = lines[i]
+            i += 1
+            lm = lab_re.match(ln)
+            if lm:
+                blocks.append(cur)
+                label, note = lm.group(1), lm.group(2)
+                loop, depth = None, 0
+                h = re.search(r'Loop Header: Depth=(\d+)', note)
+                if h:
+                    loop, depth = label, int(h.group(1))
+                    hdr_depth[label] = depth
+                else:
+                    h = re.search(r'in Loop: Header=(BB\d+_\d+) Depth=(\d+)', note)
+                    if h:
+                        loop, depth = '.L' + h.group(1), int(h.group(2))
+                cur = {'label': label, 'loop': loop, 'depth': depth, 'ins': []}
+                last_label, sub = label, 0
+                continue
+            s = ln.strip()
+            if s.startswith(';;#ASMSTART'):
+                in_asm = True
+                continue
+            if s.startswith(';;#ASMEND'):
+                in_asm = False
+                continue
+            if not s or s.startswith(';') or s.startswith('.'):
+                continue
+            ins = s.split(';')[0].strip()
+            if not ins:
+                continue
+            cur['ins'].append((ins, in_asm))
+            b = re.match(r's_c?branch\w*\s+(\.LBB\d+_\d+)', ins)
+            if b:
+                blocks.append(cur)
+                sub += 1
+                # the block behind a branch belongs to the loop of the block before it -- unless that branch was the loop's back edge
+                loop, depth = cur['loop'], cur['depth']
+                if loop is not None and b.group(1) == loop:
+                    loop, depth = None, 0
+                cur = {'label': f'{last_label}+{sub}', 'loop': loop, 'depth': depth, 'ins': []}
+        blocks.append(cur)
+        for blk in blocks:
+            mfma = sum(1 for ins, _ in blk['ins'] if ins.startswith('v_mfma'))
+            loads = sum(1 for ins, _ in blk['ins'] if re.match(r'(global|buffer|flat)_load', ins))
+            for ins, ours in blk['ins']:
+                if ours or not ins.startswith('s_waitcnt'):
+                    continue
+                v = re.search(r'vmcnt\((\d+)\)', ins)
+                rows.append({'name': name, 'loop': blk['loop'], 'depth': blk['depth'], 'block': blk['label'], 'text': ins,
+                             'vmcnt': int(v.group(1)) if v else None, 'mfma': mfma, 'loads': loads})
+    return rows
+
+
+def asm_load_hazards(asm: dict):
+    """Loads issued from inline asm (csrc/jrr_common.h, quad_load) are invisible to the compiler's wait insertion: nothing but the
+    hand-written `s_waitcnt vmcnt(N) ; landed v[a:b] ...` (quads_landed) stands between such a load and a reader of its
+    registers.  For every `global_load_dwordx4 v[a:b]` inside ;;#ASMSTART / ;;#ASMEND of the assembly texts `asm`
+    ({source name: text}, as waitcnt_rows takes them) this walks forward in program text -- round the loop once where the walk
+    meets a branch back to the loop header -- to the `landed` wait that names v[a:b], and returns one string per instruction
+    on the way that names one of those registers (a register copy the compiler put there to merge two paths, say).  An empty
+    list is what the kernels rely on.  A load whose wait the walk does not find is reported too."""
+    import re
+    out = []
+    reg_re = re.compile(r'\bv\[(\d+):(\d+)\]|\bv(\d+)\b')
+
+    def regs(operand_text):
+        s = set()
+        for m in reg_re.finditer(operand_text):
+            if m.group(3) is not None:
+                s.add(int(m.group(3)))
+            else:
+                s.update(range(int(m.group(1)), int(m.group(2)) + 1))
+        return s
+
+    for text in asm.values():
+        lines = text.splitlines()
+        starts = [i for i, ln in enumerate(lines) if re.match(r'^_Z\w+:', ln)]
+        for fi, f0 in enumerate(starts):
+            f1 = starts[fi + 1] if fi + 1 < len(starts) else len(lines)
+            name = lines[f0].split(':')[0]
+            body = lines[f0:f1]
+            label_at = {m.group(1): k for k, ln in enumerate(body) for m in [re.match(r'^(\.LBB\d+_\d+):', ln)] if m}
+            header_of = {}
+            for k, ln in enumerate(body):
+                m = re.match(r'^(\.LBB\d+_\d+):(.*)$', ln)
+                if m:
+                    h = re.search(r'in Loop: Header=(BB\d+_\d+)', m.group(2))
+                    cur = '.L' + h.group(1) if h else (m.group(1) if 'Loop Header' in m.group(2) else None)
+                header_of[k] = cur if m else header_of.get(k - 1)
+            in_asm = False
+            for k, ln in enumerate(body):
+                s = ln.strip()
+                if s.startswith(';;#ASMSTART'):
+                    in_asm = True
+                elif s.startswith(';;#ASMEND'):
+                    in_asm = False
+                m = re.match(r'global_load_dwordx4\s+v\[(\d+):(\d+)\]', s) if in_asm else None
+                if not m:
+                    continue
+                tag = f'v[{m.group(1)}:{m.group(2)}]'
+                dst = set(range(int(m.group(1)), int(m.group(2)) + 1))
+                pos, wrapped, found, steps = k + 1, False, False, 0
+                while pos < len(body) and steps < 20000:
+                    steps += 1
+                    t = body[pos].strip()
+                    ins = t.split(';')[0].strip()
+                    if t.startswith('s_waitcnt') and 'landed' in t and tag in t:
+                        found = True
+                        break
+                    br = re.match(r's_c?branch\w*\s+(\.LBB\d+_\d+)', ins)
+                    if br and ins.startswith('s_branch') and not wrapped and header_of.get(k) is not None:
+                        # the back edge: an unconditional branch up to the header, or to a block of the same loop in front of it
+                        tgt = label_at.get(br.group(1), len(body))
+                        if tgt < pos and (br.group(1) == header_of[k] or header_of.get(tgt) == header_of[k]):
+                            pos, wrapped = tgt, True
+                            continue
+                    if ins and not ins.startswith('.') and not re.match(r'^\.?\w+:', ins):
+                        parts = ins.split(None, 1)
+                        ops = parts[1] if len(parts) > 1 else ''
+                        if regs(ops) & dst:      # a reader sees stale data, a writer is overwritten when the load lands
+                            out.append(f'{name}: `{ins}` touches {tag} before its wait')
+                    pos += 1
+                if not found:
+                    out.append(f'{name}: no `landed` wait for the load into {tag}')
+    return out
+
+
 def _summarise(out: str) -> str:
     """Condense -Rpass-analysis=kernel-resource-usage remarks to one line per kernel."""
     import re

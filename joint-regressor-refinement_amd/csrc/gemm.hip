@@ -670,8 +670,19 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * KS) void k_disc_gemm(GemmA
   float cscale = 0.f;                                        // dz of this lane's column (computed while the copies fly)
   if (BTR == 2) {
     const int n = n0 + wn * 32 + l31;
+    // the dot partials, sixteen at a time: ALL loads first, then the sum in the same order.  (A loop that loads and adds compiles
+    // to one load and one full wait per partial -- 16 dependent round trips in front of the first chunk.)  Rows past nzpart load
+    // row nzpart - 1 again and are not added: no branch around a load.
+    constexpr int ZP = 16;
     float z = g.zbias[0];
-    for (int t = 0; t < g.nzpart; ++t) z += g.zpart[(size_t)t * g.ldb + n];
+    for (int t0 = 0; t0 < g.nzpart; t0 += ZP) {
+      const int zlast = g.nzpart - 1 - t0;
+      float zp[ZP];
+#pragma unroll
+      for (int t = 0; t < ZP; ++t) zp[t] = g.zpart[(size_t)(t0 + (t < zlast ? t : zlast)) * g.ldb + n];
+#pragma unroll
+      for (int t = 0; t < ZP; ++t) z = t <= zlast ? z + zp[t] : z;
+    }
     const float sg = 1.f / (1.f + expf(-z));
     const bool ok = n < g.nvalid;
     const float up = g.gout ? (ok ? g.gout[(size_t)n * g.gout_ld] : 0.f) : g.scale * (sg - g.target);

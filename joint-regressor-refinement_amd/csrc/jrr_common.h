@@ -116,6 +116,38 @@ __device__ __forceinline__ void barrier_keep_vm() {
   asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
+// Register prefetch the compiler cannot drain: row quads loaded from inline asm (quad_load) and waited for by hand
+// (quads_landed<N>).  The compiler's own wait insertion stops counting wherever two paths into a block carry different
+// numbers of vector-memory operations, and beside an LDS-DMA in flight; it then emits vmcnt(0) in front of the first use --
+// which turns a prefetch issued a tile ahead into a load-and-wait.  It does not see a load issued from asm,
+// so it inserts nothing for it (and only ever waits LONGER for its own loads: what it does not know about is in flight on
+// top of what it counts).  The quads are "+v" operands of BOTH statements, so the loaded value has no reader the compiler
+// could place in front of the wait.  Rules for the caller: no branch between a load and its wait that would make the
+// compiler merge two values of the quad (it merges with a register copy, i.e. a read of a register still in flight) --
+// tests/test_waitcnt_codegen.py reads the assembly for that.
+template <bool NT>
+__device__ __forceinline__ void quad_load(f32x4& dst, unsigned lane_off_bytes, const float* base_uniform) {
+  if constexpr (NT) asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "+v"(dst) : "v"(lane_off_bytes), "s"(base_uniform) : "memory");
+  else asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(dst) : "v"(lane_off_bytes), "s"(base_uniform) : "memory");
+}
+// all but the N youngest vector-memory operations of this wave have retired, the six quads among them
+template <int N>
+__device__ __forceinline__ void quads_landed(f32x4 (&q)[3][2]) {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
+  asm volatile("s_waitcnt vmcnt(%6) ; landed %0 %1 %2 %3 %4 %5"      // the comment names the registers for the codegen test
+               : "+v"(q[0][0]), "+v"(q[0][1]), "+v"(q[1][0]), "+v"(q[1][1]), "+v"(q[2][0]), "+v"(q[2][1])
+               : "n"(N));
+}
+// the same for two sets of quads at once
+template <int N>
+__device__ __forceinline__ void quads_landed(f32x4 (&q)[3][2], f32x4 (&p)[3][2]) {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
+  asm volatile("s_waitcnt vmcnt(%12) ; landed %0 %1 %2 %3 %4 %5 %6 %7 %8 %9 %10 %11"
+               : "+v"(q[0][0]), "+v"(q[0][1]), "+v"(q[1][0]), "+v"(q[1][1]), "+v"(q[2][0]), "+v"(q[2][1]),
+                 "+v"(p[0][0]), "+v"(p[0][1]), "+v"(p[1][0]), "+v"(p[1][1]), "+v"(p[2][0]), "+v"(p[2][1])
+               : "n"(N));
+}
+
 // torch.optim.Adam, single-tensor formula: m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps),
 // bias corrections evaluated in double like torch's Python scalars
 struct AdamScalars { float step_size, bc2_sqrt, beta1, beta2, eps; };

@@ -965,15 +965,20 @@ __global__ __launch_bounds__(256, 2) void k_lbs_bwd16(const float* __restrict__ 
 
   // row quad (plane, tile, blk) of this lane: rows 32 vt + 16 blk + 4 g + 0..3 of its pose
   auto qidx = [&](int plane, int vt, int blk) { return ((size_t)plane * (VP / 4) + vt * 8 + 4 * blk + g) * BP + bcol; };
-  const f32x4* const VP4 = reinterpret_cast<const f32x4*>(VPb);
-  const f32x4* const dV4 = reinterpret_cast<const f32x4*>(dVT);
   f32x4* const DVP4 = reinterpret_cast<f32x4*>(DVP);
-  auto load_vp = [&](int vt, f32x4 (&dst)[3][2]) __attribute__((always_inline)) {
+  // The six row quads of a tile (v_posed, or the caller's vertex adjoint) go out from inline asm and are waited for by hand with a
+  // COUNTED vmcnt (jrr_common.h, quad_load / quads_landed): six vector-memory operations, in this order, behind whatever precedes
+  // the call.  The wave-uniform part of the address (plane, tile, blk) is the scalar base, the lane's part a 32-bit byte offset.
+  const unsigned quad_lane = (unsigned)(((size_t)g * BP + bcol) * 16);
+  auto load_quads = [&](const float* src, int vt, f32x4 (&dst)[3][2], auto nt) __attribute__((always_inline)) {
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
-      for (int blk = 0; blk < 2; ++blk) dst[c][blk] = __builtin_nontemporal_load(&VP4[qidx(c, vt, blk)]);   // read once: do not displace the operands in L2
+      for (int blk = 0; blk < 2; ++blk)
+        quad_load<decltype(nt)::value>(dst[c][blk], quad_lane, src + ((size_t)c * (VP / 4) + vt * 8 + 4 * blk) * BP * 4);
   };
+  // v_posed is read once: nt, it must not displace the operands in L2
+  auto load_vp = [&](int vt, f32x4 (&dst)[3][2]) __attribute__((always_inline)) { load_quads(VPb, vt, dst, std::true_type{}); };
 
   f32x4 acc[12];                                   // dA_{r,c} at 3 r + c (c < 3), dA_{r,3} at 9 + r: 16 window rows x 16 poses
 #pragma unroll
@@ -1007,6 +1012,13 @@ __global__ __launch_bounds__(256, 2) void k_lbs_bwd16(const float* __restrict__ 
         oldv[i][e] = add ? __hip_atomic_load(rowp[i] + (size_t)ent * NJ * BP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
       }
     }
+    // every read-back retires inside the flush, on every path (a row of a joint the window does not hold is loaded by no lane and
+    // stored by none): a load still pending where the flush joins the tile again costs the tile loop a vmcnt(0) in front of the next
+    // write of its register
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int e = 0; e < 12; ++e) asm volatile("" : "+v"(oldv[i][e]));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (jr[i] >= 0) {
@@ -1029,9 +1041,33 @@ __global__ __launch_bounds__(256, 2) void k_lbs_bwd16(const float* __restrict__ 
   };
 
   f32x4 vpA[3][2], vpB[3][2];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { vpA[c][0] = vpA[c][1] = zero4(); vpB[c][0] = vpB[c][1] = zero4(); }
   if (t_begin < t_end) load_vp(tile_of(t_begin), vpA);
+  // Everything the prologue loaded is retired HERE, where the compiler's wait insertion sees it: a load it still holds pending at the
+  // loop header cannot be counted inside the loop and costs a vmcnt(0) in front of its first reader in every tile.  The first tile
+  // needs all of it anyway (the A^T slice already went through registers into LDS above).
+  if (DV != 1) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int s5 = 0; s5 < 5; ++s5) asm volatile("" : "+v"(dj[r][s5]));
+  }
+  quads_landed<0>(vpA);
   int slot = 0;
-  auto tile = [&](int ix, const f32x4 (&vpc)[3][2], f32x4 (&vpn)[3][2]) __attribute__((always_inline)) {
+  // Vector-memory operations of one wave in issue order (ONE in-order counter for LDS-DMA, loads and stores); NA = 6 loads of the
+  // caller's adjoint if DV != 0, else none:
+  //   tile ix - 1:  barrier | DMA(ix + 1) x 0..2 | adjoint(ix - 1) x NA | v_posed(ix) x 6 | ... | dvp(ix - 1) x 6
+  //   tile ix    :  barrier | DMA(ix + 2) x 0..2 | adjoint(ix) x NA     | v_posed(ix + 1) x 6 | ...
+  //       wait for adjoint(ix): 6 younger                    (in front of the vertex-adjoint products)
+  //       wait for v_posed(ix): 6 + NA + 6 younger, + DMA    (in front of the dA products of plane 0)
+  //   ... | dvp(ix) x 6
+  // The prefetch is UNCONDITIONAL -- the last tile of a chunk loads itself again and nobody reads the result -- so both counts hold
+  // on every path without a branch around a wait.  The DMA pieces (wave 3 copies one fewer, the last two tiles none) and a
+  // flush (rare) only add operations younger than v_posed(ix); the count leaves them out, which in the steady state asks for the
+  // first two dvp stores of the previous tile, a whole tile old, as well.
+  constexpr int NA = (DV != 0) ? 6 : 0;
+  auto tile = [&](int ix, f32x4 (&vpc)[3][2], f32x4 (&vpn)[3][2]) __attribute__((always_inline)) {
     const int vt = tile_of(ix);
     // record vt has landed (it was issued two tiles ago: older than the 6 prefetch loads and the 6 dvp stores of the previous
     // tile, which stay in flight) and every wave is done with the slot the next copy overwrites
@@ -1040,16 +1076,13 @@ __global__ __launch_bounds__(256, 2) void k_lbs_bwd16(const float* __restrict__ 
     if (ix + 2 < t_end) issue(tile_of(ix + 2), slot2);
     __builtin_amdgcn_sched_barrier(0);
     const float* tab = ring + slot * R16_FLOATS;
-    if (ix + 1 < t_end) load_vp(tile_of(ix + 1), vpn);
     // ---- vertex adjoint of the tile: dverts_r = Jn^T dj_r and / or the caller's ----
     f32x4 dv[3][2];
 #pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int blk = 0; blk < 2; ++blk) dv[r][blk] = (DV != 0) ? dV4[qidx(r, vt, blk)] : zero4();
-    // all six loads of the caller's adjoint in flight before the first product that accumulates onto them: left to itself the scheduler
-    // starts the chain after four and issues the last two behind a full wait -- one more memory round trip per tile
-    if (DV == 2) __builtin_amdgcn_sched_barrier(0);
+    for (int r = 0; r < 3; ++r) dv[r][0] = dv[r][1] = zero4();
+    if (DV != 0) load_quads(dVT, vt, dv, std::false_type{});
+    load_vp(tile_of(ix + 1 < t_end ? ix + 1 : t_end - 1), vpn);
+    if (DV != 0) quads_landed<6>(dv);      // all six in flight together, the v_posed prefetch behind them stays in flight
     if (DV != 1) {
 #pragma unroll
       for (int s5 = 0; s5 < 5; ++s5)
@@ -1119,6 +1152,7 @@ __global__ __launch_bounds__(256, 2) void k_lbs_bwd16(const float* __restrict__ 
           t[i] = fmaf(T[2][blk][i], dv[2][blk][i], fmaf(T[1][blk][i], dv[1][blk][i], T[0][blk][i] * dv[0][blk][i]));
         __builtin_nontemporal_store(t, &DVP4[qidx(c, vt, blk)]);      // streamed (340 MB per launch): nt, measured -2.5 us
       }
+      if (c == 0) quads_landed<12 + NA>(vpc);      // first use of this tile's v_posed, loaded a tile ago
 #pragma unroll
       for (int blk = 0; blk < 2; ++blk)
 #pragma unroll
@@ -1128,9 +1162,14 @@ __global__ __launch_bounds__(256, 2) void k_lbs_bwd16(const float* __restrict__ 
     }
     slot = slot1;
   };
-  for (int ix = t_begin; ix < t_end; ix += 2) {
-    tile(ix, vpA, vpB);
-    if (ix + 1 < t_end) tile(ix + 1, vpB, vpA);
+  if (t_begin < t_end) {
+    for (int ix = t_begin; ix < t_end; ix += 2) {
+      tile(ix, vpA, vpB);
+      if (ix + 1 < t_end) tile(ix + 1, vpB, vpA);
+    }
+    // the last tile's prefetch, which nobody reads, has to land before its registers go to other uses: only that tile's six dvp
+    // stores are younger, and it is a whole tile old
+    quads_landed<6>(vpA, vpB);
   }
   flush_window();
   if (dmask) {      // one word per (chunk, 64-pose group)
