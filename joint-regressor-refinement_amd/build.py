@@ -210,6 +210,237 @@ def _waitcnt_parse(text: str):
     return rows
 
 
+def _device_asm(sources=None):
+    """{source name: device assembly text} of the CURRENT sources, compiled into a scratch directory"""
+    import shutil
+    import tempfile
+    tmp = tempfile.mkdtemp(prefix='jrr_asm_')
+    names = list(sources or SOURCES)
+    jobs = [[_hipcc()] + FLAGS + ['--cuda-device-only', '-S', os.path.join(CSRC, src), '-o', os.path.join(tmp, src.replace('.hip', '.s'))]
+            for src in names]
+    try:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), 8)) as ex:
+            outs = list(ex.map(lambda cmd: subprocess.run(cmd, capture_output=True, text=True), jobs))
+        asm = {}
+        for src, p in zip(names, outs):
+            if p.returncode != 0:
+                raise RuntimeError('hipcc failed:\n' + p.stderr[-2000:])
+            with open(os.path.join(tmp, src.replace('.hip', '.s'))) as f:
+                asm[src] = f.read()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    return asm
+
+
+def _demangled(mangled):
+    """{mangled: `jrr::k<0, 8, false>`} -- template arguments kept, parameter list and `void ` cut"""
+    mangled = sorted(set(mangled))
+    try:
+        dem = subprocess.run(['c++filt'], input='\n'.join(mangled), capture_output=True, text=True).stdout.splitlines()
+    except OSError:
+        dem = []
+    if len(dem) != len(mangled):
+        return {m: m for m in mangled}
+    table = {}
+    for m, full in zip(mangled, dem):
+        depth, cut = 0, len(full)
+        for i, ch in enumerate(full):
+            if ch == '<':
+                depth += 1
+            elif ch == '>':
+                depth -= 1
+            elif ch == '(' and depth == 0:
+                cut = i
+                break
+        table[m] = full[:cut].replace('void ', '', 1)
+    return table
+
+
+def _functions(text: str):
+    """(mangled name, [(kind, payload)]) per function of an assembly text, in program order: kind 'label' -> (label, rest of the line),
+    kind 'ins' -> (instruction without its comment, inside ;;#ASMSTART / ;;#ASMEND?)"""
+    import re
+    fn_re = re.compile(r'^(_Z\w+):')
+    lab_re = re.compile(r'^(\.LBB\d+_\d+):(.*)$')
+    lines = text.splitlines()
+    i = 0
+    while i < len(lines):
+        m = fn_re.match(lines[i])
+        i += 1
+        if not m:
+            continue
+        items, in_asm = [], False
+        while i < len(lines) and not lines[i].startswith('.Lfunc_end'):
+            ln = lines[i]
+            i += 1
+            lm = lab_re.match(ln)
+            if lm:
+                items.append(('label', (lm.group(1), lm.group(2))))
+                continue
+            s = ln.strip()
+            if s.startswith(';;#ASMSTART'):
+                in_asm = True
+            elif s.startswith(';;#ASMEND'):
+                in_asm = False
+            elif s and not s.startswith(';') and not s.startswith('.'):
+                ins = s.split(';')[0].strip()
+                if ins:
+                    items.append(('ins', (ins, in_asm)))
+        yield m.group(1), items
+
+
+def memory_rows(sources=None, asm=None):
+    """The memory instructions of every kernel of the CURRENT sources by kind (`asm`: {source name: assembly text} to parse instead).
+    One dict per kernel:
+        name      demangled kernel name with its template arguments
+        flat      flat_load / flat_store / flat_atomic: what an access through a pointer of unknown address space compiles to.  A flat
+                  instruction counts in lgkmcnt AS WELL AS vmcnt -- every LDS wait behind it also waits for its address phase
+        glob      global_load / global_store / global_atomic (LDS-DMA not included)
+        lds_dma   global_load_lds / buffer_load ... lds
+        lds       ds_read / ds_write
+        flat_text the flat instructions themselves
+    tests/test_stage_reads_codegen.py: no flat instruction in the kernels of the inner iteration."""
+    import re
+    if asm is None:
+        asm = _device_asm(sources)
+    rows = []
+    for text in asm.values():
+        for name, items in _functions(text):
+            r = {'name': name, 'flat': 0, 'glob': 0, 'lds_dma': 0, 'lds': 0, 'flat_text': []}
+            for kind, (ins, _) in items:
+                if kind != 'ins':
+                    continue
+                op = ins.split()[0]
+                if op.startswith('flat_'):
+                    r['flat'] += 1
+                    r['flat_text'].append(ins)
+                elif op.startswith('global_load_lds') or (op.startswith('buffer_load') and re.search(r'\blds\b', ins)):
+                    r['lds_dma'] += 1
+                elif op.startswith('global_') or op.startswith('buffer_'):
+                    r['glob'] += 1
+                elif op.startswith('ds_'):
+                    r['lds'] += 1
+            rows.append(r)
+    table = _demangled(r['name'] for r in rows)
+    for r in rows:
+        r['name'] = table[r['name']]
+    return rows
+
+
+def lds_wait_rows(sources=None, asm=None):
+    """How far ahead of its consumer an LDS read was issued, read from the device assembly of the CURRENT sources (`asm`: {source name:
+    assembly text} to parse instead): one dict per s_waitcnt THE COMPILER inserted inside a loop that has an lgkmcnt field and waits for
+    at least one ds_read:
+        name           demangled kernel name with its template arguments
+        loop           label of the header of the innermost loop around the wait
+        text           the instruction
+        lgkmcnt        the count it waits for
+        reads          ds_read instructions it waits for
+        ops            their opcodes, oldest first (ds_read_b128: a quad operand; ds_read_b32 / ds_read2st64_b32: single K steps)
+        mfma           matrix instructions issued between the OLDEST ds_read it waits for and the wait
+        mfma_youngest  ... between the YOUNGEST one and the wait
+    mfma == 0 is a read with prefetch distance zero: the wave requests its operand and waits for it with nothing of its own in the
+    matrix pipe.  The walk follows the program text; at a loop header it continues from the state at the loop's back edge (reads
+    issued at the end of an iteration and consumed at the start of the next are what a software pipeline looks like), so the rows
+    describe the steady state, not the first iteration.  A wait written in inline asm empties the queue and is not listed."""
+    import re
+    if asm is None:
+        asm = _device_asm(sources)
+    rows = []
+    for text in asm.values():
+        for name, items in _functions(text):
+            at_backedge, extents, label_at = {}, [], {}      # extents: (first, last item, header) of every backward branch
+            announced = any(kind == 'label' and 'Loop Header' in payload[1] for kind, payload in items)
+            for emit in (False, True):
+                queue, nm, loop = [], 0, None          # queue: (opcode of a ds_read / None, matrix instructions issued before it)
+                seen, fell = set(), True               # labels passed; the previous instruction falls through to the next one
+                for at, (kind, payload) in enumerate(items):
+                    if kind == 'label':
+                        label, note = payload
+                        seen.add(label)
+                        label_at[label] = at
+                        if 'Loop Header' in note:
+                            if not emit and fell and loop == label:      # a rotated loop: its last block stands in front of the header
+                                at_backedge[label] = (list(queue), nm)
+                            loop = label
+                            if label in at_backedge:
+                                q, n0 = at_backedge[label]
+                                queue = [(d, c - n0 + nm) for d, c in q]
+                        else:
+                            h = re.search(r'in Loop: Header=(BB\d+_\d+)', note)
+                            loop = '.L' + h.group(1) if h else None
+                        continue
+                    ins, ours = payload
+                    op = ins.split()[0]
+                    fell = op != 's_branch'
+                    if op.startswith('v_mfma'):
+                        nm += 1
+                    elif op.startswith('ds_read'):
+                        queue.append((op, nm))
+                    elif op.startswith('ds_') or op.startswith('s_load') or op.startswith('s_buffer_load') or op.startswith('flat_'):
+                        queue.append((None, nm))
+                    elif op == 's_waitcnt':
+                        m = re.search(r'lgkmcnt\((\d+)\)', ins)
+                        if m:
+                            keep = int(m.group(1))
+                            waited = queue[:len(queue) - keep] if keep else queue
+                            reads = [c for d, c in waited if d]
+                            ops = [d for d, c in waited if d]
+                            inside = loop
+                            if inside is None and not announced:      # a function whose loops the compiler's comments do not announce (an
+                                # irreducible loop): the text between a label and a branch back to it
+                                around = [e for e in extents if e[0] <= at <= e[1]]
+                                inside = min(around, key=lambda e: e[1] - e[0])[2] if around else None
+                            if emit and reads and not ours and inside is not None:
+                                rows.append({'name': name, 'loop': inside, 'text': ins, 'lgkmcnt': keep, 'reads': len(reads), 'ops': ops,
+                                             'mfma': nm - reads[0], 'mfma_youngest': nm - reads[-1]})
+                            queue = queue[len(queue) - keep:] if keep else []
+                    else:
+                        b = re.match(r's_c?branch\w*\s+(\.LBB\d+_\d+)', ins)
+                        if b and not emit and (b.group(1) in seen or b.group(1) == loop):      # a back edge
+                            at_backedge[b.group(1)] = (list(queue), nm)
+                            if b.group(1) in seen:
+                                extents.append((label_at[b.group(1)], at, b.group(1)))
+    table = _demangled(r['name'] for r in rows)
+    for r in rows:
+        r['name'] = table[r['name']]
+    return rows
+
+
+def overlapping_lds_reads(asm: dict):
+    """Two consecutive ds_read whose destination registers overlap, with a compiler s_waitcnt and no reader of the first one's
+    registers between them: the compiler narrowed a read whose upper part nobody uses and packed the next one into it, which costs a
+    full LDS round trip per read.  One string per pair found in the assembly texts `asm` ({source name: text}); an empty list is what
+    the kernels want."""
+    import re
+    out = []
+    dst_re = re.compile(r'^ds_read\w*\s+v(?:\[(\d+):(\d+)\]|(\d+))')
+    reg_re = re.compile(r'\bv\[(\d+):(\d+)\]|\bv(\d+)\b')
+    for text in asm.values():
+        for name, items in _functions(text):
+            prev, waits, used = None, 0, False       # the last ds_read: (text, lo, hi); compiler waits behind it; its registers named since
+            for kind, payload in items:
+                if kind == 'label':
+                    prev = None
+                    continue
+                ins, ours = payload
+                m = dst_re.match(ins)
+                if m:
+                    lo, hi = (int(m.group(3)),) * 2 if m.group(3) is not None else (int(m.group(1)), int(m.group(2)))
+                    if prev and waits and not used and lo <= prev[2] and prev[1] <= hi:
+                        out.append(f'{name}: `{prev[0]}` and `{ins}` overlap, separated by a wait only')
+                    prev, waits, used = (ins, lo, hi), 0, False
+                elif prev:
+                    if ins.startswith('s_waitcnt'):
+                        waits += 0 if ours else 1
+                    else:
+                        for r in reg_re.finditer(ins.split(None, 1)[1] if ' ' in ins else ''):
+                            a, b = (int(r.group(3)),) * 2 if r.group(3) is not None else (int(r.group(1)), int(r.group(2)))
+                            if a <= prev[2] and prev[1] <= b:
+                                used = True
+    return out
+
+
 def asm_load_hazards(asm: dict):
     """Loads issued from inline asm (csrc/jrr_common.h, quad_load) are invisible to the compiler's wait insertion: nothing but the
     hand-written `s_waitcnt vmcnt(N) ; landed v[a:b] ...` (quads_landed) stands between such a load and a reader of its

@@ -442,6 +442,7 @@ __global__ __launch_bounds__(256, 2) void k_blend_adjoint(const float* __restric
   int slot = 0;
   for (int ch = c_begin; ch < c_end; ++ch) {
     // this wave's copies of chunk ch have landed once at most the next chunk's are outstanding (6 for waves 0,1; 5 for 2,3)
+    // (the boundary stays BETWEEN the chunks here: inside quad pair 1, as in k_disc_gemm below, it measured 0.2695 -> 0.2827 ms)
     if (ch + 1 < c_end) {
       if (wave < 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
@@ -702,21 +703,37 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * KS) void k_disc_gemm(GemmA
   for (int a = 0; a < NACC; ++a)
 #pragma unroll
     for (int i = 0; i < WM; ++i) accs[a][i] = zero16();
-  int slot = 0;
-  for (int ch = 0; ch < nch; ++ch) {
-    if (ch + 1 < nch) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PA + PB) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (ch + 2 < nch) issue(ch + 2, slot >= 1 ? slot - 1 : 2);
-    const f32x4* la = reinterpret_cast<const f32x4*>(lds + slot * SLOT) + wm * WM * 32 + l31;
-    const f32x4* lb = reinterpret_cast<const f32x4*>(lds + slot * SLOT + SA) + wn * 32 + l31;
-    slot = (slot == 2) ? 0 : slot + 1;
-    constexpr int GQ = 4 / KS;                            // quad pairs of a chunk this wave multiplies: ks GQ .. ks GQ + GQ - 1
-    const int gq0 = ks * GQ;
-    f32x4 a4[WM], b4;
+  // The chunk boundary sits INSIDE the last quad pair of a chunk, where a pair boundary would sit: behind that pair's first matrix
+  // instruction (every LDS read of chunk ch by this wave has been consumed by then) comes the wait + barrier for chunk ch + 1, then
+  // the first operand reads of chunk ch + 1 into the free register set, then the copies of chunk ch + 3 into the slot chunk ch has
+  // just vacated -- and the rest of the pair's matrix instructions cover the reads.  (With the boundary between the chunks the wave
+  // did barrier, copies, reads, full LDS wait with nothing of its own in the matrix pipe, once per chunk.)
+  // vmcnt at the boundary: this wave's vector-memory operations retire in issue order and the loop issues nothing but copies, so the
+  // youngest PA + PB are the copies of chunk ch + 2 (issued at the previous boundary) and everything older -- chunk ch + 1 -- has
+  // landed at vmcnt(PA + PB); the last boundary has no chunk ch + 2 in flight and drains.  (The BTR = 2 prologue's two stores are
+  // younger than the copies of chunks 0 and 1: they only make the first two waits stricter.)
+  constexpr int GQ = 4 / KS;                              // quad pairs of a chunk this wave multiplies: ks GQ .. ks GQ + GQ - 1
+  const int gq0 = ks * GQ;
+  const int lao = wm * WM * 32 + l31, lbo = wn * 32 + l31;
+  f32x4 a4[WM], b4;
+  {
+    if (1 < nch) barrier_keep_vm<PA + PB>();
+    else barrier_keep_vm<0>();
+    if (2 < nch) issue(2, 2);
+    const f32x4* la = reinterpret_cast<const f32x4*>(lds) + lao;
+    const f32x4* lb = reinterpret_cast<const f32x4*>(lds + SA) + lbo;
 #pragma unroll
     for (int i = 0; i < WM; ++i) a4[i] = la[(2 * gq0 + half) * BM + 32 * i];
     b4 = lb[(2 * gq0 + half) * BN];
+  }
+  // (the last chunk has no boundary and is written out behind the loop: a branch around the boundary made the compiler merge the two
+  // paths' operand registers with a copy, i.e. a full LDS wait directly behind the reads)
+  int slot = 0, ch = 0;
+  auto chunk = [&](auto LAST_) __attribute__((always_inline)) {
+    constexpr bool LAST = decltype(LAST_)::value;
+    const f32x4* la = reinterpret_cast<const f32x4*>(lds + slot * SLOT) + lao;
+    const f32x4* lb = reinterpret_cast<const f32x4*>(lds + slot * SLOT + SA) + lbo;
+    const int nslot = (slot == 2) ? 0 : slot + 1;
 #pragma unroll
     for (int gq = 0; gq < GQ; ++gq) {
       f32x4 ca[WM], cb;
@@ -732,6 +749,16 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * KS) void k_disc_gemm(GemmA
 #pragma unroll
         for (int i = 0; i < WM; ++i) a4[i] = la[(2 * (gq0 + gq) + 2 + half) * BM + 32 * i];
         b4 = lb[(2 * (gq0 + gq) + 2 + half) * BN];
+      } else if (!LAST) {
+        if (ch + 2 < nch) barrier_keep_vm<PA + PB>();
+        else barrier_keep_vm<0>();
+        const f32x4* na = reinterpret_cast<const f32x4*>(lds + nslot * SLOT) + lao;
+        const f32x4* nb = reinterpret_cast<const f32x4*>(lds + nslot * SLOT + SA) + lbo;
+#pragma unroll
+        for (int i = 0; i < WM; ++i) a4[i] = na[(2 * gq0 + half) * BM + 32 * i];
+        b4 = nb[(2 * gq0 + half) * BN];
+        __builtin_amdgcn_sched_barrier(0);
+        if (ch + 3 < nch) issue(ch + 3, slot);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -740,7 +767,10 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * KS) void k_disc_gemm(GemmA
         for (int i = 0; i < WM; ++i)
           if (t + i > 0) acc[i] = mfma(ca[i][t], cb[t], acc[i]);
     }
-  }
+    slot = nslot;
+  };
+  for (; ch + 1 < nch; ++ch) chunk(std::false_type{});
+  if (ch < nch) chunk(std::true_type{});
   f32x16 (&acc)[WM] = accs[0];
   if (KS == 1) {
 #pragma unroll
@@ -770,27 +800,42 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N * KS) void k_disc_gemm(GemmA
   // have left), so that the group's partial is bit-identical whatever the tile shape
   constexpr bool DOT_CHAIN = EPI == EPI_BIAS_RELU_DOT && WM == 1 && WAVES_M == 2 && WAVES_N == 1;
   float* const dotx = lds + 2 * (WM * 16 * 64) + 1024;      // behind the K-split reduction's slots
+  // ALL bias / dot-weight / mask quads of the wave's WM x 4 output quads are requested first: the stores below may alias them for all
+  // the compiler knows, so loads written beside their use compile to one load and one full wait per output quad -- WM x 4 dependent
+  // round trips at the tail of the launch, with nothing else left to run.  Tiles are exact: no branch goes around a load.
+  // (fenced: scheduled among the accumulator sums above, the loads came out in two batches with a full wait between them)
+  f32x4 bbq[WM][4], dwq[WM][4], mkq[WM][4];
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int i = 0; i < WM; ++i)
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+      const int r0u = m0 + (wm * WM + i) * 32 + 8 * q4, r0 = r0u + 4 * half;
+      if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_RELU_DOT) bbq[i][q4] = *reinterpret_cast<const f32x4*>(g.bias + r0);
+      if (EPI == EPI_BIAS_RELU_DOT) dwq[i][q4] = *reinterpret_cast<const f32x4*>(g.dotw + r0);
+      if (EPI == EPI_MASK) mkq[i][q4] = reinterpret_cast<const f32x4*>(g.mask)[(size_t)(r0u / 4 + half) * g.ldo + n];
+    }
+  __builtin_amdgcn_sched_barrier(0);
   if (DOT_CHAIN && wm == 1) { __syncthreads(); dot = dotx[lane]; }
 #pragma unroll
   for (int i = 0; i < WM; ++i)
 #pragma unroll
     for (int q4 = 0; q4 < 4; ++q4) {
       const int r0u = m0 + (wm * WM + i) * 32 + 8 * q4;            // wave-uniform part of the row
-      const int r0 = r0u + 4 * half;
       f32x4 v = {acc[i][4 * q4], acc[i][4 * q4 + 1], acc[i][4 * q4 + 2], acc[i][4 * q4 + 3]};
       if (EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_RELU_DOT) {
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(g.bias + r0);
+        const f32x4 bb = bbq[i][q4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) v[u] = fmaxf(v[u] + bb[u], 0.f);
       }
       if (EPI == EPI_BIAS_RELU_DOT) {
-        const f32x4 dw = *reinterpret_cast<const f32x4*>(g.dotw + r0);
+        const f32x4 dw = dwq[i][q4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) dot = fmaf(dw[u], v[u], dot);
       }
       const size_t qi = ((size_t)(r0u / 4 + half) * g.ldo + n);     // quad index of (row r0, column n)
       if (EPI == EPI_MASK) {
-        const f32x4 mk = reinterpret_cast<const f32x4*>(g.mask)[qi];
+        const f32x4 mk = mkq[i][q4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) v[u] = (mk[u] > 0.f) ? (BTR == 2 ? v[u] * cscale : v[u]) : 0.f;
       }

@@ -61,35 +61,39 @@ __device__ __forceinline__ int xcd_remap(int id, int n) {
 // tools/probe/dma_probe.hip).  No VGPR round trip; completion is tracked by vmcnt.
 #define JRR_LDS(p) ((__attribute__((address_space(3))) void*)(p))
 #define JRR_GLB(p) ((const __attribute__((address_space(1))) void*)(p))
+// A pointer the compiler KNOWS to be global memory.  The `asm volatile("" : "+s"(p))` that pins a row base to an SGPR pair also hides
+// where the pointer came from: an access through it compiles to flat_* -- which counts in lgkmcnt as well as vmcnt, so every LDS wait
+// behind it waits for the store's address phase too -- unless the pointer carries the address space again.
+#define JRR_GPTR(T) __attribute__((address_space(1))) T*
 
 // Row pointer of a [rows][BP] array for a WAVE-UNIFORM row, kept in an SGPR pair: the access is then
 // `global_* v_lane_offset, v_data, s[row]` (scalar address arithmetic) instead of five VALU instructions, two of
 // them quarter-rate 64-bit multiplies, per element.  The per-lane part (4 * half rows + pose column) is a
-// loop-invariant 32-bit offset.
-__device__ __forceinline__ float* urow(float* base, size_t row, int BP) {
+// loop-invariant 32-bit offset.  (Returned as a global-address-space pointer: JRR_GPTR.)
+__device__ __forceinline__ JRR_GPTR(float) urow(float* base, size_t row, int BP) {
   float* p = base + row * (size_t)BP;
   asm volatile("" : "+s"(p));
-  return p;
+  return (JRR_GPTR(float))p;
 }
-__device__ __forceinline__ const float* urow(const float* base, size_t row, int BP) {
+__device__ __forceinline__ JRR_GPTR(const float) urow(const float* base, size_t row, int BP) {
   const float* p = base + row * (size_t)BP;
   asm volatile("" : "+s"(p));
-  return p;
+  return (JRR_GPTR(const float))p;
 }
 // "Row-quad" layout of the per-vertex arrays that only travel between the LBS kernels (v_posed):
 //     element (row v, pose b) of plane c lives at  ((c * VP/4 + v/4) * BP + b) * 4 + v % 4.
 // Registers 4g .. 4g+3 of a lane of the accumulator layout are the rows 8g + 4 half + {0,1,2,3} = ONE row quad
 // (index 2g + half) of that lane's pose, i.e. 16 contiguous bytes: a tile moves as four dwordx4 per lane (a wave
 // instruction = two contiguous 512-byte runs) instead of sixteen dword accesses.
-__device__ __forceinline__ f32x4* quad_ptr(float* base, size_t plane_quad0, int g, int BP, unsigned lane_q) {
+__device__ __forceinline__ JRR_GPTR(f32x4) quad_ptr(float* base, size_t plane_quad0, int g, int BP, unsigned lane_q) {
   float* p = base + ((plane_quad0 + 2 * g) * (size_t)BP) * 4;
   asm volatile("" : "+s"(p));
-  return reinterpret_cast<f32x4*>(p) + lane_q;
+  return (JRR_GPTR(f32x4))p + lane_q;
 }
-__device__ __forceinline__ const f32x4* quad_ptr(const float* base, size_t plane_quad0, int g, int BP, unsigned lane_q) {
+__device__ __forceinline__ JRR_GPTR(const f32x4) quad_ptr(const float* base, size_t plane_quad0, int g, int BP, unsigned lane_q) {
   const float* p = base + ((plane_quad0 + 2 * g) * (size_t)BP) * 4;
   asm volatile("" : "+s"(p));
-  return reinterpret_cast<const f32x4*>(p) + lane_q;
+  return (JRR_GPTR(const f32x4))p + lane_q;
 }
 // uniform part of acc_row(q, half) = (q & 3) + 8 (q >> 2) + 4 half
 __device__ __forceinline__ constexpr int acc_row_u(int q) { return (q & 3) + 8 * (q >> 2); }

@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void k_lbs_fwd(const float* __restrict__ Dk
     const unsigned lo = ((unsigned)b0 + (unsigned)(ln & 31)) * (3u * VP) + 4u * (unsigned)(ln >> 5);
     float* base = VTb + ((size_t)r * VP + vt * 32 + 8 * g4);
     asm volatile("" : "+s"(base));
-    *reinterpret_cast<f32x4*>(base + lo) = t;
+    *(JRR_GPTR(f32x4))(base + lo) = t;
   };
   const int t_first = (t_begin < t_end) ? (LIST ? tl[t_begin] : t_begin) : 0;
   if (SPARSE && WIDE && t_begin < t_end) wide_next = tnj[t_first] > KJS;
@@ -304,6 +304,11 @@ __global__ __launch_bounds__(256, 2) void k_lbs_fwd(const float* __restrict__ Dk
         // 4 LDS reads per 12 matrix instructions instead of 16.  The last chunk holds k = 192 .. 217: its group 3 has only the
         // steps t = 0, 1 (k = 216, 217 against zero rows).  Operands of group g + 1 are requested right after the first
         // instruction of group g.
+        // (Entering stage s + 1 INSIDE the last group of stage s -- barrier, first operand reads and the copies of stage s + 2 behind
+        // the group's first instruction, so that its other eleven cover the reads -- was built and measured SLOWER, 0.3527 -> 0.3610
+        // ms: the barrier then asks for the next stage's copies eleven instructions earlier, a quarter of the one stage the 2-deep ring
+        // gives them.  Reading group 3 of the last chunk (two live steps) as four 8-byte reads, instead of the 16-byte reads the compiler
+        // narrows into overlapping registers with a wait between each two, was measured too: 0.3507 -> 0.3520 ms.  DESIGN.md section 8.)
         constexpr int ngroups = 4;
         const f32x4* dq = reinterpret_cast<const f32x4*>(buf) + half * 96 + l31;                          // quad q, plane c: + (q * 3 + c) * 32
         const f32x4* fq = reinterpret_cast<const f32x4*>(buf + KCH * 96) + half * BG + wave * BT + l31;   // quad q: + q * 128
