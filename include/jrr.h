@@ -180,6 +180,26 @@ enum {
   JRR_ACCEL_ACC_TRAILER = 2         /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
 };
 
+/* jrr_vertex_error: the per-vertex error of meshes, and the row of its group table: JRR_PVE_ACC_ROW int64 per group, offsets in
+ * int64, then the trailer of the evaluation table behind the last row.  Layout version 1.
+ * Overflow: a value below the cap 1.0e3f gives llrintf(v * 2^24) < 2^34, so a sum stays below 2^63 for 5e8 poses in one word. */
+enum {
+  JRR_PVE_ACC_LAYOUT_VERSION = 1,
+  JRR_PVE_MAX_VERTS = 65536,        /* 1 <= n_verts <= 65536 */
+  JRR_PVE_MAX_PARTS = 32,           /* 1 <= n_parts <= 32 */
+  JRR_PVE_ACC_ROW = 370,
+  JRR_PVE_ACC_COUNT = 0,            /* poses counted */
+  JRR_PVE_ACC_BAD = 1,              /* poses of this group left out: pve or pa_pve is NaN */
+  JRR_PVE_ACC_SUM = 2,              /* sum over the poses of llrintf(pve * 2^24) (units of 2^-24 m) */
+  JRR_PVE_ACC_SUM_PA = 3,           /* the same for pa_pve */
+  JRR_PVE_ACC_HIST = 4,             /* 151: histogram of the PER-POSE pve, bin min((int)floorf(pve * 1000.f), 150): the bins of JRR_EVAL_ACC_HIST */
+  JRR_PVE_ACC_HIST_PA = 155,        /* 151: the same for pa_pve */
+  JRR_PVE_ACC_PART = 306,           /* 32: sum over the poses of llrintf(m_p * 2^24), m_p the pose's mean plain error over part p */
+  JRR_PVE_ACC_PART_PA = 338,        /* 32: the same for the aligned error */
+  JRR_PVE_ACC_BINS = 151,
+  JRR_PVE_ACC_TRAILER = 2           /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
+};
+
 #define JRR_FLAG_SIL_SIZE(size) ((((size) / 32) & 15) << 16)
 
 typedef struct jrr_model jrr_model_t;   /* device-resident, re-laid-out SMPL constants */
@@ -632,6 +652,42 @@ int jrr_eval_accumulate(const float* err_j_dev, const float* err_pa_j_dev, const
 int jrr_accel_error(const float* pred_dev, const float* gt_mm_dev, int64_t n_rows, const int32_t* order_dev, const int32_t* run_dev,
                     const int32_t* group_dev, int m, int begin, int count, int n_groups, float* err_j_dev, float* acc_pred_j_dev,
                     float* acc_gt_j_dev, int64_t* acc_dev, int32_t* status_dev, void* stream);
+
+/* The per-vertex error of meshes (`--eval_pve`): PVE / MPVPE and its Procrustes-aligned form PA-PVE, the fourth column mesh-recovery
+ * papers print.  pred_dev and gt_dev are (batch,n_verts,3) fp32 METRES, both; root_pred_dev / root_gt_dev (batch,3) or NULL (zero) are
+ * subtracted first; 1 <= n_verts <= JRR_PVE_MAX_VERTS.  Per pose b, every fp32 operation rounded once in the order written, no product
+ * fused into a sum:
+ *   x_i = P_i - root_pred, y_i = Q_i - root_gt;  d_i = sqrtf((dx dx + dy dy) + dz dz) of x_i - y_i.
+ *   Procrustes (scripts/eval_utils.py:7-58 of the reference on all vertices): from the fp32 x_i, y_i IN DOUBLE the means mu1, mu2, then
+ *   K = sum (x_i - mu1)(y_i - mu2)^T and var1 = sum ((a0 a0 + a1 a1) + a2 a2), a = x_i - mu1, about the double means.  The order of
+ *   the double sums is a function of n_verts alone (vertex i belongs to thread i mod 256, which adds its vertices in ascending order;
+ *   the 64 sums of a wave are combined by an xor butterfly over lane distances 32, 16, ..., 1; the 4 wave sums are added in wave
+ *   order).  mu1, mu2, K, var1 are each rounded to fp32; the rotation, scale = trace(R K) / var1 and t = mu2 - scale R mu1 are those
+ *   of jrr_evaluate, statement by statement (one-sided Jacobi on K, six sweeps, the sort, the rank-1 and rank-0 rules);
+ *   e_i = |scale R x_i + t - y_i|, h_r = scale * ((R_r0 x_0 + R_r1 x_1) + R_r2 x_2) + t_r.  A constant target gives e_i == 0 exactly; a
+ *   constant pred (also n_verts == 1) gives NaN in e only.
+ *   q_i = llrintf(d_i * 2^24), S = sum q_i (int64, exact), pve = (float)((double)S / ((double)n_verts * 16777216.0)); pve = NaN when
+ *   a d_i fails d_i < 1.0e3f.  The same on e_i gives pa_pve.
+ *   pve_dev, pa_pve_dev   (batch) fp32 metres, each may be NULL
+ *   err_v_dev, err_pa_v_dev   (batch,n_verts) fp32: d_i, e_i as computed, each may be NULL
+ *   acc_dev     NULL, or int64 [n_groups][JRR_PVE_ACC_ROW] + JRR_PVE_ACC_TRAILER words, layout above, to which the call ADDS its poses
+ *               by group_dev (batch) int32 (NULL: every pose in group 0); the caller zeroes it once per report.  group < 0 counts in
+ *               trailer word 0 only, group >= n_groups in trailer word 1 only.  Otherwise: a pose with either mean NaN adds BAD += 1 and
+ *               nothing else; else COUNT += 1, SUM += llrintf(pve * 2^24), SUM_PA likewise, HIST[min((int)floorf(pve * 1000.f), 150)]
+ *               += 1, HIST_PA likewise, and per part p with part_dev (n_verts) int32 labels given, 1 <= n_parts <= JRR_PVE_MAX_PARTS:
+ *               PART[p] += llrintf(m_p * 2^24), m_p = (float)((double)(sum of q_i over part_dev[i] == p) / ((double)n_p * 16777216.0)),
+ *               n_p the part's vertex count; PART_PA likewise.  Empty parts and labels outside [0, n_parts) add nothing.
+ *   acc_v_dev   NULL, or int64 [2][n_verts], to which the call ADDS q_i (plain, then aligned) of every counted pose: one whose means
+ *               are both no NaN and whose group lies in [0, n_groups) (group_dev NULL: every such pose).
+ * Integer atomics only: the tables are a function of the multiset of (pose, group) pairs -- not of the order, the split into calls or
+ * the sharding over ranks (sum the ranks' tables).  A pose's outputs do not depend on batch or on its place in the batch.
+ * batch == 0 returns JRR_OK without a launch.  JRR_ERR_ARG with a message, nothing touched: a NULL pred / gt, all six outputs NULL,
+ * batch < 0, n_verts out of range, part_dev without 1 <= n_parts <= 32, n_groups outside 1 .. JRR_EVAL_ACC_MAX_GROUPS with acc_dev (or
+ * with acc_v_dev and group_dev), a misaligned array (4 bytes; acc_dev, acc_v_dev 8).  Touches no engine and no body model.       */
+int jrr_vertex_error(const float* pred_dev, const float* gt_dev, const float* root_pred_dev, const float* root_gt_dev,
+                     const int32_t* group_dev, const int32_t* part_dev, int n_parts, int batch, int n_verts, int n_groups,
+                     float* pve_dev, float* pa_pve_dev, float* err_v_dev, float* err_pa_v_dev, int64_t* acc_dev, int64_t* acc_v_dev,
+                     void* stream);
 
 /* ---- regressor report (`--regressor_report`): how far the retrained regressor moved each joint, and discs on a picture ------
  * No reference counterpart in code: the reference's teaser.png shows the joints of the accepted regressor, of the retrained one and

@@ -79,6 +79,7 @@ SIGNATURES = {
     'jrr_regress_joints': (c_int, [_P, c_int, _P, c_int, _P, _P]),
     'jrr_eval_accumulate': (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     'jrr_accel_error': (c_int, [_P, _P, ctypes.c_int64, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
+    'jrr_vertex_error': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     'jrr_regressor_shift_accumulate': (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     'jrr_draw_discs': (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, _P, c_int, c_int, _P]),
     'jrr_project_joints': (c_int, [_P, _P, _P, c_int, _P]),

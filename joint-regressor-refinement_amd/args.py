@@ -132,6 +132,14 @@ def build_parser() -> argparse.ArgumentParser:
                              'acceleration error of both regressors\' joints along each video sequence -- per run of consecutive frames of '
                              'one camera, from the frame paths (images.pkl; paths.txt) -- in mm per sampled frame^2 (accel_report.py); with '
                              '--smooth_refined / --fuse_refined: the per-sample accel_err_mm_* arrays of the raw and the processed rows')
+    parser.add_argument('--eval_pve', action='store_true',
+                        help='with --eval_vertices DIR --eval_report OUT: also write OUT/pve.json, OUT/pve.md and OUT/pve_per_vertex.npy, the '
+                             'per-vertex error (PVE / MPVPE) and its Procrustes-aligned form of the meshes of DIR/vertices.npy against '
+                             'DIR/gt_vertices.npy ((N,6890,3) float32 m), both centred at joint 0 of the initial regressor, per group, per '
+                             'pose percentile and per vertex (vertex_report.py); no joint regressor is scored')
+    parser.add_argument('--eval_pve_parts', action='store_true',
+                        help='with --eval_pve: per-part means as well, a vertex belonging to the SMPL joint with its largest skinning weight; '
+                             'needs the body model (--smpl_dir, or the synthetic one under --synthetic)')
     parser.add_argument('--regressor_report', type=str, default=None, metavar='DIR',
                         help='regressor report: DIR/regressor.json and DIR/regressor.md -- per H36M joint the support of the initial and '
                              'the retrained regressor and how far, in a frame fixed to the body, the retrained one moves the joint on the '

@@ -905,6 +905,42 @@ def accel_error(pred: torch.Tensor, gt_mm: torch.Tensor, order: torch.Tensor, ru
     return out
 
 
+PVE_ACC_ROW, PVE_ACC_TRAILER, PVE_MAX_PARTS, PVE_MAX_VERTS = 370, 2, 32, 65536      # include/jrr.h: JRR_PVE_ACC_ROW, JRR_PVE_ACC_TRAILER, ...
+
+
+def vertex_error(pred: torch.Tensor, gt: torch.Tensor, root_pred: Optional[torch.Tensor] = None, root_gt: Optional[torch.Tensor] = None,
+                 group: Optional[torch.Tensor] = None, part: Optional[torch.Tensor] = None, n_parts: int = 0, n_groups: int = 1,
+                 acc: Optional[torch.Tensor] = None, acc_v: Optional[torch.Tensor] = None, means: bool = True, rows: bool = True):
+    """jrr_vertex_error: the per-vertex error of meshes `pred` against `gt`, (B,n_verts,3) fp32 METRES both, after subtracting
+    root_pred / root_gt (B,3; None: zero).  Returns (pve, pa_pve, err_v, err_pa_v): (B,) per-pose means in metres (means=False: None,
+    None) and the (B,n_verts) distances (rows=False: None, None).  acc: the int64 group table (n_groups * 370 + 2 words, include/jrr.h
+    JRR_PVE_ACC_*) the poses are ADDED to by `group` (B, int32; None: group 0), with per-part sums when `part` (n_verts, int32 labels
+    in [0, n_parts)) is given; acc_v: the int64 (2,n_verts) per-vertex table the counted poses are ADDED to."""
+    lib = _lib.load()
+    dev = pred.device
+    B, n = int(pred.shape[0]), int(pred.shape[1])
+    assert pred.shape == (B, n, 3) and gt.shape == (B, n, 3) and pred.dtype == torch.float32 and gt.dtype == torch.float32
+    assert pred.is_contiguous() and gt.is_contiguous() and gt.device == dev
+    for r in (root_pred, root_gt):
+        assert r is None or (r.shape == (B, 3) and r.dtype == torch.float32 and r.is_contiguous() and r.device == dev)
+    if group is not None:
+        assert group.shape == (B,) and group.dtype == torch.int32 and group.is_contiguous() and group.device == dev
+    if part is not None:
+        assert part.shape == (n,) and part.dtype == torch.int32 and part.is_contiguous() and part.device == dev
+    if acc is not None:
+        assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.device == dev
+        assert acc.numel() == int(n_groups) * PVE_ACC_ROW + PVE_ACC_TRAILER
+    if acc_v is not None:
+        assert acc_v.dtype == torch.int64 and acc_v.is_contiguous() and acc_v.device == dev and acc_v.shape == (2, n)
+    pve, pa = (torch.empty(B, device=dev), torch.empty(B, device=dev)) if means else (None, None)
+    ev, epa = (torch.empty(B, n, device=dev), torch.empty(B, n, device=dev)) if rows else (None, None)
+    if B == 0:                                      # an empty tensor has no address to pass
+        return pve, pa, ev, epa
+    check(lib.jrr_vertex_error(ptr(pred), ptr(gt), ptr(root_pred), ptr(root_gt), ptr(group), ptr(part), int(n_parts), B, n, int(n_groups),
+                               ptr(pve), ptr(pa), ptr(ev), ptr(epa), ptr(acc), ptr(acc_v), stream_ptr(dev)), 'vertex_error')
+    return pve, pa, ev, epa
+
+
 SHIFT_ACC_ROW, SHIFT_ACC_TRAILER = 1277, 2      # include/jrr.h: JRR_SHIFT_ACC_ROW, JRR_SHIFT_ACC_TRAILER
 DISCS_MAX_SETS, DISCS_MAX_POINTS = 8, 256       # include/jrr.h: JRR_DISCS_MAX_SETS, JRR_DISCS_MAX_POINTS
 

@@ -14,7 +14,8 @@ on a CPU tensor table with a gloo group as well.
 (/root/reference/scripts/test.py:141-301 test_pose_refiner_model_VIBE_MEVA and the METRO block :362-373 do `relu(J) / rowsum`,
 `J @ pred_vertices`, `evaluate` on another model's vertices) -- `vertices.npy` (N,6890,3) float32 metres, `gt_j3d.npy` (N,17,3) mm,
 optionally `paths.txt` or `group.npy` + `group_names.txt` -- through jrr_regress_joints with both regressors on one read of the
-vertices.  No SMPL model file, no engine.
+vertices.  No SMPL model file, no engine.  `--eval_pve` adds the per-vertex error of the same meshes against `gt_vertices.npy`
+(vertex_report.py): one more launch per chunk, one more all-reduce at the end, and the files above keep their contents.
 """
 from __future__ import annotations
 
@@ -273,15 +274,24 @@ def open_vertices_dir(directory: str, kind: str = 'action'):
 
 def evaluate_vertices(log=print) -> Optional[dict]:
     """`--eval_vertices DIR --eval_report OUT`: rank r takes shard_bounds(N, r, world) of the meshes in chunks of --batch_size
-    (pinned uploads), both regressors on one read of the vertices, one all-reduce per report at the end."""
-    from . import accel_report, checkpoint, engine as _engine, regressor_report, smpl_model, utils
+    (pinned uploads), both regressors on one read of the vertices, one all-reduce per report at the end.  `--eval_pve`: the target
+    meshes of gt_vertices.npy ride the same loop on a third pinned buffer into vertex_report.VertexReport."""
+    from . import accel_report, checkpoint, engine as _engine, regressor_report, smpl_model, utils, vertex_report
     from .args import args
     if not args.eval_report and not args.regressor_report:
         raise ValueError('--eval_vertices needs --eval_report or --regressor_report DIR (where eval.json / eval.md, regressor.json / '
                          'regressor.md go)')
     regressor_report.check_flags(args._get())
     accel_report.check_flags(args._get())
+    vertex_report.check_flags(args._get())
     verts, gt, names, ids = open_vertices_dir(args.eval_vertices, args.eval_groups)          # before any launch
+    gt_verts = vertex_report.open_gt_vertices(args.eval_vertices, verts.shape[0]) if args.eval_pve else None
+    part_np = None
+    if args.eval_pve and args.eval_pve_parts:      # the body model as --regressor_report resolves it; every rank labels the vertices alike
+        model_parts = regressor_report.resolve_body_model(args.smpl_dir, args.synthetic)
+        if model_parts is None:
+            raise ValueError('--eval_pve_parts needs the body model: --smpl_dir with SMPL_NEUTRAL.npz / .pkl, or --synthetic')
+        part_np = vertex_report.part_labels(model_parts['lbs_weights'])
     accel_paths = accel_report.read_paths(args.eval_vertices, verts.shape[0]) if args.eval_accel else None
     jdist.init(args.dist_backend)
     rank, local_rank, world = jdist.env_rank_world()
@@ -299,10 +309,13 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     shift = regressor_report.Run(args._get(), names, device, J_np, J_after.cpu().numpy(), mask_np, 'vertices') if args.regressor_report else None
     N = verts.shape[0]
     track = accel_report.JointTrack(N, 2, device) if accel_paths is not None else None
+    pve = vertex_report.VertexReport(names, device, 6890, part_np, 0 if part_np is None else model_parts['lbs_weights'].shape[1]) if gt_verts is not None else None
+    root_table = _engine.JointRegressorTable(Js[:1], utils.find_j_reg_mask(Js[0])) if pve is not None else None      # joint 0 of the INITIAL regressor centres both meshes
     lo, hi = jdist.shard_bounds(N, rank, world)
     bs = max(1, int(args.batch_size))
     stage = [(torch.empty((bs, 6890, 3), dtype=torch.float32).pin_memory(), torch.empty((bs, NJ, 3), dtype=torch.float32).pin_memory(),
               torch.empty((bs,), dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(2)]
+    stage_gt = [torch.empty((bs, 6890, 3), dtype=torch.float32).pin_memory() for _ in range(2)] if pve is not None else None      # --eval_pve: the third pinned buffer
     used = [False, False]
     with torch.no_grad():
         for k, a in enumerate(range(lo, hi, bs)):
@@ -315,6 +328,9 @@ def evaluate_vertices(log=print) -> Optional[dict]:
             pg.numpy()[:n] = gt[a:b]
             pi.numpy()[:n] = ids[a:b]
             dv, dg, di = (t[:n].to(device, non_blocking=True) for t in (pv, pg, pi))
+            if pve is not None:
+                stage_gt[k % 2].numpy()[:n] = gt_verts[a:b]
+                dq = stage_gt[k % 2][:n].to(device, non_blocking=True)
             ev.record()
             used[k % 2] = True
             joints = table.regress(dv)
@@ -326,6 +342,8 @@ def evaluate_vertices(log=print) -> Optional[dict]:
                 track.add(np.arange(a, b), (joints[0], joints[1]), gtc)
             if shift is not None:
                 shift.add(dv, joints[0], joints[1], gtc, di, ids[a:b] >= 0)
+            if pve is not None:
+                pve.add(dv, dq, joints[0][:, 0, :].contiguous(), root_table.regress(dq)[0][:, 0, :].contiguous(), di)
     initial, retrained = (args.j_regressor_init, sha16(args.j_regressor_init, J_np)), (path, sha16(path))
     if shift is not None:      # the body model is for the pictures alone: only when --smpl_dir resolves, or --synthetic allows the synthetic one
         model_np = regressor_report.resolve_body_model(args.smpl_dir, args.synthetic) if rank == 0 else None
@@ -333,16 +351,20 @@ def evaluate_vertices(log=print) -> Optional[dict]:
         if reports is None:
             return shift_doc
     results = {k: r.finish() for k, r in reports.items()}
-    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', accel_report.flags_doc(args._get()), initial, retrained)
+    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', vertex_report.flags_doc(accel_report.flags_doc(args._get())), initial,
+                retrained)
     accel_doc = None
     if track is not None:      # every mesh is present and every rank knows it: the float all-reduce, the launches, the integer all-reduce
         accel_doc = accel_report.write(args.eval_report, track.finish(accel_paths, ids, names, ('before', 'after'), present=np.ones(N, dtype=bool)),
                                        args.eval_groups, 'vertices')
+    pve_doc = vertex_report.write(args.eval_report, pve.finish(), names, args.eval_groups, 'vertices', initial) if pve is not None else None
     if rank == 0:
         for k in ('before', 'after'):
             r = results[k][ALL]
             log(f'{k}: n {r["n"]} (bad {r["n_bad"]})  MPJPE {_fmt(r["mpjpe_mm"], ".4f")}  PAMPJPE {_fmt(r["pampjpe_mm"], ".4f")}')
         if accel_doc is not None:
             log(accel_report.summary_line(accel_doc))
+        if pve_doc is not None:
+            log(vertex_report.summary_line(pve_doc))
         log(f'evaluation report: {os.path.join(args.eval_report, "eval.md")}')
     return doc

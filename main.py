@@ -35,6 +35,7 @@ if __name__ == '__main__':
     importlib.import_module(PKG + '.regressor_report').check_flags(args._get())   # --regressor_report: refused before anything runs
     importlib.import_module(PKG + '.accel_report').check_flags(args._get())       # --eval_accel: likewise
     importlib.import_module(PKG + '.regressor_fit').check_flags(args._get())      # --fit_regressor: likewise
+    importlib.import_module(PKG + '.vertex_report').check_flags(args._get())      # --eval_pve: likewise
     if args.fit_regressor:                                                   # Adam steps of the regressor on fixed meshes; no inner loop
         importlib.import_module(PKG + '.regressor_fit').fit_command()
         sys.exit(0)

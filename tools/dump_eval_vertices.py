@@ -7,7 +7,15 @@
 OUT_DIR/vertices.npy (N,6890,3) float32 metres in SMPL vertex order, OUT_DIR/gt_j3d.npy (N,17,3) float32 mm, and OUT_DIR/paths.txt
 (one frame path per mesh) when the dataset split lists its frames.  It is the template for other models: write the same three files
 from their vertices (VIBE, MEVA, METRO: /root/reference/scripts/test.py:141-301,362-373) and the second command evaluates both
-regressors on them.  The arrays are written through numpy's open_memmap, batch by batch."""
+regressors on them.  The arrays are written through numpy's open_memmap, batch by batch.
+
+    python tools/dump_eval_vertices.py OUT_DIR --gt_refined PATH --data_root ROOT [...]
+    python main.py --eval_vertices OUT_DIR --eval_report out/eval --eval_pve [...]
+
+`--gt_refined PATH` (a `--save_refined` directory, or one of its .npz tables: the smoothed or the fused one) also writes
+OUT_DIR/gt_vertices.npy (N,6890,3) float32 metres for `--eval_pve`: the SMPL forward of `pose6d` / `shape` of the table's row at each
+emitted sample's dataset index.  Samples whose row holds no refined pose (has_refined == 0) are dropped from EVERY file, so the files
+keep the same rows."""
 import importlib
 import os
 import sys
@@ -21,7 +29,14 @@ PKG = 'joint-regressor-refinement_amd'
 
 
 def main(argv):
-    out, flags = argv[0], argv[1:]
+    out, flags = argv[0], list(argv[1:])
+    gt_refined = None
+    if '--gt_refined' in flags:
+        at = flags.index('--gt_refined')
+        if at + 1 >= len(flags):
+            raise SystemExit('--gt_refined needs a path')
+        gt_refined = flags[at + 1]
+        del flags[at:at + 2]
     argsmod = importlib.import_module(PKG + '.args')
     argsmod._LazyArgs._ns = argsmod.get_args(flags)
     args = argsmod.args
@@ -36,31 +51,49 @@ def main(argv):
     J_np = sm.default_h36m_regressor(args.j_regressor_init,
                                      allow_default=args.synthetic or args.j_regressor_init == 'SPIN/data/J_regressor_h36m.npy')
     paths = jdata.split_image_paths(jdata.split_location('validation', args.data_root)) if args.data_root else None
-    verts, gts, kept = [], [], []
+    table = None
+    if gt_refined is not None:
+        if not args.data_root:
+            raise SystemExit('--gt_refined needs --data_root: the table\'s rows are dataset indices')
+        table = importlib.import_module(PKG + '.refined').load_path(gt_refined)
+    verts, gts, kept, gt_verts = [], [], [], []
     engines = {}
     with torch.no_grad():
-        for batch in evaluation.validation_batches(smpl.model_np, J_np, device, with_index=paths is not None):
+        for batch in evaluation.validation_batches(smpl.model_np, J_np, device, with_index=paths is not None or table is not None):
             B = int(batch['pose6d'].shape[0])
             if B not in engines:
                 engines[B] = engine.RefineEngine(smpl.device_model, B, flags=engine.FLAG_KEEP_VERTS)
                 engines[B].set_j_regressor(torch.from_numpy(J_np).float().to(device))
             _, v = engines[B].find_joints_forward(batch['betas'].to(device).float().contiguous(),
                                                   x6d=batch['pose6d'].to(device).float().contiguous(), return_verts=True)
-            verts.append(v.cpu().numpy())
-            gts.append(batch['gt_j3d'].float().numpy())
+            v, gt, index = v.cpu().numpy(), batch['gt_j3d'].float().numpy(), None if batch.get('index') is None else np.asarray(batch['index'])
+            if table is not None:
+                if index.max() >= table['has_refined'].shape[0]:
+                    raise SystemExit(f'{gt_refined}: {table["has_refined"].shape[0]} rows, the split has a sample {int(index.max())}')
+                _, g = engines[B].find_joints_forward(torch.from_numpy(table['shape'][index]).to(device).float().contiguous(),
+                                                      x6d=torch.from_numpy(table['pose6d'][index]).to(device).float().contiguous(),
+                                                      return_verts=True)
+                has = table['has_refined'][index].astype(bool)
+                v, gt, index = v[has], gt[has], index[has]
+                gt_verts.append(g.cpu().numpy()[has])
+            verts.append(v)
+            gts.append(gt)
             if paths is not None:
-                kept += [paths[int(i)] for i in batch['index']]
+                kept += [paths[int(i)] for i in index]
     if not verts:
         raise SystemExit('no validation batch (drop_last=True needs at least --batch_size samples)')
     N = sum(v.shape[0] for v in verts)
     os.makedirs(out, exist_ok=True)
-    vm = np.lib.format.open_memmap(os.path.join(out, 'vertices.npy'), mode='w+', dtype=np.float32, shape=(N, 6890, 3))
-    at = 0
-    for v in verts:
-        vm[at:at + v.shape[0]] = v
-        at += v.shape[0]
-    vm.flush()
-    del vm
+    for name, pieces in (('vertices.npy', verts), ('gt_vertices.npy', gt_verts if table is not None else None)):
+        if pieces is None:
+            continue
+        vm = np.lib.format.open_memmap(os.path.join(out, name), mode='w+', dtype=np.float32, shape=(N, 6890, 3))
+        at = 0
+        for v in pieces:
+            vm[at:at + v.shape[0]] = v
+            at += v.shape[0]
+        vm.flush()
+        del vm
     np.save(os.path.join(out, 'gt_j3d.npy'), np.concatenate(gts).astype(np.float32))
     if paths is not None:
         with open(os.path.join(out, 'paths.txt'), 'w') as f:
