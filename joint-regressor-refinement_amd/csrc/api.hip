@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "lbs_tile.h"
 
 using namespace jrr;
 
@@ -81,13 +82,13 @@ static void plan_geometry(int BP, int& nvc, int& nvcb, int& nvcb16, int& nsplit,
   int fwd_cap = nbg <= 2 ? 108 : 54;
   if (kn.fwd_chunk_cap) fwd_cap = kn.fwd_chunk_cap;
   nvc = pick_chunks(nbg, fwd_cap);
-  // exactly one round of 512 workgroups with an even chunk count lets k_lbs_fwd pair the two workgroups of a CU (lbs.hip)
-  if (kn.fwd_round && 512 % nbg == 0 && 512 / nbg <= 64 && ((512 / nbg) & 1) == 0 && 32 % (512 / nbg / 2) == 0) nvc = 512 / nbg;
+  // exactly one round of 512 workgroups with an even chunk count lets k_lbs_fwd pair the two workgroups of a CU (lbs_tile.h)
+  if (kn.fwd_round && 512 % nbg == 0 && 512 / nbg <= 64 && pairs_one_round(nbg, 512 / nbg)) nvc = 512 / nbg;
   nvcb = pick_chunks(BP / BT, 36);                  // backward, role kernel: one workgroup per (32 poses, chunk)
   nvcb16 = pick_chunks(BP / 64, 36);                // backward, k_lbs_bwd16: one workgroup per (64 poses, chunk)
   // ... but exactly one round of 512 workgroups with an even chunk count lets the kernel pair the two workgroups of a CU on
-  // one pose group (lbs.hip), which is worth more than the last per cent of tile balance
-  if (512 % (BP / 64) == 0 && 512 / (BP / 64) <= 36 && ((512 / (BP / 64)) & 1) == 0 && 32 % (512 / (BP / 64) / 2) == 0) nvcb16 = 512 / (BP / 64);
+  // one pose group (lbs_tile.h), which is worth more than the last per cent of tile balance
+  if (512 % (BP / 64) == 0 && 512 / (BP / 64) <= 36 && pairs_one_round(BP / 64, 512 / (BP / 64))) nvcb16 = 512 / (BP / 64);
   nsplit = (512 + nbg - 1) / nbg;
   // at most 32 slabs -- 64 for batches of up to 512 poses, whose 32 x (BP / 128) workgroups leave most of the chip idle (256 poses, the
   // reference's default batch: blend adjoint 81 -> 46 us, the iteration 0.383 -> 0.357 ms; at 1024 poses 64 slabs gain the product

@@ -35,7 +35,7 @@ struct jrr_engine {
   // entry point that overwrites FT / AT / VPb / VTb or may run between the two calls (drop_cached_forward)
   bool fwd_cached; const float *fc_x6d, *fc_betas;
   float* dJraw;                                      // (17,6890) gradient scratch of the in-call J steps (jrr_refine_run_j_steps)
-  jrr::JSupport jsup; bool have_jsup;                // support lists of the normalised regressor (KEEP_VERTS engines; lbs.hip)
+  jrr::JSupport jsup; bool have_jsup;                // support lists of the normalised regressor (KEEP_VERTS engines; jreg.hip)
   bool jsup_fits_known;                              // jrr_j_support_info has seen flag = 1 for the current regressor lineage
   const float* jsup_mask;                            // ... under this mask (another mask may un-mask entries: knowledge dropped)
   float* hist; int hist_cap, hist_every, hist_n; long long hist_iter;   // loss history (jrr_engine_set_loss_history)

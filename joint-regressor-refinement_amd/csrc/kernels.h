@@ -1,4 +1,4 @@
-// Internal launcher interface: the launch_* functions that cross a translation unit, i.e. the kernels of prep / lbs / gemm / sup / fold
+// Internal launcher interface: the launch_* functions that cross a translation unit, i.e. the kernels of prep / lbs_fwd / lbs_bwd / jreg / gemm / sup / fold
 // and the few of disc / sil that the engine (api.hip) and the fused loop (refine.hip) launch.  A launcher with no caller outside the file
 // of its kernel is static there and is not listed; the feature files (image, report, shade, export, eval, evalrep, regrep, smooth, views, accel) keep
 // their include/jrr.h entry points beside their kernels and declare nothing here.
@@ -88,7 +88,7 @@ int launch_reduce_slabs2(const float* P1, int nslab1, size_t stride1, float* out
 int launch_adam_flat(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step, float lr, float b1,
                      float b2, float eps, hipStream_t s, int step_plus = 0);
 
-// lbs.hip
+// lbs_fwd.hip
 int launch_lbs_fwd(const Model& m, const float* Jn_vi, const float* FT, const float* AT, float* VPb, float* JP,
                    float* VTb, int B, int BP, int nvc, hipStream_t s, long long* probe = nullptr, const int* vmask = nullptr,
                    const int* tl = nullptr, int ntl = 0, int verts_pose_major = 0);
@@ -96,6 +96,7 @@ int launch_lbs_fwd(const Model& m, const float* Jn_vi, const float* FT, const fl
 // tl / ntl (nullable; joint-sparse classes, VPb kept): run the ntl listed tiles only (the regressor's support tiles: every other
 // tile adds exact zeros to the joints); also launch_lbs_bwd and launch_blend_adjoint
 // vmask (nullable, with VTb): store the vertices of the tiles with vmask[tile] != 0 only (JSupport::tmask)
+// lbs_bwd.hip
 int launch_verts_untranspose(const float* VTb, float* verts, int ldv, int vlimit, const float* cam, float* ndc, int B, int BP,
                              hipStream_t s, const int* p2v = nullptr);
 int launch_bwd_tab_static(const Model& m, float* Tb, hipStream_t s);
@@ -105,6 +106,7 @@ int launch_lbs_bwd(const Model& m, const float* Tb, const float* AT, const float
 // dmask (nullable; k_lbs_bwd16 only -- ignored by the role kernel, which fills its slabs): [nvc][BP / 64] joint masks of the rows written
 // (rows of untouched joints are then not zero-filled; consumer: PrepBwdLaunch::dmaskA)
 int launch_dverts_transpose(const float* dverts, int ldv, float* dVT, int B, int BP, hipStream_t s, const int* p2v = nullptr);
+// jreg.hip
 // Support of the normalised regressor (the J step's products only need it: ReLU' makes dJ exactly zero elsewhere).
 // JSupport lives in the engine workspace: cnt[i] positive entries of row i, their internal vertex rows / weights in ascending
 // vertex order, flag[0] = 1 when every row has at most JSUP_CAP of them (else the dense products run).
@@ -128,7 +130,7 @@ int launch_jsup_scatter(const JSupport& sup, const float* in, const int* p2v, fl
 // sup / p2v / dJs (nullable): also deliver the gradient on the support lists, dJs [17][JSUP_CAP]
 int launch_jreg_bwd(const float* J, const float* mask, const float* Jn, const float* rowsum, const float* dJn, int ldn,
                     float* dJ, const int* v2p, hipStream_t s, const JSupport* sup = nullptr, const int* p2v = nullptr, float* dJs = nullptr);
-// the J step's second half in one launch (lbs.hip k_jstep_update)
+// the J step's second half in one launch (jreg.hip k_jstep_update)
 struct JStepUpdate {
   float* J; const float* dJ; const float* dJs; float* m; float* v; int32_t* step; float lr;
   const float* mask; float* Jraw; float* Jmask; float* rowsum; float* Jn; float* Jn_vi; float* Jn_iv; float* Jn_q;

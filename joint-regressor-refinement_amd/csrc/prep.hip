@@ -394,7 +394,7 @@ __global__ __launch_bounds__(PP * NJ) void k_prep_fwd_dconv(const float* __restr
 // p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps), bias corrections evaluated in double like
 // torch's Python scalars.
 // ------------------------------------------------------------------------------------------
-// (AdamScalars / adam_scalars / adam_update: jrr_common.h -- shared with the fused J-step update of lbs.hip)
+// (AdamScalars / adam_scalars / adam_update: jrr_common.h -- shared with the fused J-step update of jreg.hip)
 
 // ------------------------------------------------------------------------------------------
 // Perspective projection of the regressed joints (scripts/renderer.py:35-49 with pytorch3d 0.3.0

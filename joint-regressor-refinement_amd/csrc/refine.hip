@@ -449,7 +449,7 @@ int jrr::j_grad_from_verts(jrr_engine* e, float* dJ, hipStream_t s, float* dJs) 
     jrr_set_error("dJ: the stored vertices are those of a J step over the regressor's support; run jrr_find_joints_forward first");
     return JRR_ERR_STATE;
   }
-  // over the regressor's support when its lists fit (lbs.hip, "J step over the regressor's SUPPORT"), else the dense product
+  // over the regressor's support when its lists fit (jreg.hip, "J step over the regressor's SUPPORT"), else the dense product
   const int* sflag = e->have_jsup ? e->jsup.flag : nullptr;
   if (e->have_jsup) launch_jgrad_sparse(e->jsup, e->dJT, e->VTb, e->dJn, e->BP, s);
   if (!(e->have_jsup && e->jsup_fits_known)) {      // (known to fit: the dense product and its slab sum are not even enqueued)
@@ -607,7 +607,7 @@ int jrr::j_step_apply(jrr_engine* e, float* J, const float* dJ, float* m, float*
   const bool cached = e->fwd_cached, known = e->jsup_fits_known && mask == e->jsup_mask;
   if (!known && e->have_jsup) JRR_HIP(hipMemsetAsync(e->jsup.flag + JSUP_KNOWN, 0, sizeof(int32_t), s));   // (another mask: no baseline to hold the new support against)
   if (e->have_jsup && e->have_J && e->tab_static) {
-    // Adam, the engine's copy, the row sums, the normalised layouts and the support lists in ONE launch (lbs.hip k_jstep_update)
+    // Adam, the engine's copy, the row sums, the normalised layouts and the support lists in ONE launch (jreg.hip k_jstep_update)
     JStepUpdate a;
     a.J = J; a.dJ = dJ; a.dJs = dJs; a.m = m; a.v = v; a.step = step; a.lr = lr;
     a.mask = mask; a.Jraw = e->Jraw; a.Jmask = e->Jmask; a.rowsum = e->rowsum; a.Jn = e->Jn; a.Jn_vi = e->Jn_vi; a.Jn_iv = e->Jn_iv;

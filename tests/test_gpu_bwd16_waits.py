@@ -1,4 +1,4 @@
-"""k_lbs_bwd16 keeps its register prefetch in flight with hand-counted vmcnt waits (csrc/lbs.hip, csrc/jrr_common.h quad_load /
+"""k_lbs_bwd16 keeps its register prefetch in flight with hand-counted vmcnt waits (csrc/lbs_bwd.hip, csrc/jrr_common.h quad_load /
 quads_landed).  A count that is too large is a DATA HAZARD -- a product reads a register whose load has not landed -- and shows as
 wrong or non-repeatable numbers, not as a fault.  So every case here runs TWICE and must be bitwise equal to itself, and is held
 against the oracle with the bounds tests/test_gpu_round4.py uses for the same quantities.  The shapes reach the edges of the

@@ -257,6 +257,22 @@ def test_full_size_properties(eng_mod, dmodel, smpl_model_np, j_h36m_np):
     assert (j2 - rigid).abs().max().item() < 2e-5
 
 
+# batch -> (BP, nvc, nvcb, nsplit, nsplitJ) of the default joint-sparse model (nvcb: the chunks of k_lbs_bwd16).  Worked out by hand from
+# the planner's rules (pick_chunks; one paired round of 512 workgroups where the chunk count comes out even, within its cap, and whole
+# pose groups fall on an XCD), not read off an engine: the planner and the two launchers share that condition (lbs_tile.h,
+# pairs_one_round), and a planner that stops choosing the paired geometries shows here -- 1024, 2048 and 4096 are paired in both kernels.
+LAUNCH_GEOMETRY = {128: (128, 108, 36, 64, 3), 300: (384, 54, 36, 64, 3), 512: (512, 54, 36, 64, 3), 1024: (1024, 64, 32, 32, 3),
+                   2048: (2048, 32, 16, 32, 3), 3000: (3072, 20, 31, 22, 3), 4096: (4096, 16, 8, 16, 3)}
+
+
+@pytest.mark.parametrize('B', sorted(LAUNCH_GEOMETRY))
+def test_launch_geometry_of_the_default_model(eng_mod, dmodel, B):
+    """no kernel runs: the engine's plan alone"""
+    info = eng_mod.RefineEngine(dmodel, B).info
+    assert info['joint_sparse'] in (8, 12), info
+    assert (info['BP'], info['nvc'], info['nvcb'], info['nsplit'], info['nsplitJ']) == LAUNCH_GEOMETRY[B], info
+
+
 @pytest.mark.parametrize('B', [4096, 8192])
 def test_full_size_matches_small_engines_and_oracle(eng_mod, dmodel, smpl_model_np, j_h36m_np, B):
     """B = 4096 / 8192 run the single-round launch geometry (512 workgroups, two per CU sharing a chunk pair

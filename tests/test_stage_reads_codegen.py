@@ -25,7 +25,7 @@ def asm():
     with tempfile.TemporaryDirectory(prefix='jrr_asm_') as tmp:
         jobs = {src: subprocess.Popen([b._hipcc()] + b.FLAGS + ['--cuda-device-only', '-S', os.path.join(b.CSRC, src), '-o',
                                                                os.path.join(tmp, src + '.s')], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-                for src in ('lbs.hip', 'gemm.hip', 'prep.hip')}
+                for src in ('lbs_fwd.hip', 'gemm.hip', 'prep.hip')}
         for src, p in jobs.items():
             _, err = p.communicate()
             assert p.returncode == 0, err[-2000:]
@@ -144,9 +144,9 @@ def test_the_loops_left_as_they_were_are_listed_by_name(asm):
                                                 10 per tile), and the skinning / regressor stages, whose reads depend on a matrix
                                                 result (single K steps, not counted here)
     and group 3 of the last blend chunk of k_lbs_fwd keeps the 16-byte reads the compiler narrows into overlapping registers (8-byte
-    reads were measured slower as well): build.overlapping_lds_reads lists them, in lbs.hip only."""
+    reads were measured slower as well): build.overlapping_lds_reads lists them, in lbs_fwd.hip only."""
     b = _build()
-    rows = b.lds_wait_rows(asm={k: asm[k] for k in ('gemm.hip', 'lbs.hip')})
+    rows = b.lds_wait_rows(asm={k: asm[k] for k in ('gemm.hip', 'lbs_fwd.hip')})
     adj = _quad_waits(rows, 'jrr::k_blend_adjoint<')
     for n in ('jrr::k_blend_adjoint<false>', 'jrr::k_blend_adjoint<true>'):
         assert sorted(r['mfma'] for r in adj if r['name'] == n) == [0, 27], n
@@ -158,7 +158,7 @@ def test_the_loops_left_as_they_were_are_listed_by_name(asm):
         assert zero in (9, 10), (n, zero)
         assert {r['mfma'] for r in fwd if r['name'] == n} <= {0, 11}, n
     assert b.overlapping_lds_reads({'gemm.hip': asm['gemm.hip']}) == []
-    found = b.overlapping_lds_reads({'lbs.hip': asm['lbs.hip']})
+    found = b.overlapping_lds_reads({'lbs_fwd.hip': asm['lbs_fwd.hip']})
     assert found and all('k_lbs_fwd' in f for f in found), found[:3]
 
 

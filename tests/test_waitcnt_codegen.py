@@ -24,7 +24,7 @@ def asm():
     with tempfile.TemporaryDirectory(prefix='jrr_asm_') as tmp:
         jobs = {src: subprocess.Popen([b._hipcc()] + b.FLAGS + ['--cuda-device-only', '-S', os.path.join(b.CSRC, src), '-o',
                                                                os.path.join(tmp, src + '.s')], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-                for src in ('lbs.hip', 'gemm.hip')}
+                for src in ('lbs_bwd.hip', 'gemm.hip')}
         for src, p in jobs.items():
             _, err = p.communicate()
             assert p.returncode == 0, err[-2000:]
@@ -112,7 +112,7 @@ def test_k_lbs_bwd16_tile_loop_has_no_full_drain_beside_matrix_work(asm):
     """every instantiation (DV 0 / 1 / 2, 8 / 12 joint slots, WIDE, LIST): no basic block of the tile loop that holds a matrix
     instruction holds a compiler-emitted vmcnt(0).  (The flush blocks hold none and may drain.)  On the parent of this change the
     same helper lists three per tile pair in the headline instantiation -- DESIGN.md section 8 quotes them."""
-    rows = [r for r in _build().waitcnt_rows(asm={'lbs.hip': asm['lbs.hip']}) if 'k_lbs_bwd16<' in r['name']]
+    rows = [r for r in _build().waitcnt_rows(asm={'lbs_bwd.hip': asm['lbs_bwd.hip']}) if 'k_lbs_bwd16<' in r['name']]
     names = {r['name'] for r in rows}
     assert len(names) == 16, sorted(names)                      # 4 x (8, 12) x WIDE, DV = 0 also LIST
     bad = [(r['name'], r['block'], r['text']) for r in rows if r['loop'] is not None and r['mfma'] > 0 and r['vmcnt'] == 0]
@@ -124,9 +124,9 @@ def test_k_lbs_bwd16_tile_loop_has_no_full_drain_beside_matrix_work(asm):
 
 def test_k_lbs_bwd16_asm_loads_reach_their_wait_untouched(asm):
     """the prefetch is issued from inline asm, invisible to the compiler: nothing may name its registers before the hand-written wait"""
-    text = asm['lbs.hip']
+    text = asm['lbs_bwd.hip']
     assert len(re.findall(r'; landed v\[', text)) >= 16 * 4      # prologue, two tiles, the wait behind the loop -- per instantiation
-    assert _build().asm_load_hazards({'lbs.hip': text}) == []
+    assert _build().asm_load_hazards({'lbs_bwd.hip': text}) == []
 
 
 def test_fc2_adjoint_gemm_prologue_loads_its_dot_partials_together(asm):
