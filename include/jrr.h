@@ -34,7 +34,8 @@ typedef enum {
   JRR_ERR_ARG = -1,       /* null pointer / bad size */
   JRR_ERR_HIP = -2,       /* a HIP runtime call failed; see jrr_last_error() */
   JRR_ERR_WORKSPACE = -3, /* workspace too small */
-  JRR_ERR_STATE = -4      /* engine not configured for the requested op */
+  JRR_ERR_STATE = -4,     /* engine not configured for the requested op */
+  JRR_ERR_SEGMENT = -5    /* jrr_bootstrap_sums: a segment with a negative count, or one that leaves the unit table */
 } jrr_status;
 
 enum {
@@ -198,6 +199,37 @@ enum {
   JRR_PVE_ACC_PART_PA = 338,        /* 32: the same for the aligned error */
   JRR_PVE_ACC_BINS = 151,
   JRR_PVE_ACC_TRAILER = 2           /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
+};
+
+/* The paired bootstrap of the evaluation report (`--eval_ci`): jrr_paired_units fills two int64 tables, jrr_bootstrap_sums resamples
+ * the first.  Layout version 1.
+ *   units  [n_units][JRR_BOOT_UNIT_ROW]: per resampling unit (a video sequence, or a frame) the sums over its counted poses.
+ *   wins   [n_groups][JRR_BOOT_WINS_ROW] + JRR_BOOT_WINS_TRAILER words behind the last row.
+ * Overflow: a counted pose has 17 values below 1.0e3f per column, so its sum is below 17 * 10^3 * 2^24 < 2^39.  A replicate adds
+ * count_s unit rows: BEFORE the launch the host computes, in unbounded integers, (largest count_s) x (largest word of the unit table)
+ * and refuses when it reaches 2^62 -- nothing overflows silently. */
+enum {
+  JRR_BOOT_LAYOUT_VERSION = 1,
+  JRR_BOOT_UNIT_ROW = 5,
+  JRR_BOOT_UNIT_BEFORE = 0,         /* sum over the unit's poses of sum_j rn(err_j * 2^24), initial regressor (units of 2^-24 m) */
+  JRR_BOOT_UNIT_BEFORE_PA = 1,      /* the same for err_pa_j */
+  JRR_BOOT_UNIT_AFTER = 2,          /* retrained regressor */
+  JRR_BOOT_UNIT_AFTER_PA = 3,
+  JRR_BOOT_UNIT_COUNT = 4,          /* poses counted */
+  JRR_BOOT_WINS_ROW = 8,
+  JRR_BOOT_WINS_COUNT = 0,          /* poses counted */
+  JRR_BOOT_WINS_BAD = 1,            /* poses of this group left out for BOTH regressors: one of their 68 values fails e < 1.0e3f */
+  JRR_BOOT_WINS_BETTER = 2,         /* counted poses whose AFTER sum is smaller than their BEFORE sum (integer comparison) */
+  JRR_BOOT_WINS_WORSE = 3,          /* ... larger */
+  JRR_BOOT_WINS_TIE = 4,            /* ... equal */
+  JRR_BOOT_WINS_BETTER_PA = 5,      /* the same three for the aligned sums */
+  JRR_BOOT_WINS_WORSE_PA = 6,
+  JRR_BOOT_WINS_TIE_PA = 7,
+  JRR_BOOT_WINS_TRAILER = 3,
+  JRR_BOOT_WINS_TRAILER_IGNORED = 0,    /* poses with group < 0 (ignored on purpose) */
+  JRR_BOOT_WINS_TRAILER_BAD_GROUP = 1,  /* poses with group >= n_groups (the caller treats non-zero as an error) */
+  JRR_BOOT_WINS_TRAILER_BAD_UNIT = 2,   /* poses with a unit outside [0, n_units) (likewise) */
+  JRR_BOOT_MAX_SEGMENTS = 1025          /* all units + one segment per group (JRR_EVAL_ACC_MAX_GROUPS) */
 };
 
 #define JRR_FLAG_SIL_SIZE(size) ((((size) / 32) & 15) << 16)
@@ -688,6 +720,38 @@ int jrr_vertex_error(const float* pred_dev, const float* gt_dev, const float* ro
                      const int32_t* group_dev, const int32_t* part_dev, int n_parts, int batch, int n_verts, int n_groups,
                      float* pve_dev, float* pa_pve_dev, float* err_v_dev, float* err_pa_v_dev, int64_t* acc_dev, int64_t* acc_v_dev,
                      void* stream);
+
+/* The paired bootstrap of the evaluation report (`--eval_ci`; no reference counterpart: scripts/test.py:125-138 prints four means and
+ * no word on how sure their difference is).  Tables: JRR_BOOT_* above.
+ *
+ * jrr_paired_units: the four (batch,17) fp32 arrays jrr_evaluate_joints wrote -- plain and aligned errors of the initial regressor
+ * (before_dev, before_pa_dev) and of the retrained one (after_dev, after_pa_dev) on the SAME poses -- with group_dev and unit_dev
+ * (batch) int32.  Per pose, four int64 sums S_c = sum_j rn(e_j * 2^24): the expression of jrr_eval_accumulate, from one shared header,
+ * so per group the column sums of the units equal the sums over j of that table's SUM words.  A pose adds to exactly one word class:
+ * group < 0 to trailer word IGNORED only; group >= n_groups to BAD_GROUP only; else a unit outside [0, n_units) to BAD_UNIT only;
+ * else, with one of its 68 values failing e < 1.0e3f (NaN, inf; a guard against overflow, no tolerance), to its group's BAD only -- the
+ * analysis is paired: a pose that is bad for one regressor is out for both --; else S_before, S_before_pa, S_after, S_after_pa, 1 to
+ * units_dev[unit] and, in wins_dev[group], COUNT += 1 and one of BETTER / WORSE / TIE by the integer comparison of S_after with
+ * S_before, and one of the three _PA words likewise.  Integer atomics only: the tables are a function of the multiset of poses -- not
+ * of the order, the split into calls or the sharding over ranks (sum the ranks' tables).  The caller zeroes both tables once per
+ * report; nothing is read back.  1 <= n_groups <= JRR_EVAL_ACC_MAX_GROUPS, n_units >= 1; batch == 0 returns JRR_OK without a launch.
+ *
+ * jrr_bootstrap_sums: units_dev int64 [n_units][5]; segments_host int32 [n_seg][2] = (begin, count) runs of unit rows, in HOST
+ * memory: the call checks them and then uploads these very words to segments_dev (n_seg * 2 int32 of device memory the caller owns), so
+ * the launch reads what was checked.  out_dev int64 [n_seg][rep_count][5]: row (s, r - rep_begin) is the sum of count_s unit rows,
+ * draw i of which is row begin_s + ((w * count_s) >> 32) with w the word i & 3 of Philox4x32-10 at counter (i >> 2, r, s, 0) under
+ * key (seed & 0xffffffff, seed >> 32), for replicates r = rep_begin .. rep_begin + rep_count - 1 (multipliers 0xD2511F53 and
+ * 0xCD9E8D57, Weyl constants 0x9E3779B9 and 0xBB67AE85).  A segment with count 0 gives a zero row.  Every output word is stored exactly
+ * once: no atomics, nothing to zero.  A row depends on (seed, r, s, begin_s, count_s) and the unit rows alone: not on the launch, on
+ * rep_begin, on rep_count or on the other segments, so the replicates may be split over calls and over ranks.
+ * JRR_ERR_SEGMENT, with a message and without a launch: a negative count, a segment that leaves [0, n_units).  JRR_ERR_ARG: a NULL
+ * pointer, n_seg outside 1 .. JRR_BOOT_MAX_SEGMENTS, a negative replicate range or one that reaches 2^31, a misaligned table.
+ * rep_count == 0 returns JRR_OK without a launch.  The caller keeps the sums below 2^63: the overflow rule at JRR_BOOT_*.          */
+int jrr_paired_units(const float* before_dev, const float* before_pa_dev, const float* after_dev, const float* after_pa_dev,
+                     const int32_t* group_dev, const int32_t* unit_dev, int batch, int n_groups, int n_units, int64_t* units_dev,
+                     int64_t* wins_dev, void* stream);
+int jrr_bootstrap_sums(const int64_t* units_dev, int n_units, const int32_t* segments_host, int32_t* segments_dev, int n_seg, uint64_t seed,
+                       int rep_begin, int rep_count, int64_t* out_dev, void* stream);
 
 /* ---- regressor report (`--regressor_report`): how far the retrained regressor moved each joint, and discs on a picture ------
  * No reference counterpart in code: the reference's teaser.png shows the joints of the accepted regressor, of the retrained one and

@@ -80,6 +80,8 @@ SIGNATURES = {
     'jrr_eval_accumulate': (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     'jrr_accel_error': (c_int, [_P, _P, ctypes.c_int64, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     'jrr_vertex_error': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
+    'jrr_paired_units': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    'jrr_bootstrap_sums': (c_int, [_P, c_int, _P, _P, c_int, ctypes.c_uint64, c_int, c_int, _P, _P]),
     'jrr_regressor_shift_accumulate': (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     'jrr_draw_discs': (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, _P, c_int, c_int, _P]),
     'jrr_project_joints': (c_int, [_P, _P, _P, c_int, _P]),

@@ -140,6 +140,15 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--eval_pve_parts', action='store_true',
                         help='with --eval_pve: per-part means as well, a vertex belonging to the SMPL joint with its largest skinning weight; '
                              'needs the body model (--smpl_dir, or the synthetic one under --synthetic)')
+    parser.add_argument('--eval_ci', action='store_true',
+                        help='with --eval_report DIR (the evaluation, --eval_vertices): also write DIR/ci.json and DIR/ci.md, paired bootstrap '
+                             'intervals of MPJPE / PA-MPJPE before, after and of their difference, per group (ci_report.py): how sure the '
+                             'arrow of the report is; the seed is --seed')
+    parser.add_argument('--eval_ci_unit', type=str, default='sequence', choices=['sequence', 'frame'],
+                        help='--eval_ci: what is resampled with replacement -- whole video sequences (frames that share a camera directory, '
+                             'from the frame paths: images.pkl; paths.txt) or single frames (the dataset index; treats frames as independent)')
+    parser.add_argument('--eval_ci_reps', type=int, default=10000, metavar='R', help='--eval_ci: the number of resamples')
+    parser.add_argument('--eval_ci_level', type=float, default=0.95, help='--eval_ci: the level of the percentile intervals')
     parser.add_argument('--regressor_report', type=str, default=None, metavar='DIR',
                         help='regressor report: DIR/regressor.json and DIR/regressor.md -- per H36M joint the support of the initial and '
                              'the retrained regressor and how far, in a frame fixed to the body, the retrained one moves the joint on the '

@@ -26,6 +26,7 @@
 //                        and of the sharding over ranks.
 #include "jrr_common.h"
 #include "evalk.h"
+#include "fixedpt.h"
 #include "../../include/jrr.h"
 
 namespace jrr {
@@ -215,7 +216,7 @@ __global__ __launch_bounds__(256) void k_eval_accumulate(const float* __restrict
 #pragma unroll
     for (int o = 0; o < 2; ++o) {
       const float e = o == 0 ? e0[i] : e1[i];
-      acc_add(row + (o == 0 ? JRR_EVAL_ACC_SUM : JRR_EVAL_ACC_SUM_PA) + i, __float2ll_rn(e * 16777216.f));
+      acc_add(row + (o == 0 ? JRR_EVAL_ACC_SUM : JRR_EVAL_ACC_SUM_PA) + i, err_fixed24(e));
       // distances are never negative; a negative value a caller passes anyway lands in bin 0 (no index below the row)
       const int bin = max(min((int)floorf(e * 1000.f), JRR_EVAL_ACC_BINS - 1), 0);
       acc_add(row + (o == 0 ? JRR_EVAL_ACC_HIST : JRR_EVAL_ACC_HIST_PA) + bin, 1);

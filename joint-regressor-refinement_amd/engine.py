@@ -941,6 +941,59 @@ def vertex_error(pred: torch.Tensor, gt: torch.Tensor, root_pred: Optional[torch
     return pve, pa, ev, epa
 
 
+BOOT_UNIT_ROW, BOOT_WINS_ROW, BOOT_WINS_TRAILER, BOOT_MAX_SEGMENTS = 5, 8, 3, 1025      # include/jrr.h: JRR_BOOT_*
+BOOT_SUM_LIMIT = 1 << 62                        # the overflow rule of include/jrr.h: (largest count) x (largest unit word) stays below
+
+
+def paired_units(before: torch.Tensor, before_pa: torch.Tensor, after: torch.Tensor, after_pa: torch.Tensor, group: torch.Tensor,
+                 unit: torch.Tensor, n_groups: int, units: torch.Tensor, wins: torch.Tensor) -> None:
+    """jrr_paired_units: ADD the poses' four fixed-point error sums and a 1 to rows `unit` (B, int32) of the int64 table `units`
+    (n_units,5), and their better / worse / tie counts to rows `group` (B, int32) of `wins` (n_groups * 8 + 3 words, include/jrr.h
+    JRR_BOOT_*).  The four inputs are the (B,17) arrays of evaluate_joints for the two regressors on the same poses."""
+    lib = _lib.load()
+    B = before.shape[0]
+    errs = [t.contiguous() for t in (before, before_pa, after, after_pa)]
+    group, unit = group.contiguous(), unit.contiguous()
+    dev = errs[0].device
+    assert all(t.shape == (B, 17) and t.dtype == torch.float32 and t.device == dev for t in errs)
+    assert all(t.shape == (B,) and t.dtype == torch.int32 and t.device == dev for t in (group, unit))
+    assert units.dtype == torch.int64 and units.is_contiguous() and units.dim() == 2 and units.shape[1] == BOOT_UNIT_ROW and units.device == dev
+    assert wins.dtype == torch.int64 and wins.is_contiguous() and wins.numel() == int(n_groups) * BOOT_WINS_ROW + BOOT_WINS_TRAILER and wins.device == dev
+    if B == 0:                                      # an empty tensor has no address to pass
+        return
+    check(lib.jrr_paired_units(ptr(errs[0]), ptr(errs[1]), ptr(errs[2]), ptr(errs[3]), ptr(group), ptr(unit), B, int(n_groups), int(units.shape[0]),
+                               ptr(units), ptr(wins), stream_ptr(dev)), 'paired_units')
+
+
+def bootstrap_sums(units: torch.Tensor, segments, seed: int, rep_begin: int, rep_count: int, max_word: Optional[int] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """jrr_bootstrap_sums: (n_seg, rep_count, 5) int64, replicates rep_begin .. rep_begin + rep_count - 1 of every segment of the int64
+    unit table `units` (n_units,5).  segments: (n_seg,2) host integers (begin, count).  max_word: the largest word of `units` where the
+    caller knows it (it has the table on the host anyway); without it the table is read back once for the overflow rule, which is
+    checked here in Python integers BEFORE the launch.  out: the tensor to fill (every word is stored, none is read); allocated when None."""
+    lib = _lib.load()
+    assert units.dtype == torch.int64 and units.is_contiguous() and units.dim() == 2 and units.shape[1] == BOOT_UNIT_ROW
+    seg = np.ascontiguousarray(np.asarray(segments, dtype=np.int64).reshape(-1, 2))
+    if seg.size and (np.abs(seg).max() >= 1 << 31):
+        raise ValueError('bootstrap_sums: a segment word outside int32')
+    seg32 = np.ascontiguousarray(seg.astype(np.int32))
+    n_seg, n_units = int(seg32.shape[0]), int(units.shape[0])
+    if max_word is None:
+        max_word = int(units.abs().max().item()) if units.numel() else 0
+    worst = (int(seg[:, 1].max()) if n_seg else 0) * int(max_word)
+    if worst >= BOOT_SUM_LIMIT:
+        raise OverflowError(f'bootstrap_sums: {int(seg[:, 1].max())} draws of unit words up to {int(max_word)} could reach {worst} >= 2^62')
+    if out is None:
+        out = torch.empty((n_seg, int(rep_count), BOOT_UNIT_ROW), dtype=torch.int64, device=units.device)
+    assert out.shape == (n_seg, int(rep_count), BOOT_UNIT_ROW) and out.dtype == torch.int64 and out.is_contiguous() and out.device == units.device
+    if n_seg == 0 or int(rep_count) == 0:           # an empty tensor has no address to pass
+        return out
+    seg_dev = torch.empty((n_seg, 2), dtype=torch.int32, device=units.device)
+    check(lib.jrr_bootstrap_sums(ptr(units), n_units, c_void_p(seg32.ctypes.data), ptr(seg_dev), n_seg, int(seed) & 0xffffffffffffffff,
+                                 int(rep_begin), int(rep_count), ptr(out), stream_ptr(units.device)), 'bootstrap_sums')
+    return out
+
+
 SHIFT_ACC_ROW, SHIFT_ACC_TRAILER = 1277, 2      # include/jrr.h: JRR_SHIFT_ACC_ROW, JRR_SHIFT_ACC_TRAILER
 DISCS_MAX_SETS, DISCS_MAX_POINTS = 8, 256       # include/jrr.h: JRR_DISCS_MAX_SETS, JRR_DISCS_MAX_POINTS
 

@@ -276,7 +276,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     """`--eval_vertices DIR --eval_report OUT`: rank r takes shard_bounds(N, r, world) of the meshes in chunks of --batch_size
     (pinned uploads), both regressors on one read of the vertices, one all-reduce per report at the end.  `--eval_pve`: the target
     meshes of gt_vertices.npy ride the same loop on a third pinned buffer into vertex_report.VertexReport."""
-    from . import accel_report, checkpoint, engine as _engine, regressor_report, smpl_model, utils, vertex_report
+    from . import accel_report, checkpoint, ci_report, engine as _engine, regressor_report, smpl_model, utils, vertex_report
     from .args import args
     if not args.eval_report and not args.regressor_report:
         raise ValueError('--eval_vertices needs --eval_report or --regressor_report DIR (where eval.json / eval.md, regressor.json / '
@@ -284,6 +284,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     regressor_report.check_flags(args._get())
     accel_report.check_flags(args._get())
     vertex_report.check_flags(args._get())
+    ci_report.check_flags(args._get())
     verts, gt, names, ids = open_vertices_dir(args.eval_vertices, args.eval_groups)          # before any launch
     gt_verts = vertex_report.open_gt_vertices(args.eval_vertices, verts.shape[0]) if args.eval_pve else None
     part_np = None
@@ -293,6 +294,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
             raise ValueError('--eval_pve_parts needs the body model: --smpl_dir with SMPL_NEUTRAL.npz / .pkl, or --synthetic')
         part_np = vertex_report.part_labels(model_parts['lbs_weights'])
     accel_paths = accel_report.read_paths(args.eval_vertices, verts.shape[0]) if args.eval_accel else None
+    ci_paths = ci_report.read_paths(args.eval_vertices, verts.shape[0]) if args.eval_ci and args.eval_ci_unit == 'sequence' else None
     jdist.init(args.dist_backend)
     rank, local_rank, world = jdist.env_rank_world()
     device = torch.device(args.device if (world == 1 or args.single_device) else f'cuda:{local_rank}')
@@ -309,6 +311,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     shift = regressor_report.Run(args._get(), names, device, J_np, J_after.cpu().numpy(), mask_np, 'vertices') if args.regressor_report else None
     N = verts.shape[0]
     track = accel_report.JointTrack(N, 2, device) if accel_paths is not None else None
+    ci = ci_report.PairedBootstrap(names, *ci_report.unit_ids(args.eval_ci_unit, N, ci_paths), device, ids) if args.eval_ci else None
     pve = vertex_report.VertexReport(names, device, 6890, part_np, 0 if part_np is None else model_parts['lbs_weights'].shape[1]) if gt_verts is not None else None
     root_table = _engine.JointRegressorTable(Js[:1], utils.find_j_reg_mask(Js[0])) if pve is not None else None      # joint 0 of the INITIAL regressor centres both meshes
     lo, hi = jdist.shard_bounds(N, rank, world)
@@ -340,6 +343,8 @@ def evaluate_vertices(log=print) -> Optional[dict]:
                 reports['after'].add(joints[1], gtc, di)
             if track is not None:
                 track.add(np.arange(a, b), (joints[0], joints[1]), gtc)
+            if ci is not None:
+                ci.add(joints[0], joints[1], gtc, di, np.arange(a, b))
             if shift is not None:
                 shift.add(dv, joints[0], joints[1], gtc, di, ids[a:b] >= 0)
             if pve is not None:
@@ -351,12 +356,14 @@ def evaluate_vertices(log=print) -> Optional[dict]:
         if reports is None:
             return shift_doc
     results = {k: r.finish() for k, r in reports.items()}
-    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', vertex_report.flags_doc(accel_report.flags_doc(args._get())), initial,
+    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(args._get()))), initial,
                 retrained)
     accel_doc = None
     if track is not None:      # every mesh is present and every rank knows it: the float all-reduce, the launches, the integer all-reduce
         accel_doc = accel_report.write(args.eval_report, track.finish(accel_paths, ids, names, ('before', 'after'), present=np.ones(N, dtype=bool)),
                                        args.eval_groups, 'vertices')
+    ci_doc = ci_report.write(args.eval_report, ci.finish(args.eval_ci_reps, args.seed, args.eval_ci_level, args.eval_ci_unit), names, args.eval_groups,
+                             'vertices') if ci is not None else None
     pve_doc = vertex_report.write(args.eval_report, pve.finish(), names, args.eval_groups, 'vertices', initial) if pve is not None else None
     if rank == 0:
         for k in ('before', 'after'):
@@ -366,5 +373,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
             log(accel_report.summary_line(accel_doc))
         if pve_doc is not None:
             log(vertex_report.summary_line(pve_doc))
+        if ci_doc is not None:
+            log(ci_report.summary_line(ci_doc))
         log(f'evaluation report: {os.path.join(args.eval_report, "eval.md")}')
     return doc

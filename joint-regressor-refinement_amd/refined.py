@@ -30,6 +30,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 import torch
 
+from . import ci_report
 from . import dist as jdist
 from .args import args
 
@@ -119,7 +120,7 @@ class RefinedExport:
     def finish(self):
         if self.table is None:
             raise RuntimeError('--save_refined: no batch was refined, there is nothing to save')
-        flags_doc = {k: v for k, v in vars(args._get()).items() if isinstance(v, (bool, int, float, str, type(None))) and k != 'eval_accel'}
+        flags_doc = {k: v for k, v in ci_report.flags_doc(args._get()).items() if isinstance(v, (bool, int, float, str, type(None))) and k != 'eval_accel'}
         self.table.finish(self.directory, {'flags': flags_doc, 'body_model': self.body_model, 'j_regressor_sha256_16': self.j_hash,
                                            'inner_iters': int(args.inner_iters), 'data': 'dataset' if args.data_root else 'synthetic'})
 

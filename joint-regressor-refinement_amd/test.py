@@ -18,7 +18,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import accel_report, batches, checkpoint, engine as _engine, eval_report, regressor_report, smpl_model, utils
+from . import accel_report, batches, checkpoint, ci_report, engine as _engine, eval_report, regressor_report, smpl_model, utils
 from .args import args
 from .smpl import SMPL
 
@@ -57,6 +57,23 @@ def _accel_paths():
     return paths
 
 
+def _ci_units():
+    """`--eval_ci`: (unit of every dataset index, number of units) of the whole split for `sequence` units, None for `frame` units (the
+    dataset index: the table is sized by the first batch); ValueError naming what is missing"""
+    ci_report.check_flags(args._get())
+    if args.eval_ci_unit == 'frame':
+        return None
+    if not args.data_root:
+        raise ValueError('--eval_ci --eval_ci_unit sequence needs --data_root (a dataset whose images.pkl holds the frame paths: they say which '
+                         'samples share a video sequence), or resample frames: --eval_ci_unit frame')
+    from . import data as jdata
+    location = jdata.split_location('validation', args.data_root)
+    paths = jdata.split_image_paths(location)
+    if paths is None:
+        raise ci_report.missing_paths_error(os.path.join(location, 'images.pkl'))
+    return ci_report.unit_ids('sequence', len(paths), paths)
+
+
 def _batch_groups(batch, group_ids, B: int, device) -> torch.Tensor:
     """the batch's group ids on the device; samples the batch marks `valid == 0` get -1 (not scored)"""
     gid = torch.zeros(B, dtype=torch.int32)
@@ -69,6 +86,7 @@ def _batch_groups(batch, group_ids, B: int, device) -> torch.Tensor:
 
 def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> Dict[str, float]:
     accel_paths = _accel_paths() if args.eval_accel else None                                            # refuses before any launch
+    ci_units = _ci_units() if args.eval_ci else None                                                     # likewise
     device = torch.device(args.device)
     torch.cuda.set_device(device)
     smpl = SMPL(args.smpl_dir, batch_size=1, allow_synthetic=args.synthetic or args.smpl_dir == 'SPIN/data/smpl').to(device)   # :40-43
@@ -79,7 +97,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     J_regressor_initial = torch.from_numpy(J_np).float().to(device)                                      # :48-49
     j_reg_mask = utils.find_j_reg_mask(J_regressor_initial)                                              # :51-53
 
-    source = validation_batches(smpl.model_np, J_np, device, with_index=bool(args.eval_report or args.regressor_report or args.eval_accel))
+    source = validation_batches(smpl.model_np, J_np, device, with_index=bool(args.eval_report or args.regressor_report or args.eval_accel or args.eval_ci))
     reports, group_ids = None, None
     shift = None
     if args.regressor_report:  # what the retrained regressor did to each joint: one more launch per batch, the vertices of its forward kept
@@ -89,6 +107,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
         names, group_ids = _groups()
         reports = {'before': eval_report.EvalReport(names, device), 'after': eval_report.EvalReport(names, device)}
     track = accel_report.JointTrack(len(accel_paths), 2, device) if accel_paths is not None else None
+    ci, ci_seen = None, 0      # --eval_ci: the paired bootstrap's unit table, opened at the first batch (frame units: one per sample of the split)
 
     mpjpe_before, pampjpe_before, mpjpe_after, pampjpe_after = [], [], [], []
     engines: Dict[int, _engine.RefineEngine] = {}
@@ -122,6 +141,12 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
                 reports['after'].add(joints, gt, gid)
             if track is not None:
                 track.add(batch['index'], (joints_before, joints), gt, batch.get('valid'))
+            if args.eval_ci:   # three more launches: both regressors' per-joint errors, then the units; nothing read back
+                if ci is None:
+                    unit_of_row, n_units = ci_units or ci_report.unit_ids('frame', int(batch.get('n_samples', args.synthetic_batches * B)))
+                    ci = ci_report.PairedBootstrap(names, unit_of_row, n_units, device, group_ids)
+                ci.add(joints_before, joints, gt, gid, batch['index'] if 'index' in batch else torch.arange(ci_seen, ci_seen + B))
+                ci_seen += B
             if shift is not None:
                 shift.add(verts, joints_initial, joints, gt, gid, None if 'valid' not in batch else batch['valid'].cpu().bool().numpy())
     if not mpjpe_before:
@@ -133,11 +158,14 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     if reports is not None:    # this function runs in ONE process (main.py: rank 0) on whole batches: nothing to reduce
         results = {k: r.finish(reduce=False) for k, r in reports.items()}
         rep['eval_report'] = eval_report.write(args.eval_report, results, names, args.eval_groups if group_ids is not None else 'none', 'parameters',
-                                               accel_report.flags_doc(args._get()), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
+                                               ci_report.flags_doc(accel_report.flags_doc(args._get())), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
                                                (path, eval_report.sha16(path)))
     if track is not None:      # one launch per regressor over the whole split's time order, one read-back
         rep['accel_report'] = accel_report.write(args.eval_report, track.finish(accel_paths, group_ids, names, ('before', 'after'), reduce=False),
                                                  args.eval_groups, 'parameters')
+    if ci is not None:         # the read-back of the unit table, one launch for all replicates, the read-back of their sums
+        rep['ci_report'] = ci_report.write(args.eval_report, ci.finish(args.eval_ci_reps, args.seed, args.eval_ci_level, args.eval_ci_unit, reduce=False),
+                                           names, args.eval_groups if group_ids is not None else 'none', 'parameters')
     if shift is not None:
         rep['regressor_report'] = shift.finish((args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
                                                (path, eval_report.sha16(path)), smpl.model_np, smpl.device_model, reduce=False)
@@ -153,6 +181,8 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     log(f"{rep['pampjpe_after']:.4f}")
     if track is not None:
         log(accel_report.summary_line(rep['accel_report']))
+    if ci is not None:
+        log(ci_report.summary_line(rep['ci_report']))
     return rep
 
 
