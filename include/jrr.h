@@ -1113,6 +1113,40 @@ int jrr_jfit_norm_moments(void* state_dev, const void* cache_dev, int64_t n_rows
                           const double* x_dev /* [17][128] */, int mode, double delta_m, double* out_dev, void* scratch_dev,
                           size_t scratch_bytes, void* stream);
 
+/* ---- the price of every mesh vertex in the regressor solve (`--fit_solve --fit_grow R`, regressor_solve.py, csrc/jprice.hip) ------------
+ * The solve above is exact over the entries it was given; its Frank-Wolfe gap says nothing about the other vertices of a row.  What is
+ * missing is the gradient of the loss with respect to a weight on EVERY vertex at the current solution.  With the residuals of section
+ * 3k / 3l (r_i = q_i - q_0 - gt_i / 1000, q_i = sum_e x_i[e] v[vtx_i[e]], rho = sqrt(r.r + delta^2); an empty row is left out, an empty
+ * pelvis row means q_0 = 0) and the adjoint  a_i = r_i (JRR_JFIT_PRICE_MSE)  or  a_i = r_i / rho (JRR_JFIT_PRICE_NORM), the pass gives
+ *     S[i][u] = sum_s sum_c a_i,c(s) v[s][u][c]          i = 1 .. 16, u = 0 .. 6889                       (fp64 throughout)
+ * and the host forms  g_i[u] = 2 S[i][u] / (51 n)  (MSE)  or  S[i][u] / (17 n)  (NORM),  g_0 = - sum_i g_i: at listed vertices exactly the
+ * gradient of the solve, elsewhere the reduced cost g_i[u] - lambda_i that certifies the solution over the whole mesh or names the
+ * vertices to add (regressor_solve.global_gap, grow_select).  No engine, no body model, no jfit state.
+ *
+ * jrr_jfit_price_bytes  the bytes of the output (fixed: JRR_JFIT_PRICE_DOUBLES doubles); *scratch_bytes (nullable) receives the bytes of
+ *                  the caller-owned scratch for this batch.  batch < 1: both 0.
+ * jrr_jfit_price   verts_dev (batch,6890,3) fp32 m, gt_mm_dev (batch,17,3) fp32 pelvis-centred mm.  The lists are HOST arrays:
+ *                  vtx_host[17][128] the vertices of each row's entries, counts_host[17], x_host[17][128] the weights (entries behind a
+ *                  row's count are not used).  They are validated on the host, so that every refusal happens before a launch, and copied
+ *                  into the head of the scratch on the stream; the call waits for that copy (it synchronises the stream once, as
+ *                  jrr_jfit_norm_moments does), so the arrays are the caller's again when it returns.  out_dev: S row-major, row i - 1 for joint i (16 * 6890 doubles), then per joint
+ *                  i = 1 .. 16 four doubles: sum r.r, sum rho, sum |r|, samples counted.  An empty row gives zeros everywhere.
+ *                  accumulate = 0: out is this batch's sums (whatever it held).  accumulate = 1: every element of out gets this batch's
+ *                  complete sum added once, so the result is a function of the sequence of batch sizes alone.
+ *                  Three launches: the residuals into the scratch, the products (v_mfma_f64_16x16x4_f64: the 16 joints are the M side,
+ *                  a tile is 16 vertices, k = 4 samples of one axis) over (tile blocks x sample chunks) into slabs of at most 32 MiB,
+ *                  and a finish that adds the slabs in chunk order.  No floating-point atomics: two identical call sequences give the
+ *                  same bits.
+ *                  JRR_ERR_ARG, with a message and before anything is enqueued: a NULL pointer, misalignment (verts / gt 4 bytes, out /
+ *                  scratch 8), batch < 1, a count outside 0 .. 128, a listed vertex outside 0 .. 6889 or repeated in its row, no row
+ *                  with entries, an unknown mode, a delta_m that is negative or not finite, or not positive in NORM mode.
+ *                  JRR_ERR_WORKSPACE: a scratch below jrr_jfit_price_bytes.                                                       */
+enum { JRR_JFIT_PRICE_MSE = 0, JRR_JFIT_PRICE_NORM = 1, JRR_JFIT_PRICE_DOUBLES = 16 * 6890 + 16 * 4 };
+size_t jrr_jfit_price_bytes(int batch, size_t* scratch_bytes);
+int jrr_jfit_price(const float* verts_dev /* (batch,6890,3) */, const float* gt_mm_dev /* (batch,17,3), pelvis-centred mm */, int batch,
+                   const int32_t* vtx_host /* [17][128] */, const int32_t* counts_host /* [17] */, const double* x_host /* [17][128] */,
+                   int mode, double delta_m, int accumulate, double* out_dev, void* scratch_dev, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,9 @@ SIGNATURES = {
     'jrr_jfit_norm_bytes': (c_size_t, [POINTER(c_int32), POINTER(c_size_t)]),
     'jrr_jfit_norm_moments': (c_int, [_P, _P, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_int, _P, c_int, ctypes.c_double, _P, _P, c_size_t,
                                       _P]),
+    'jrr_jfit_price_bytes': (c_size_t, [c_int, POINTER(c_size_t)]),
+    'jrr_jfit_price': (c_int, [_P, _P, c_int, POINTER(c_int32), POINTER(c_int32), POINTER(ctypes.c_double), c_int, ctypes.c_double, c_int, _P, _P,
+                               c_size_t, _P]),
 }
 
 _lib = None

@@ -114,6 +114,13 @@ def build_parser() -> argparse.ArgumentParser:
                              'gains the key `norm`')
     parser.add_argument('--fit_solve_delta_mm', type=float, default=0.01,
                         help='--fit_solve_loss mpjpe: the smoothing of the norm, sqrt(|r|^2 + delta^2), in mm; finite and > 0')
+    parser.add_argument('--fit_grow', type=int, default=None, metavar='R',
+                        help='--fit_solve: price EVERY mesh vertex at the solution (jrr_jfit_price: the gradient of the loss with respect to '
+                             'a weight on each of the 6890 vertices), report the Frank-Wolfe gap over the whole mesh and grow the support where '
+                             'the data want it -- up to R rounds, each adding the vertices with the most negative reduced cost and solving '
+                             'again (0: certify only); solve.json gains the key `grow`')
+    parser.add_argument('--fit_grow_add', type=int, default=8, metavar='A',
+                        help='--fit_grow: most vertices a row adds per round, 1 .. 128')
     parser.add_argument('--eval_report', type=str, default=None, metavar='DIR',
                         help='evaluation report: DIR/eval.json and DIR/eval.md with MPJPE / PA-MPJPE per group and per joint, PCK and AUC, '
                              'initial against retrained regressor (eval_report.py); the printed lines of scripts/test.py:125-138 stay as they are')

@@ -849,6 +849,47 @@ class RegressorFit:
         check(self.lib.jrr_jfit_set_entries(ptr(self.state), ptr(J), stream_ptr(self.device)), 'jfit_set_entries')
 
 
+PRICE_MSE, PRICE_NORM, PRICE_DOUBLES = 0, 1, 16 * 6890 + 16 * 4         # include/jrr.h: JRR_JFIT_PRICE_*
+_price_scratch = {}                                                     # (device, batch) -> the scratch of jrr_jfit_price
+
+
+def price_vertices(verts: torch.Tensor, gt_centred_mm: torch.Tensor, vtx, counts, x, mode: int, delta_m: float,
+                   out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """jrr_jfit_price: the sums S[i][u] (16 x 6890, joint i + 1 against every vertex u) and per joint sum r.r, sum rho, sum |r|, samples of
+    the meshes verts (B,6890,3) against gt_centred_mm (B,17,3) at the lists vtx (17 rows of vertex indices, or (17,128) int32 with
+    `counts`; counts None: the rows' lengths) and the float64 weights x (17 rows, or (17,128)): the (PRICE_DOUBLES,) float64 device tensor
+    regressor_solve.price_gradients reads.  accumulate: ADD this batch's sums to `out`.  The lists are checked by the library on the
+    host; a refusal raises before anything is launched.  No engine, no body model."""
+    lib = _lib.load()
+    B = int(verts.shape[0])
+    verts, gt = verts.contiguous(), gt_centred_mm.contiguous()
+    assert verts.shape == (B, NUM_VERTS, 3) and gt.shape == (B, NUM_H36M, 3) and verts.dtype == gt.dtype == torch.float32
+    assert verts.is_cuda and gt.device == verts.device
+    if counts is None:
+        counts = [len(r) for r in vtx]
+    ch = np.ascontiguousarray(np.asarray(counts, dtype=np.int32).reshape(NUM_H36M))
+    vh, xh = np.zeros((NUM_H36M, JFIT_ROW_CAP), dtype=np.int32), np.zeros((NUM_H36M, JFIT_ROW_CAP), dtype=np.float64)
+    for i in range(NUM_H36M):
+        c = min(max(int(ch[i]), 0), JFIT_ROW_CAP)
+        vh[i, :c] = np.asarray(vtx[i], dtype=np.int64).reshape(-1)[:c]
+        xh[i, :c] = np.asarray(x[i], dtype=np.float64).reshape(-1)[:c]
+    if accumulate:
+        assert out is not None, 'accumulate adds to `out`'
+    if out is None:
+        out = torch.empty(PRICE_DOUBLES, dtype=torch.float64, device=verts.device)
+    assert out.shape == (PRICE_DOUBLES,) and out.dtype == torch.float64 and out.is_contiguous() and out.device == verts.device
+    key = (verts.device, B)
+    if key not in _price_scratch:
+        need = ctypes.c_size_t(0)
+        assert int(lib.jrr_jfit_price_bytes(B, ctypes.byref(need))) == PRICE_DOUBLES * 8
+        _price_scratch[key] = torch.empty((int(need.value) + 7) // 8, dtype=torch.float64, device=verts.device)
+    scratch = _price_scratch[key]
+    as_p = lambda a, t: a.ctypes.data_as(ctypes.POINTER(t))
+    check(lib.jrr_jfit_price(ptr(verts), ptr(gt), B, as_p(vh, c_int32), as_p(ch, c_int32), as_p(xh, ctypes.c_double), int(mode), float(delta_m),
+                             1 if accumulate else 0, ptr(out), ptr(scratch), scratch.numel() * 8, stream_ptr(verts.device)), 'jfit_price')
+    return out
+
+
 EVAL_ACC_ROW, EVAL_ACC_TRAILER = 338, 2         # include/jrr.h: JRR_EVAL_ACC_ROW, JRR_EVAL_ACC_TRAILER
 
 

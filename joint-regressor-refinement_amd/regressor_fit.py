@@ -52,6 +52,15 @@ def check_flags(ns) -> None:
         raise ValueError(f'--fit_solve_delta_mm {delta_mm}: a finite positive number of millimetres')
     if (loss_kind != 'mse' or delta_mm != 0.01) and not getattr(ns, 'fit_solve', False):
         raise ValueError('--fit_solve_loss / --fit_solve_delta_mm need --fit_solve')
+    grow, grow_add = getattr(ns, 'fit_grow', None), int(getattr(ns, 'fit_grow_add', 8))
+    if grow is not None and int(grow) < 0:
+        raise ValueError(f'--fit_grow {grow}: 0 or more rounds')
+    if not 1 <= grow_add <= ROW_CAP:
+        raise ValueError(f'--fit_grow_add {grow_add}: 1 .. {ROW_CAP}')
+    if (grow is not None or grow_add != 8) and not getattr(ns, 'fit_solve', False):
+        raise ValueError('--fit_grow / --fit_grow_add need --fit_solve')
+    if grow_add != 8 and grow is None:
+        raise ValueError('--fit_grow_add belongs to --fit_grow R')
     if ns.fit_regressor is None:
         if ns.fit_from is not None:
             raise ValueError('--fit_from belongs to --fit_regressor OUT')

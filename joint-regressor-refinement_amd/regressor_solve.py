@@ -16,6 +16,10 @@ jrr_jfit_moments: one pass over the table, fp64).  This module is the host side,
                       majorise-minimise -- each pass (the device's, or norm_blocks_reference) gives the objective, its gradient, the gap
                       and a quadratic majoriser, which solve_quadratic_blocks minimises; certificate L(x) - min L <= gap + delta
 
+  price_reference     `--fit_grow R`: the pass of jrr_jfit_price restated -- the gradient of the loss with respect to a weight on EVERY
+  price_gradients     vertex of the mesh at the current solution; global_gap: the Frank-Wolfe gap over the whole mesh; grow_select / grow:
+  global_gap, grow    column generation -- add the vertices with the most negative reduced cost, drop the zero weights, solve again
+
 The solver is a projected Newton method on the faces of the simplices.  At x the free set is the entries with x > 0 and the entries
 at zero whose gradient lies below their row's multiplier grad_i . x_i (they want to enter).  On the free set the sum constraints are
 eliminated by a Householder basis per row, and the reduced Hessian, plus a small multiple of the identity (the Gram matrix of
@@ -483,6 +487,211 @@ def candidate_pattern(cands: Sequence[np.ndarray], nv: int = NV) -> np.ndarray:
     return P
 
 
+# ---- every vertex priced: the certificate over the whole mesh and the growth of the support (`--fit_grow R`; include/jrr.h, jrr_jfit_price) ----
+PRICE_MSE, PRICE_NORM = 0, 1          # include/jrr.h: JRR_JFIT_PRICE_*
+PRICE_DOUBLES = (NJ - 1) * NV + (NJ - 1) * 4
+UNION_CAP = NJ * ROW_CAP              # 2176 vertices in the union of the lists: what the state of the fit holds
+GROW_KEYS = ('rounds', 'add', 'max_rounds', 'eligible', 'global_gap', 'global_converged')
+GROW_ROUND_KEYS = ('round', 'candidates', 'support', 'loss', 'gap', 'global_gap', 'added', 'dropped', 'min_reduced', 'capped')
+
+
+def _residuals(verts, gt, cands, x):
+    """r (n, 17, 3) float64 in m (row 0 and the empty rows zero), from meshes (n, 6890, 3) and pelvis-centred gt (n, 17, 3) in mm"""
+    cands = _lists(cands)
+    x = _rows(x, cands)
+    V = np.asarray(verts)
+    G = np.asarray(gt)
+    if V.ndim != 3 or V.shape[1:] != (NV, 3) or G.shape != (V.shape[0], NJ, 3) or V.shape[0] < 1:
+        raise ValueError(f'meshes of shape {V.shape} with ground truth of shape {G.shape}')
+    for v in cands:
+        if v.size > ROW_CAP or (v.size and (v.min() < 0 or v.max() >= NV)) or np.unique(v).size != v.size:
+            raise ValueError(f'a list of at most {ROW_CAP} different vertices in 0 .. {NV - 1}')
+    if sum(v.size for v in cands) == 0:
+        raise ValueError('no listed entry')
+    n = V.shape[0]
+    q = np.zeros((n, NJ, 3))
+    for i in range(NJ):
+        if cands[i].size:
+            q[:, i] = np.einsum('e,nec->nc', x[i], V[:, cands[i]].astype(np.float64))
+    r = np.zeros((n, NJ, 3))
+    for i in range(1, NJ):
+        if cands[i].size:
+            r[:, i] = q[:, i] - q[:, 0] - G[:, i].astype(np.float64) / 1000.0
+    return r
+
+
+def price_reference(verts, gt, cands, x, mode: int, delta: float) -> np.ndarray:
+    """the pass of jrr_jfit_price restated in numpy float64, the same output array: S (16, 6890) row-major -- S[i - 1][u] = sum over
+    the meshes and axes of a_i,c v[u][c], a_i = r_i (PRICE_MSE) or r_i / rho (PRICE_NORM) -- then per joint i = 1 .. 16 sum r.r, sum rho,
+    sum |r| and the samples counted.  verts (n, 6890, 3) m, gt (n, 17, 3) pelvis-centred mm, cands / x: 17 lists of vertices and their
+    weights, delta in m."""
+    if mode not in (PRICE_MSE, PRICE_NORM) or not (np.isfinite(delta) and delta >= 0.0) or (mode == PRICE_NORM and not delta > 0.0):
+        raise ValueError(f'mode {mode} with delta {delta}')
+    r = _residuals(verts, gt, cands, x)
+    cands = _lists(cands)
+    n = r.shape[0]
+    rr = (r * r).sum(2)                                            # (n, 17)
+    rho = np.sqrt(rr + float(delta) * float(delta))
+    a = r / rho[:, :, None] if mode == PRICE_NORM else r
+    V2 = np.asarray(verts).astype(np.float64).transpose(0, 2, 1).reshape(3 * n, NV)
+    S = a[:, 1:].transpose(1, 0, 2).reshape(NJ - 1, 3 * n) @ V2
+    out = np.zeros(PRICE_DOUBLES)
+    out[:(NJ - 1) * NV] = S.reshape(-1)
+    tail = out[(NJ - 1) * NV:].reshape(NJ - 1, 4)
+    for i in range(1, NJ):
+        if cands[i].size:
+            tail[i - 1] = (rr[:, i].sum(), rho[:, i].sum(), np.sqrt(rr[:, i]).sum(), float(n))
+    return out
+
+
+def price_loss(out, n: int, mode: int) -> float:
+    """the loss the prices belong to, from the scalars of the pass: sum r.r / (51 n) (PRICE_MSE) or sum rho / (17 n) (PRICE_NORM: L_delta)"""
+    tail = np.asarray(out, dtype=np.float64).reshape(-1)[(NJ - 1) * NV:].reshape(NJ - 1, 4)
+    return float(tail[:, 0].sum()) / (float(n) * NJ * 3) if mode == PRICE_MSE else float(tail[:, 1].sum()) / (float(n) * NJ)
+
+
+def price_gradients(out, n: int, cands, mode: int) -> np.ndarray:
+    """g (17, 6890): the gradient of the loss with respect to a weight on vertex u in row i, from the output of the pass over n meshes:
+    g_i = 2 S_i / (51 n) (PRICE_MSE) or S_i / (17 n) (PRICE_NORM) for i >= 1, and g_0 = - sum of the g_i of the rows with entries when row
+    0 has entries (else zeros).  At listed vertices it is the gradient loss_from_moments / norm_gradient returns."""
+    cands = _lists(cands)
+    flat = np.asarray(out, dtype=np.float64).reshape(-1)
+    if flat.size != PRICE_DOUBLES or n < 1 or mode not in (PRICE_MSE, PRICE_NORM):
+        raise ValueError(f'{flat.size} doubles over {n} meshes in mode {mode}')
+    c = 2.0 / (float(n) * NJ * 3) if mode == PRICE_MSE else 1.0 / (float(n) * NJ)
+    g = np.zeros((NJ, NV))
+    for i in range(1, NJ):
+        if cands[i].size:
+            g[i] = c * flat[(i - 1) * NV:i * NV]
+    if cands[0].size:
+        g[0] = -g[1:].sum(0)
+    return g
+
+
+def _eligible(eligible, cands) -> np.ndarray:
+    E = np.ones((NJ, NV), dtype=bool) if eligible is None else np.asarray(eligible) > 0
+    if E.shape != (NJ, NV):
+        raise ValueError(f'eligible of shape {E.shape}: ({NJ}, {NV})')
+    E = E.copy()
+    for i, v in enumerate(cands):
+        E[i, v] = True                                             # a listed entry is a vertex of its row whatever the mask says
+    return E
+
+
+def global_gap(g, cands, x, eligible=None):
+    """(gap, lambda (17,), min_reduced (17,)): lambda_i = g_i[listed] . x_i, min_reduced_i = min over the eligible u of g_i[u] - lambda_i
+    (<= 0), gap = - sum of min_reduced over the rows with entries -- the Frank-Wolfe gap over the product of the simplices on ALL
+    eligible vertices, the unlisted ones at weight zero: 0 <= L(x) - min L <= gap.  eligible (17, 6890), > 0 where a vertex may carry
+    weight (None: everywhere); rows without entries give zeros."""
+    cands = _lists(cands)
+    x = _rows(x, cands)
+    g = np.asarray(g, dtype=np.float64)
+    E = _eligible(eligible, cands)
+    lam, low = np.zeros(NJ), np.zeros(NJ)
+    for i in range(NJ):
+        if cands[i].size:
+            lam[i] = float(g[i, cands[i]] @ x[i])
+            low[i] = float(g[i][E[i]].min()) - lam[i]
+    return float(-low.sum()), lam, low
+
+
+def grow_select(g, cands, x, eligible, add: int) -> dict:
+    """one selection of the column generation.  First every row with entries drops its listed entries whose weight is exactly 0.  Then,
+    rows in order 0 .. 16, a row with entries adds up to `add` eligible unlisted vertices with the most negative reduced cost
+    g_i[u] - lambda_i, strictly below 0, ties to the lower vertex; never above 128 entries a row or 2176 vertices in the union of the
+    lists (`capped`: a cap stopped an addition).  Rows without entries stay empty.  Returns {'cands' (each ascending), 'x' (zeros on the
+    new entries), 'added' [17], 'dropped' [17], 'capped'}."""
+    cands = _lists(cands)
+    x = _rows(x, cands)
+    g = np.asarray(g, dtype=np.float64)
+    add = int(add)
+    if add < 0:
+        raise ValueError(f'add {add}: 0 or more')
+    E = _eligible(eligible, cands)
+    _, lam, _ = global_gap(g, cands, x, E)
+    kept, wts, dropped = [], [], [0] * NJ
+    for i in range(NJ):
+        on = x[i] != 0.0
+        dropped[i] = int((~on).sum())
+        kept.append(cands[i][on])
+        wts.append(x[i][on])
+    union = set(np.concatenate(kept).tolist())
+    added, capped = [0] * NJ, False
+    for i in range(NJ):
+        if cands[i].size == 0:
+            continue
+        red = g[i] - lam[i]
+        ok = E[i] & (red < 0.0)
+        ok[kept[i]] = False
+        pool = np.flatnonzero(ok)
+        pool = pool[np.lexsort((pool, red[pool]))]                 # by reduced cost, then by vertex
+        new = []
+        for u in pool.tolist():
+            if len(new) >= add:
+                break
+            if kept[i].size + len(new) >= ROW_CAP:
+                capped = True
+                break
+            if u not in union:
+                if len(union) >= UNION_CAP:                         # (17 rows of at most 128: the row cap always binds first)
+                    capped = True
+                    continue
+                union.add(u)
+            new.append(u)
+        added[i] = len(new)
+        v = np.concatenate([kept[i], np.asarray(new, dtype=np.int64)])
+        w = np.concatenate([wts[i], np.zeros(len(new))])
+        order = np.argsort(v, kind='stable')
+        kept[i], wts[i] = v[order], w[order]
+    return {'cands': kept, 'x': wts, 'added': added, 'dropped': dropped, 'capped': capped}
+
+
+def grow(solve_fn, price_fn, cands, x0, tol: float, rounds: int, add: int, eligible=None, mode: int = PRICE_MSE) -> dict:
+    """the column generation: solve -> price -> stop or select -> solve, warm-started at the current weights with zeros on the new entries.
+    solve_fn(cands, x_start) returns what `solve` returns ('x', 'loss', 'loss0', 'gap', ...); price_fn(cands, x) returns (the output
+    array of the pass, the number of meshes n); `mode` says which loss the prices belong to.  Ends when the global gap is at most
+    tol * L(x0) (`global_converged`), when a selection adds nothing, or after `rounds` selections; rounds = 0 solves once and prices once.
+    Returns {'cands', 'x', 'rounds': one record (GROW_ROUND_KEYS) per solve, 'global_gap', 'global_converged', 'loss0', 'result': the
+    last solve's}."""
+    cands = _lists(cands)
+    x = _rows(x0, cands)
+    rounds, add = int(rounds), int(add)
+    if rounds < 0 or add < 1 or not tol > 0.0:
+        raise ValueError(f'grow: rounds {rounds} (0 or more), add {add} (1 or more), tol {tol} (positive)')
+    records, loss0, k = [], None, 0
+    while True:
+        res = solve_fn(cands, x)
+        x = _rows(res['x'], cands)
+        if loss0 is None:
+            loss0 = float(res['loss0'])
+        out, n = price_fn(cands, x)
+        g = price_gradients(out, n, cands, mode)
+        gap, _, low = global_gap(g, cands, x, eligible)
+        rec = {'round': k, 'candidates': [int(v.size) for v in cands], 'support': [int((r > 0).sum()) for r in x], 'loss': float(res['loss']),
+               'gap': float(res['gap']), 'global_gap': gap, 'added': [0] * NJ, 'dropped': [0] * NJ, 'min_reduced': [float(v) for v in low],
+               'capped': False}
+        records.append(rec)
+        converged = bool(gap <= tol * loss0)
+        if converged or k >= rounds:
+            break
+        sel = grow_select(g, cands, x, eligible, add)
+        if sum(sel['added']) == 0:
+            rec['capped'] = bool(sel['capped'])
+            break
+        rec.update(added=sel['added'], dropped=sel['dropped'], capped=bool(sel['capped']))
+        cands, x = sel['cands'], sel['x']
+        k += 1
+    return {'cands': cands, 'x': x, 'rounds': records, 'global_gap': gap, 'global_converged': converged, 'loss0': loss0, 'result': res}
+
+
+def build_grow_doc(result: dict, add: int, max_rounds: int, eligible: int) -> dict:
+    """the `grow` key of solve.json from what grow returned (its records may carry the command's scores of the round)"""
+    plain = lambda v: v.item() if isinstance(v, np.generic) else v
+    rounds = [{k: ([plain(e) for e in v] if isinstance(v, (list, tuple)) else plain(v)) for k, v in r.items()} for r in result['rounds']]
+    return {'rounds': rounds, 'add': int(add), 'max_rounds': int(max_rounds), 'eligible': int(eligible),
+            'global_gap': float(result['global_gap']), 'global_converged': bool(result['global_converged'])}
+
+
 def build_doc(source: str, flags: dict, n_train: int, n_holdout: int, rings: int, support_before, candidates, support_after, losses: dict,
               result: dict, tol: float, initial: dict, final: dict, checkpoint: str, j_regressor_init) -> dict:
     """solve.json.  losses: LOSS_KEYS (the held-out ones None without held-out rows); result: what solve returned; initial / final:
@@ -498,7 +707,8 @@ def build_doc(source: str, flags: dict, n_train: int, n_holdout: int, rings: int
 
 
 def solve_command(log=print) -> Optional[dict]:
-    """`python main.py --fit_regressor OUT --fit_from PATH --fit_solve [--fit_rings K] [--fit_solve_tol 1e-6] [--fit_solve_iters N]`.
+    """`python main.py --fit_regressor OUT --fit_from PATH --fit_solve [--fit_rings K] [--fit_solve_tol 1e-6] [--fit_solve_iters N]
+    [--fit_grow R [--fit_grow_add 8]]`.
     One process: under torchrun rank 0 works and the other ranks return.  Prints one summary line."""
     import torch
     from . import checkpoint, dist as jdist, engine as _engine, regressor_fit as rf, smpl_model, utils
@@ -544,9 +754,6 @@ def solve_command(log=print) -> Optional[dict]:
         jf = _engine.RegressorFit(J_init, mask, order.size)
     rf.fill_cache(jf, source, order, int(ns.batch_size), device)
     before = rf._score_doc(rf._scores(jf, n_train, n_hold).cpu().numpy())
-    M_train = jf.moments(0, n_train).cpu().numpy()
-    M_hold = jf.moments(n_train, n_hold).cpu().numpy() if n_hold else None
-    jf.info()                                                      # raises if the device refused a call
     cols = np.unique(np.concatenate(cands))
     assert cols.size == jf.ns and [v.size for v in cands] == jf.counts
     lists = [np.searchsorted(cols, v) for v in cands]
@@ -555,31 +762,99 @@ def solve_command(log=print) -> Optional[dict]:
         r = np.maximum(Jm[i, v].astype(np.float64), 0.0)
         x0.append(r / r.sum() if v.size else r)
     tol = float(ns.fit_solve_tol)
-    norm_doc = None
-    if getattr(ns, 'fit_solve_loss', 'mse') == 'mpjpe':
+    mpjpe = getattr(ns, 'fit_solve_loss', 'mse') == 'mpjpe'
+    delta = float(ns.fit_solve_delta_mm) / 1000.0
+
+    def run_solve(jf, lists, x_start):
+        """the solve on a filled state: (result, moments of the training rows, of the held-out rows, the `norm` document or None)"""
+        M_train = jf.moments(0, n_train).cpu().numpy()
+        M_hold = jf.moments(n_train, n_hold).cpu().numpy() if n_hold else None
+        jf.info()                                                  # raises if the device refused a call
+        if not mpjpe:
+            return solve(M_train, n_train, lists, x_start, tol=tol, max_iter=int(ns.fit_solve_iters)), M_train, M_hold, None
         # the MPJPE itself: reweighted moment passes on the device, the quadratics on the host; the MSE loss block below then says
         # what the switch costs in MSE; `gap` is the gap of the smoothed MPJPE in m, `iterations` the Newton steps of all quadratics
-        delta = float(ns.fit_solve_delta_mm) / 1000.0
         blocks_of = lambda x, mode, d, a, c: parse_norm_blocks(jf.norm_moments(x, mode, d, a, c).cpu().numpy(), jf.counts)
-        nres = solve_norm(lambda x, mode, d: blocks_of(x, mode, d, 0, n_train), n_train, lists, x0, delta, tol=tol,
+        nres = solve_norm(lambda x, mode, d: blocks_of(x, mode, d, 0, n_train), n_train, lists, x_start, delta, tol=tol,
                           max_iter=int(ns.fit_solve_iters))
         held_obj = None
         if n_hold:
             held_obj = {k: norm_objective(blocks_of(xs, NORM_INV, delta, n_train, n_hold), n_hold)[1]
-                        for k, xs in (('start', x0), ('mse', nres['x_mse']), ('final', nres['x']))}
+                        for k, xs in (('start', x_start), ('mse', nres['x_mse']), ('final', nres['x']))}
         jf.info()
-        norm_doc = build_norm_doc(nres, float(ns.fit_solve_delta_mm), held_obj)
-        res = {'x': nres['x'], 'loss0': loss_from_moments(M_train, n_train, lists, x0)[0],
+        res = {'x': nres['x'], 'loss0': loss_from_moments(M_train, n_train, lists, x_start)[0],
                'loss': loss_from_moments(M_train, n_train, lists, nres['x'])[0], 'gap': nres['gap'], 'iterations': nres['inner_iterations'],
-               'converged': nres['converged']}
-    else:
-        res = solve(M_train, n_train, lists, x0, tol=tol, max_iter=int(ns.fit_solve_iters))
-    losses ={'train_before': res['loss0'], 'train_after': res['loss'], 'holdout_before': None, 'holdout_after': None}
+               'converged': nres['converged'], 'smoothed': nres['smoothed']}
+        return res, M_train, M_hold, build_norm_doc(nres, float(ns.fit_solve_delta_mm), held_obj)
+
+    res, M_train, M_hold, norm_doc = run_solve(jf, lists, x0)
+    losses = {'train_before': res['loss0'], 'train_after': res['loss'], 'holdout_before': None, 'holdout_after': None}
     if n_hold:
         losses['holdout_before'] = loss_from_moments(M_hold, n_hold, lists, x0)[0]
+    grow_doc, J_fill = None, J_np
+    if getattr(ns, 'fit_grow', None) is not None:
+        # every vertex priced at the solution; the support grows where the reduced costs are negative and the solve runs again on a
+        # state prepared from the new lists: two passes over the source per round (the cache fill and the prices)
+        eligible = mask_np > 0
+        J_base = J_np.copy()                                       # what the unlisted elements of a grown row hold: zeros
+        for i, v in enumerate(cands):
+            J_base[i, v] = 0.0
+        cur = {'jf': jf, 'lists': lists, 'M_hold': M_hold, 'first': res}
+        extras = []
+
+        def dense_of(c, xs):
+            Jd = J_base.copy()
+            for i, v in enumerate(c):
+                Jd[i, v] = np.asarray(xs[i], dtype=np.float32)
+            return Jd
+
+        def solve_fn(c, x_start):
+            if cur['first'] is not None:                           # round 0 is the solve above
+                r, cur['first'] = cur['first'], None
+            else:
+                f = _engine.RegressorFit(torch.from_numpy(candidate_pattern(c)).to(device), mask, order.size)
+                f.J_init = torch.from_numpy(J_base).to(device)
+                f.set_entries(torch.from_numpy(dense_of(c, x_start)).to(device))
+                rf.fill_cache(f, source, order, int(ns.batch_size), device)
+                cols_ = np.unique(np.concatenate(c))
+                assert cols_.size == f.ns and [v.size for v in c] == f.counts
+                ls = [np.searchsorted(cols_, v) for v in c]
+                r, _, mh, nd = run_solve(f, ls, x_start)
+                cur.update(jf=f, lists=ls, M_hold=mh, norm=nd)
+            f = cur['jf']
+            f.set_entries(torch.from_numpy(dense_of(c, r['x'])).to(device))
+            extra = dict(rf._score_doc(rf._scores(f, n_train, n_hold).cpu().numpy()), holdout_loss=None)
+            if n_hold:
+                extra['holdout_loss'] = float(loss_from_moments(cur['M_hold'], n_hold, cur['lists'], r['x'])[0])
+            extras.append(extra)
+            if mpjpe:                                              # the prices are those of the smoothed MPJPE: so are loss and gap of a round
+                return dict(r, mse=r['loss'], loss=r['smoothed']['final'], loss0=r['smoothed']['start'])
+            return r
+
+        def price_fn(c, xs):
+            out = None
+            with torch.no_grad():
+                for a in range(0, n_train, int(ns.batch_size)):
+                    verts, gt = source.chunk(order[a:min(a + int(ns.batch_size), n_train)], device)
+                    out = _engine.price_vertices(verts, gt, c, None, xs, PRICE_NORM if mpjpe else PRICE_MSE, delta if mpjpe else 0.0,
+                                                 out=out, accumulate=out is not None)
+            return out.cpu().numpy(), n_train
+
+        gres = grow(solve_fn, price_fn, cands, x0, tol, int(ns.fit_grow), int(ns.fit_grow_add), eligible,
+                    PRICE_NORM if mpjpe else PRICE_MSE)
+        for rec, extra in zip(gres['rounds'], extras):
+            rec.update(extra)
+        grow_doc = build_grow_doc(gres, int(ns.fit_grow_add), int(ns.fit_grow), int(eligible.sum()))
+        last = gres['result']
+        res = dict(last, loss0=res['loss0'], loss=last.get('mse', last['loss']))
+        cands, jf, lists, M_hold = gres['cands'], cur['jf'], cur['lists'], cur['M_hold']
+        norm_doc = cur.get('norm', norm_doc)
+        losses['train_after'] = res['loss']
+        J_fill = J_base
+    if n_hold:
         losses['holdout_after'] = loss_from_moments(M_hold, n_hold, lists, res['x'])[0]
     # the normalised weights are the raw values; zeros stay zeros
-    J_new = J_np.copy()
+    J_new = J_fill.copy()
     for i, v in enumerate(cands):
         J_new[i, v] = res['x'][i].astype(np.float32)
     jf.set_entries(torch.from_numpy(J_new).to(device))
@@ -593,6 +868,8 @@ def solve_command(log=print) -> Optional[dict]:
                     rf.support_counts(J.cpu().numpy(), mask_np), losses, res, tol, before, after, path, ns.j_regressor_init)
     if norm_doc is not None:
         doc['norm'] = norm_doc
+    if grow_doc is not None:
+        doc['grow'] = grow_doc
     with open(os.path.join(ns.fit_regressor, 'solve.json'), 'w') as f:
         json.dump(doc, f, indent=1, sort_keys=True, default=str)
     fmt = lambda d, k: '-' if d is None or d[k] is None else format(d[k], '.4f')
@@ -601,6 +878,10 @@ def solve_command(log=print) -> Optional[dict]:
         o = norm_doc['objective_mm']
         extra = (f', objective MPJPE in {norm_doc["passes"]} passes: {o["start"]:.4f} mm at the start, {o["mse"]:.4f} mm at the MSE optimum, '
                  f'{o["final"]:.4f} mm at the end, at most {norm_doc["bound_mm"]:.3e} mm above the optimum (delta {norm_doc["delta_mm"]:g} mm)')
+    if grow_doc is not None:
+        extra += (f', over the whole mesh ({grow_doc["eligible"]} eligible entries): global gap {grow_doc["global_gap"]:.3e} '
+                  f'({"converged" if grow_doc["global_converged"] else "NOT converged"}) after {len(grow_doc["rounds"]) - 1} of at most '
+                  f'{grow_doc["max_rounds"]} rounds of up to {grow_doc["add"]} vertices a row')
     log(f'solved the regressor on {n_train} rows ({n_hold} held out, {jf.entries} entries on {jf.ns} vertices, {rings} rings) in '
         f'{res["iterations"]} steps: loss {res["loss0"]:.6e} -> {res["loss"]:.6e}, gap {res["gap"]:.3e} '
         f'({"converged" if res["converged"] else "NOT converged"} at tol {tol:g}), support {sum(doc["support"]["before"])} -> '
