@@ -919,8 +919,16 @@ int jrr_j_step_apply_support(jrr_engine_t* e, float* J_dev, const float* dJs_dev
  * the same arithmetic up to the summation order of the regressor product.  Reuse is explicit per call: by calling this
  * entry point the caller states that the previous calls on this engine were jrr_j_regressor_grad on the same x6d / betas
  * buffers (optionally followed by jrr_j_step_apply / jrr_engine_set_j_regressor) and that nothing has written those
- * buffers since.  What the engine can check it checks: any other entry point drops the cached forward, and the call then
- * returns JRR_ERR_STATE (also when the pointers differ) instead of differentiating through a stale forward.           */
+ * buffers since.  What the engine can check it checks: the stored forward is dropped by every entry point that enqueues work
+ * on the engine's workspace, uploads parameters or changes a loss term (jrr_find_joints_forward / _backward, jrr_smpl_*_backward, jrr_pose_disc_*,
+ * jrr_shape_disc_*, jrr_silhouette_forward / _backward / _loss_grad, jrr_camera_prefit, jrr_refine_run, jrr_refine_aux_losses,
+ * jrr_engine_set_folded / _pose_disc / _shape_disc / _reprojection / _silhouette), and by jrr_engine_set_j_regressor when the J
+ * step stored the support's tiles only (jrr_j_step_apply_support above); the call then returns JRR_ERR_STATE (also when the
+ * pointers differ) instead of differentiating through a stale forward.  It is kept by the J step's own calls, by
+ * jrr_find_joints_after_j_step, and by the calls that only read or configure: jrr_smpl_posed_joints,
+ * jrr_silhouette_pix_to_face, jrr_j_support_info (unless it reports a grown support), jrr_engine_support_tiles / _vertices,
+ * jrr_engine_info, jrr_engine_set_batch_norm, the loss history, profiling and probe calls (tests/test_gpu_engine_state.py holds
+ * every entry point to this list).                                                                                     */
 int jrr_refine_run_after_j_step(jrr_engine_t* e, float* x6d_dev, float* betas_dev, const float* gt_centred_mm_dev,
                                 float* adam_m_dev, float* adam_v_dev, int32_t* step_dev, float lr, int n_iters,
                                 float* sqerr_dev, void* stream);

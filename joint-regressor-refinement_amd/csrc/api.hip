@@ -223,7 +223,7 @@ static size_t carve(jrr_engine* e, void* ws, int B, int flags) {
     if (flags & JRR_FLAG_SUPPORT_TILES) { float* sb = c.take(sup_tables_floats()); if (sb) sup_tables_carve(t->sup, sb); }
   }
   if (e) {
-    e->BP = BP; e->nvc = nvc; e->nvcb = (e->has_model && e->m.kjs && e->m.bwd16) ? nvcb16 : nvcb; e->nsplit = nsplit; e->nsplitJ = nsplitJ;
+    e->BP = BP; e->nvc = nvc; e->nvcb = (e->has_model && uses_r16(e->m)) ? nvcb16 : nvcb; e->nsplit = nsplit; e->nsplitJ = nsplitJ;
   }
   return c.off;
 }
@@ -259,7 +259,7 @@ extern "C" int jrr_engine_create(const jrr_model_t* model, int batch, int batch_
   e->flags = flags;
   e->sil = sil_size_of(flags);
   carve(e, ws, batch, flags);
-  e->have_jsup = (flags & JRR_FLAG_KEEP_VERTS) != 0;
+  e->st.engine_created((flags & JRR_FLAG_KEEP_VERTS) != 0);
   if (flags & JRR_FLAG_BLEND_BF16X3) {      // side mode: the basis is split once, here
     launch_split_blend_basis(e->m.Dq, e->Dsplit, nullptr);
     const hipError_t he = hipStreamSynchronize(nullptr);
@@ -364,16 +364,16 @@ int jrr::fold_rebuild(jrr_engine* e, hipStream_t s) {
     if (rc) return rc;
   }
   launch_transpose(e->Hm, e->Hk, NH * NJ * 3, KFP, s, KFP, FOLD_M);
-  e->fold_valid = true;
+  e->st.fold_rebuilt();
   return 0;
 }
 
 extern "C" int jrr_engine_set_folded(jrr_engine_t* e, int enabled, void* stream) {
   if (!e) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (enabled && !(e->flags & JRR_FLAG_FOLDED)) { jrr_set_error("engine created without JRR_FLAG_FOLDED"); return JRR_ERR_STATE; }
-  e->folded = enabled != 0;
-  if (e->folded && e->have_J && !e->fold_valid) {
+  e->st.folded_set(enabled != 0);
+  if (e->st.folded() && e->st.have_J() && !e->st.fold_valid()) {
     int rc = fold_rebuild(e, (hipStream_t)stream);
     if (rc) return rc;
     CHECK_LAUNCH();
@@ -388,29 +388,23 @@ int jrr::set_j_regressor_impl(jrr_engine* e, const float* J, const float* mask, 
   if (!e || !J) { jrr_set_error("set_j_regressor: null"); return JRR_ERR_ARG; }
   if (!e->has_model) { jrr_set_error("engine was created without an SMPL model (discriminators only)"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
-  e->jsup_fits_known = false;      // a regressor from outside: its support is not known to fit until jrr_j_support_info says so
-  if (e->verts_partial) e->fwd_cached = false;      // the stored vertices cover the OLD regressor's support tiles only
-  e->act_valid = false; e->sup_valid = false;
-  if (e->have_jsup && !step_inc) JRR_HIP(hipMemsetAsync(e->jsup.flag + JSUP_KNOWN, 0, sizeof(int32_t), s));   // (a J step keeps the baseline: step_inc != NULL)
+  e->st.regressor_uploaded(mask, step_inc != nullptr);
+  if (e->st.have_jsup() && !step_inc) JRR_HIP(hipMemsetAsync(e->jsup.flag + JSUP_KNOWN, 0, sizeof(int32_t), s));   // (a J step keeps the baseline: step_inc != NULL)
   JRR_HIP(hipMemcpyAsync(e->Jraw, J, (size_t)NH * V * 4, hipMemcpyDeviceToDevice, s));
   if (mask) JRR_HIP(hipMemcpyAsync(e->Jmask, mask, (size_t)NH * V * 4, hipMemcpyDeviceToDevice, s));
-  e->have_mask = mask != nullptr;
-  if (mask != e->jsup_mask) e->jsup_fits_known = false;      // a different mask may un-mask entries: the support may have grown
-  e->jsup_mask = mask;
-  if (!e->tab_static) {                                                                     // model-only: once per engine
-    launch_bwd_tab_static(e->m, e->Jn_iv, s); e->tab_static = true;
+  if (!e->st.tab_static()) {                                                                     // model-only: once per engine
+    launch_bwd_tab_static(e->m, e->Jn_iv, s); e->st.static_tables_written();
     // the support-restricted J step writes dJn on the support only: everything else must be finite (it meets Jn = 0)
-    if (e->have_jsup) JRR_HIP(hipMemsetAsync(e->dJn, 0, (size_t)NH * VP * sizeof(float), s));
+    if (e->st.have_jsup()) JRR_HIP(hipMemsetAsync(e->dJn, 0, (size_t)NH * VP * sizeof(float), s));
   }
-  launch_jreg_normalize(e->Jraw, e->have_mask ? e->Jmask : nullptr, e->rowsum, e->Jn, e->Jn_vi, e->Jn_iv, e->Jn_q, e->m.p2v, s,
-                        (e->m.kjs && e->m.bwd16) ? 1 : 0, e->m.v2p, e->have_jsup ? &e->jsup : nullptr, step_inc);
-  e->fold_valid = false;
-  if (e->folded) {
+  launch_jreg_normalize(e->Jraw, e->st.have_mask() ? e->Jmask : nullptr, e->rowsum, e->Jn, e->Jn_vi, e->Jn_iv, e->Jn_q, e->m.p2v, s,
+                        uses_r16(e->m) ? 1 : 0, e->m.v2p, e->st.have_jsup() ? &e->jsup : nullptr, step_inc);
+  if (e->st.folded()) {
     int rc = fold_rebuild(e, s);
     if (rc) return rc;
   }
   CHECK_LAUNCH();
-  e->have_J = true;
+  e->st.regressor_ready();
   return JRR_OK;
 }
 
@@ -468,7 +462,7 @@ void jrr::reduce_adjoint_partials(jrr_engine* e, hipStream_t s, const float* con
 }
 // k_lbs_bwd16's slabs carry joint masks instead of zero rows when k_chain_bwd sums them itself (a slab-sum launch reads every row)
 unsigned* jrr::slab_masks(jrr_engine* e) {
-  return (e->m.kjs && e->m.bwd16 && e->nvcb <= MAX_SLABS_IN_CONSUMER) ? e->dmask : nullptr;
+  return (uses_r16(e->m) && e->nvcb <= MAX_SLABS_IN_CONSUMER) ? e->dmask : nullptr;
 }
 void jrr::set_adjoint_slabs(jrr_engine* e, PrepBwdLaunch& L) {
   const bool pre = e->nvcb > MAX_SLABS_IN_CONSUMER;
@@ -481,16 +475,16 @@ int jrr::smpl_forward(jrr_engine* e, const float* x6d, const float* R, const flo
   launch_prep_fwd(e->m, x6d, R, betas, e->FT, e->FTq, e->AT, e->R0T, e->B, e->BP, step_inc, s);
   launch_lbs_fwd(e->m, e->Jn_vi, e->FTq, e->AT, keep_vp ? e->VPb : nullptr, e->JP, verts_pm ? e->VPM : keep_verts ? e->VTb : nullptr, e->B, e->BP,
                  e->nvc, s, nullptr, tl ? nullptr : vmask, tl, ntl, verts_pm ? 1 : 0);
-  if (keep_verts && !verts_pm) e->verts_partial = vmask != nullptr || tl != nullptr;
+  if (keep_verts && !verts_pm) e->st.verts_stored(vmask != nullptr || tl != nullptr);
   return 0;
 }
 
 extern "C" int jrr_find_joints_forward(jrr_engine_t* e, const float* x6d, const float* R, const float* betas,
                                        float* joints, float* verts, void* stream) {
   if (!e || !betas || !joints || ((x6d == nullptr) == (R == nullptr))) { jrr_set_error("find_joints_forward: bad argument"); return JRR_ERR_ARG; }
-  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
+  if (!e->st.have_J()) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   const bool kv = (e->flags & JRR_FLAG_KEEP_VERTS) != 0;
   if (verts && !e->VTb) { jrr_set_error("return_verts needs an engine created with JRR_FLAG_KEEP_VERTS"); return JRR_ERR_STATE; }
   smpl_forward(e, x6d, R, betas, true, kv || verts, nullptr, s);
@@ -510,9 +504,9 @@ extern "C" int jrr_find_joints_backward(jrr_engine_t* e, const float* x6d, const
                                         const float* djoints, float* dx6d, float* dR, float* dbetas, float* dJ,
                                         void* stream) {
   if (!e || !betas || !djoints || ((x6d == nullptr) == (R == nullptr))) { jrr_set_error("find_joints_backward: bad argument"); return JRR_ERR_ARG; }
-  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
+  if (!e->st.have_J()) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   launch_joints_loss(nullptr, 0, nullptr, djoints, 0.f, nullptr, nullptr, e->dJT, e->B, e->BP, s);   // (B,17,3) -> [3][18][BP]
   if (dx6d || dR || dbetas) {
     launch_lbs_bwd(e->m, e->Jn_iv, e->AT, e->VPb, e->dJT, nullptr, e->DVP, e->dATp, e->BP, e->nvcb, s, nullptr, 0, slab_masks(e));
@@ -538,9 +532,9 @@ extern "C" int jrr_smpl_vertices_backward(jrr_engine_t* e, const float* x6d, con
                                           const float* dverts, float* dx6d, float* dR, float* dbetas, void* stream) {
   if (!e || !betas || !dverts || ((x6d == nullptr) == (R == nullptr))) { jrr_set_error("smpl_vertices_backward: bad argument"); return JRR_ERR_ARG; }
   if (!(e->flags & JRR_FLAG_KEEP_VERTS)) { jrr_set_error("smpl_vertices_backward requires JRR_FLAG_KEEP_VERTS"); return JRR_ERR_STATE; }
-  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
+  if (!e->st.have_J()) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   // the caller's adjoint, transposed into its own [3][VP][BP] buffer (the stored vertices stay valid for a later dJ)
   launch_dverts_transpose(dverts, V * 3, e->dVTb, e->B, e->BP, s, e->m.p2v);
   launch_lbs_bwd(e->m, e->Jn_iv, e->AT, e->VPb, nullptr, e->dVTb, e->DVP, e->dATp, e->BP, e->nvcb, s, nullptr, 0, slab_masks(e));
@@ -560,6 +554,7 @@ extern "C" int jrr_smpl_vertices_backward(jrr_engine_t* e, const float* x6d, con
 extern "C" int jrr_smpl_posed_joints(jrr_engine_t* e, const float* betas, float* joints24, void* stream) {
   if (!e || !betas || !joints24) { jrr_set_error("smpl_posed_joints: null"); return JRR_ERR_ARG; }
   if (e->flags & JRR_FLAG_NO_MODEL) { jrr_set_error("smpl_posed_joints: engine created without a body model"); return JRR_ERR_STATE; }
+  // (reads AT and writes the caller's buffer only: a J step's stored forward stays)
   launch_posed_joints(e->m, e->AT, betas, joints24, e->B, e->BP, (hipStream_t)stream);
   CHECK_LAUNCH();
   return JRR_OK;
@@ -571,7 +566,7 @@ extern "C" int jrr_smpl_posed_joints_backward(jrr_engine_t* e, const float* x6d,
   if (!e || !betas || !djoints24 || ((x6d == nullptr) == (R == nullptr))) { jrr_set_error("smpl_posed_joints_backward: bad argument"); return JRR_ERR_ARG; }
   if (e->flags & JRR_FLAG_NO_MODEL) { jrr_set_error("smpl_posed_joints_backward: engine created without a body model"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   launch_posed_joints_bwd(e->m, e->AT, betas, djoints24, e->dA, e->dbT, e->B, e->BP, s);
   JRR_HIP(hipMemsetAsync(e->dF, 0, (size_t)KFP * e->BP * sizeof(float), s));      // the posed joints do not read the blend features
   PrepBwdLaunch L;
@@ -616,7 +611,7 @@ extern "C" int jrr_project_joints(const float* joints, const float* cam, float* 
 
 extern "C" int jrr_engine_set_reprojection(jrr_engine_t* e, const float* gt_j2d, float* cam, float* cam_m, float* cam_v) {
   if (!e) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (gt_j2d && (!cam || !cam_m || !cam_v)) { jrr_set_error("set_reprojection: cam / cam_m / cam_v required"); return JRR_ERR_ARG; }
   e->gt_j2d = gt_j2d; e->cam = cam; e->cam_m = cam_m; e->cam_v = cam_v;
   return JRR_OK;
@@ -625,9 +620,9 @@ extern "C" int jrr_engine_set_reprojection(jrr_engine_t* e, const float* gt_j2d,
 extern "C" int jrr_camera_prefit(jrr_engine_t* e, const float* x6d, const float* betas, const float* gt_j2d, float* cam,
                                  int n_steps, float lr, float* sq2d, void* stream) {
   if (!e || !x6d || !betas || !gt_j2d || !cam || n_steps < 0) return JRR_ERR_ARG;
-  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
+  if (!e->st.have_J()) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   smpl_forward(e, x6d, nullptr, betas, false, false, nullptr, s);
   launch_joints_loss(e->JP, e->nvc, nullptr, nullptr, 0.f, e->joints, nullptr, nullptr, e->B, e->BP, s);
   const float scale2d = (float)(2.0 / ((double)e->bnorm * 34.0));     // optimize.py:193 unweighted MSE

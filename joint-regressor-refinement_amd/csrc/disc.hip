@@ -450,7 +450,7 @@ using namespace jrr;
 
 extern "C" int jrr_engine_set_pose_disc(jrr_engine_t* e, const float* P, void* stream) {
   if (!e || !P) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!(e->flags & JRR_FLAG_POSE_DISC)) { jrr_set_error("engine created without JRR_FLAG_POSE_DISC"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
   JRR_HIP(hipMemcpyAsync(e->Pd, P, (size_t)DP_TOTAL * 4, hipMemcpyDeviceToDevice, s));
@@ -469,7 +469,7 @@ extern "C" int jrr_engine_set_pose_disc(jrr_engine_t* e, const float* P, void* s
 
 extern "C" int jrr_engine_set_shape_disc(jrr_engine_t* e, const float* P, void* stream) {
   if (!e || !P) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!(e->flags & JRR_FLAG_SHAPE_DISC)) { jrr_set_error("engine created without JRR_FLAG_SHAPE_DISC"); return JRR_ERR_STATE; }
   JRR_HIP(hipMemcpyAsync(e->Ps, P, (size_t)JRR_SHAPE_DISC_PARAMS * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   e->have_sd = true;
@@ -523,7 +523,7 @@ int jrr::disc_backward_input(jrr_engine* e, const float* x6d, float* out, const 
 
 extern "C" int jrr_pose_disc_forward(jrr_engine_t* e, const float* x6d, float* out, void* stream) {
   if (!e || !x6d || !out) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
   int rc = disc_forward(e, x6d, out, s);
@@ -536,7 +536,7 @@ extern "C" int jrr_pose_disc_forward(jrr_engine_t* e, const float* x6d, float* o
 extern "C" int jrr_pose_disc_backward_input(jrr_engine_t* e, const float* x6d, float weight, float target, float* dx,
                                             void* stream) {
   if (!e || !x6d || !dx) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
   const float scale = (float)(2.0 * (double)weight / ((double)e->bnorm * 25.0));
   int rc = disc_backward_input(e, x6d, nullptr, nullptr, scale, target, dx, (hipStream_t)stream);
@@ -547,7 +547,7 @@ extern "C" int jrr_pose_disc_backward_input(jrr_engine_t* e, const float* x6d, f
 
 extern "C" int jrr_pose_disc_vjp_input(jrr_engine_t* e, const float* x6d, const float* gout, float* dx, void* stream) {
   if (!e || !x6d || !gout || !dx) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
   int rc = disc_backward_input(e, x6d, nullptr, gout, 0.f, 0.f, dx, (hipStream_t)stream);
   if (rc) return rc;
@@ -618,21 +618,21 @@ static int disc_backward_params(jrr_engine* e, const float* x6d, const float* go
 extern "C" int jrr_pose_disc_backward_params(jrr_engine_t* e, const float* x6d, float target, float* dP, float* sqerr,
                                              void* stream) {
   if (!e || !x6d || !dP) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
   return disc_backward_params(e, x6d, nullptr, (float)(2.0 / ((double)e->bnorm * 25.0)), target, dP, sqerr, (hipStream_t)stream);
 }
 
 extern "C" int jrr_pose_disc_vjp_params(jrr_engine_t* e, const float* x6d, const float* gout, float* dP, void* stream) {
   if (!e || !x6d || !gout || !dP) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!e->have_pd) { jrr_set_error("pose discriminator not set"); return JRR_ERR_STATE; }
   return disc_backward_params(e, x6d, gout, 0.f, 0.f, dP, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int jrr_shape_disc_vjp_params(jrr_engine_t* e, const float* betas, const float* gout, float* dP, void* stream) {
   if (!e || !betas || !gout || !dP) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
   launch_shape_disc_bwd_params(e->Ps, betas, gout, 0.f, 0.f, dP, nullptr, e->B, (hipStream_t)stream);
   CHECK_LAUNCH();
@@ -642,7 +642,7 @@ extern "C" int jrr_shape_disc_vjp_params(jrr_engine_t* e, const float* betas, co
 extern "C" int jrr_shape_disc_backward_params(jrr_engine_t* e, const float* betas, float target, float* dP, float* sqerr,
                                               void* stream) {
   if (!e || !betas || !dP) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
   const float scale = (float)(2.0 / ((double)e->bnorm * 1.0));
   launch_shape_disc_bwd_params(e->Ps, betas, nullptr, scale, target, dP, sqerr, e->B, (hipStream_t)stream);
@@ -652,7 +652,7 @@ extern "C" int jrr_shape_disc_backward_params(jrr_engine_t* e, const float* beta
 
 extern "C" int jrr_shape_disc_forward(jrr_engine_t* e, const float* betas, float* out, void* stream) {
   if (!e || !betas || !out) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
   launch_shape_disc(e->Ps, betas, out, nullptr, 0.f, 0.f, e->B, (hipStream_t)stream);
   CHECK_LAUNCH();
@@ -661,7 +661,7 @@ extern "C" int jrr_shape_disc_forward(jrr_engine_t* e, const float* betas, float
 
 extern "C" int jrr_shape_disc_vjp_input(jrr_engine_t* e, const float* betas, const float* gout, float* dbetas, void* stream) {
   if (!e || !betas || !gout || !dbetas) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (!e->have_sd) { jrr_set_error("shape discriminator not set"); return JRR_ERR_STATE; }
   launch_shape_disc(e->Ps, betas, nullptr, dbetas, 0.f, 0.f, e->B, (hipStream_t)stream, gout);
   CHECK_LAUNCH();

@@ -5,18 +5,19 @@
 #pragma once
 #include <vector>
 
+#include "engine_state.h"
 #include "jrr_common.h"
 #include "kernels.h"
 
 struct jrr_engine {
   jrr::Model m;
+  jrr::EngineState st;                               // what of the stored results may still be used (engine_state.h)
   int B, BP, bnorm, flags;
   int sil;                                           // silhouette image size: 224, or 256 with JRR_FLAG_SIL_256
   int nvc, nvcb, nsplit, nsplitJ;
-  bool have_J, have_mask, have_pd, have_sd, has_model;
+  bool have_pd, have_sd, has_model;
   // workspace sections
   float *rowsum, *Jraw, *Jmask, *Jn, *Jn_vi, *Jn_iv, *Jn_q;
-  bool tab_static;                                   // the W parts of the backward operand records are in place
   float *FT, *FTq, *AT, *VPb, *JP, *dJT, *DVP, *dATp, *dFTp, *joints, *sqerr, *Jsum, *dA, *dF, *R0T, *dRT, *dbT;
   unsigned* dmask;                                   // [slab][BP / 64] joint masks of the dA slabs (k_lbs_bwd16 -> k_chain_bwd)
   float *convL;                                      // LDS image of the per-joint MLP parameters (k_conv_image)
@@ -27,29 +28,22 @@ struct jrr_engine {
   float *dsq, *ssq;                                  // per-pose squared adversarial errors of the last iteration [25][BP], [BP]
   long long* probe;                                  // shader-clock probe of k_lbs_fwd (profiling)
   float *ndc, *sqsil, *VPM; unsigned* cover; int* ncover;   // soft silhouette (JRR_FLAG_SILHOUETTE)
-  const float* sil_mask; float* smask; bool smask_valid;     // target masks, per-pose sum(mask^2)
+  const float* sil_mask; float* smask;      // target masks, per-pose sum(mask^2)
   float *JW, *Hm, *Hk, *G0, *MT, *dMT;      // folded regressor (JRR_FLAG_FOLDED)
   float* Dsplit;                            // the blend basis as bf16 hi | lo chunks (JRR_FLAG_BLEND_BF16X3)
-  bool folded, fold_valid;
-  // forward reuse (jrr_refine_run_after_j_step): state left by jrr_j_regressor_grad's SMPL forward; dropped by every
-  // entry point that overwrites FT / AT / VPb / VTb or may run between the two calls (drop_cached_forward)
-  bool fwd_cached; const float *fc_x6d, *fc_betas;
   float* dJraw;                                      // (17,6890) gradient scratch of the in-call J steps (jrr_refine_run_j_steps)
-  jrr::JSupport jsup; bool have_jsup;                // support lists of the normalised regressor (KEEP_VERTS engines; jreg.hip)
-  bool jsup_fits_known;                              // jrr_j_support_info has seen flag = 1 for the current regressor lineage
-  const float* jsup_mask;                            // ... under this mask (another mask may un-mask entries: knowledge dropped)
+  jrr::JSupport jsup;                                // support lists of the normalised regressor (KEEP_VERTS engines; jreg.hip)
   float* hist; int hist_cap, hist_every, hist_n; long long hist_iter;   // loss history (jrr_engine_set_loss_history)
   float *VTb;       // [3][VP][BP] vertices / transposed vertex adjoint (KEEP_VERTS or SILHOUETTE)
   float *dVTb, *dJnp, *dJn;   // transposed external vertex adjoint [3][VP][BP]; J-gradient partial slabs [3*nsplitJ][32][VP]
   int32_t* step_scratch;      // arrival counter of k_sup_step's step-count protocol (prep.hip), its only user
   bool profiling;
-  bool verts_partial;                                // VTb holds the support tiles of the last J step only
   // JRR_FLAG_SUPPORT_TILES: the 32-vertex tiles that hold an entry of the regressor's support (ascending), taken when
   // jrr_j_support_info reports that the support fits; J steps only shrink the support, so the list stays a superset
-  int* act_list; int nact; bool act_valid;
+  int* act_list;
   // ... and, when the support has at most SUP_NSV vertices, the joint-loss iteration runs per VERTEX in one workgroup per 32-pose group
   // (supk.h): the gathered basis rows and skinning lists of the support, built with the tile list
-  jrr::SupTables sup; int sup_nsv; bool sup_valid;
+  jrr::SupTables sup;
   // JRR_SUP_OVERLAP: a second stream for the half of the support-vertex iteration that does not read the discriminator GEMMs' results,
   // and the two events that fork / join it (all three or none: refine.hip ensure_side_stream, created on first use)
   hipStream_t side; hipEvent_t ev_fork, ev_join;
@@ -67,13 +61,15 @@ static inline void prof_mark(jrr_engine* e, int cls, hipStream_t s) {
   e->ev[cls]->push_back(ev);
 }
 
-// the joint-loss iteration on the regressor's support tiles only (JRR_FLAG_SUPPORT_TILES)
+// the model runs k_lbs_bwd16: the regressor's part of the backward operand records is written in its R16 layout
+static inline bool uses_r16(const jrr::Model& m) { return m.kjs && m.bwd16; }
+// EngineState's two iteration choices with what they need from outside the state
 static inline bool use_tile_list(const jrr_engine* e) {
-  return (e->flags & JRR_FLAG_SUPPORT_TILES) && e->act_valid && e->have_jsup && e->jsup_fits_known && e->sil_mask == nullptr &&
-         e->m.kjs && e->m.bwd16 && !(e->folded && e->fold_valid);
+  return e->st.use_tile_list((e->flags & JRR_FLAG_SUPPORT_TILES) != 0, e->sil_mask != nullptr, uses_r16(e->m));
 }
-// ... per support VERTEX in one workgroup per 32-pose group (supk.h): the same condition and the support's vertex tables built
-static inline bool use_sup_vertices(const jrr_engine* e) { return use_tile_list(e) && e->sup_valid; }
+static inline bool use_sup_vertices(const jrr_engine* e) {
+  return e->st.use_sup_vertices((e->flags & JRR_FLAG_SUPPORT_TILES) != 0, e->sil_mask != nullptr, uses_r16(e->m));
+}
 
 namespace jrr {
 

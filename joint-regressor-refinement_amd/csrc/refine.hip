@@ -13,12 +13,12 @@ int jrr::joints_from_stored_verts(jrr_engine* e, hipStream_t s, int32_t* step_in
   // slab layout [split][plane][32][BP], what k_joints_loss reads with jp_rows = 32.  The support-restricted kernel writes ONE
   // complete slab (slab 0) when the regressor's support lists fit (device flag jsup.flag, which k_joints_loss also reads to
   // sum one slab only); otherwise it returns at once and the dense product below does the work -- and vice versa.
-  if (e->have_jsup) launch_rejoints_sparse(e->jsup, e->VTb, e->dFTp, e->BP, s, step_inc);
+  if (e->st.have_jsup()) launch_rejoints_sparse(e->jsup, e->VTb, e->dFTp, e->BP, s, step_inc);
   // the host KNOWS that the lists fit (jrr_j_support_info; J steps only shrink the support): the dense product need not even be
   // enqueued (an idle launch still costs ~4.7 us of stream time)
-  if (e->have_jsup && e->jsup_fits_known) return 0;
+  if (e->st.support_known()) return 0;
   return launch_gemm_q32(e->Jn_q, 32, 0, e->VTb, e->BP, (size_t)VP * e->BP, e->dFTp, e->BP, (size_t)3 * 32 * e->BP,
-                         (size_t)32 * e->BP, e->BP, VP, 3, e->nsplit, s, e->have_jsup ? e->jsup.flag : nullptr);
+                         (size_t)32 * e->BP, e->BP, VP, 3, e->nsplit, s, e->st.have_jsup() ? e->jsup.flag : nullptr);
 }
 
 // =============================================================================================
@@ -108,7 +108,7 @@ static int in_call_j_step(const RefineCtx& c, const JStepArgs& js, bool& reuse_n
   rc = j_step_apply(e, js.J, e->dJraw, js.m, js.v, js.step, js.lr, js.mask, c.s);
   if (rc) return rc;
   reuse_next = js.reuse;
-  if (!js.reuse) e->fwd_cached = false;
+  if (!js.reuse) e->st.workspace_overwritten();
   return 0;
 }
 
@@ -162,7 +162,7 @@ static int iter_support_step(const RefineCtx& c, bool last, bool& h2t_ready) {
   const bool overlap = c.pd && (want < 0 ? e->B <= 512 : want == 1);
   if (overlap) { int rc = ensure_side_stream(e); if (rc) return rc; }
   SupStepLaunch q;
-  q.t = e->sup; q.nsv = e->sup_nsv; q.Jn_vi = e->Jn_vi; q.gt_mm = c.gt_mm; q.scale = c.jscale;
+  q.t = e->sup; q.nsv = e->st.sup_nsv(); q.Jn_vi = e->Jn_vi; q.gt_mm = c.gt_mm; q.scale = c.jscale;
   q.FT = e->FT; q.FTq = e->FTq; q.AT = e->AT; q.R0T = e->R0T; q.joints_out = e->joints; q.sqerr = c.sqerr;
   q.dA = e->dA; q.dF = e->dF;
   if (c.pd) {
@@ -196,7 +196,7 @@ static int iter_support_step(const RefineCtx& c, bool last, bool& h2t_ready) {
 static void chain_forward(const RefineCtx& c, bool reuse) {
   jrr_engine* e = c.e;
   prof_mark(e, 0, c.s);
-  if (reuse) { if (!e->have_jsup) launch_step_inc(c.step, c.s); }      // (with support lists the count rides in k_rejoints_sparse)
+  if (reuse) { if (!e->st.have_jsup()) launch_step_inc(c.step, c.s); }      // (with support lists the count rides in k_rejoints_sparse)
   else if (c.pd) launch_prep_fwd_dconv(e->m, c.x6d, c.betas, e->FT, e->FTq, e->AT, e->R0T, e->B, e->BP, c.step, e->convL, e->H2T, nullptr, c.s);
   else launch_prep_fwd(e->m, c.x6d, nullptr, c.betas, e->FT, e->FTq, e->AT, e->R0T, e->B, e->BP, c.step, c.s);
   prof_mark(e, 0, c.s);
@@ -263,7 +263,7 @@ static int iter_support_split(const RefineCtx& c) {
   chain_forward(c, false);
   prof_mark(e, 1, s);
   ReprojLaunch rl{e->gt_j2d, e->cam, e->gcam, e->sq2d, c.scale2d};
-  int rc = launch_sup_iter(e->sup, e->sup_nsv, e->Jn_vi, e->FTq, e->AT, c.gt_mm, c.jscale, e->joints, c.sqerr, e->dA, e->dF, e->B, e->BP, s,
+  int rc = launch_sup_iter(e->sup, e->st.sup_nsv(), e->Jn_vi, e->FTq, e->AT, c.gt_mm, c.jscale, e->joints, c.sqerr, e->dA, e->dF, e->B, e->BP, s,
                            e->gt_j2d ? &rl : nullptr);
   if (rc) return rc;
   prof_mark(e, 1, s);
@@ -286,7 +286,7 @@ static int iter_chain(const RefineCtx& c, bool listed, bool reuse, bool sil) {
   jrr_engine* e = c.e;
   hipStream_t s = c.s;
   const int* tl = listed ? e->act_list : nullptr;
-  const int ntl = listed ? e->nact : 0;
+  const int ntl = listed ? e->st.nact() : 0;
   // split-K of the blend adjoint: its K range is 6 chunks per listed tile -- at least JRR_ADJ_CHUNKS (6) chunks per split, so that a
   // handful of tiles does not leave 16 slabs of 3.7 MB (at 4096 poses) for the slab sum to read (6 tiles, 4096 poses: 6 splits
   // 0.3575 ms per iteration, 16 splits 0.3623, 4 splits 0.3618, 2 splits 0.377)
@@ -308,13 +308,13 @@ static int iter_chain(const RefineCtx& c, bool listed, bool reuse, bool sil) {
   }
   prof_mark(e, 1, s);
   prof_mark(e, 2, s);
-  if (reuse) joints_loss(c, e->dFTp, e->nsplit, 32, e->have_jsup ? e->jsup.flag : nullptr);
+  if (reuse) joints_loss(c, e->dFTp, e->nsplit, 32, e->st.have_jsup() ? e->jsup.flag : nullptr);
   else joints_loss(c, e->JP, e->nvc, NH, nullptr);
   prof_mark(e, 2, s);
   if (sil) {   // 100 * mean((silhouette - mask)^2), optimize.py:234-237,252
     prof_mark(e, 8, s);
     const float silscale = (float)(2.0 * 100.0 / ((double)e->bnorm * (double)e->sil * (double)e->sil));
-    if (!e->smask_valid) { launch_mask_sq(e->sil_mask, e->smask, e->B, s, e->sil); e->smask_valid = true; }
+    if (!e->st.smask_valid()) { launch_mask_sq(e->sil_mask, e->smask, e->B, s, e->sil); e->st.mask_sums_computed(); }
     // projection, rasterisation, loss and adjoint in one kernel, straight from / into the row-quad vertex buffer
     launch_sil_raster_adj(e->VTb, e->BP, e->cam, e->m.faces_int_pk ? e->m.faces_int_pk : e->m.faces_pk, e->m.nfaces, e->sil_mask, e->smask, e->cover, e->ncover, e->sqsil,
                           silscale, e->gcam, e->gt_j2d ? 1 : 0, e->B, s, e->sil, e->VPM);
@@ -342,7 +342,7 @@ static int refine_run_impl(jrr_engine_t* e, float* x6d, float* betas, const floa
                            float* adam_v, int32_t* step, float lr, int n_iters, float* sqerr, bool reuse_first,
                            const JStepArgs* js, void* stream) {
   if (!e || !x6d || !betas || !gt_mm || !adam_m || !adam_v || !step || n_iters < 0) { jrr_set_error("refine_run: bad argument"); return JRR_ERR_ARG; }
-  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
+  if (!e->st.have_J()) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
   RefineCtx c;
   c.e = e; c.x6d = x6d; c.betas = betas; c.gt_mm = gt_mm; c.adam_m = adam_m; c.adam_v = adam_v; c.step = step; c.lr = lr;
   c.sqerr = sqerr ? sqerr : e->sqerr;
@@ -356,8 +356,7 @@ static int refine_run_impl(jrr_engine_t* e, float* x6d, float* betas, const floa
   if (reuse_first) {
     // the caller states that the previous call on this engine was the J step on exactly these poses and that nothing
     // has written them since; everything the engine can check is checked
-    const bool ok = e->fwd_cached && e->fc_x6d == x6d && e->fc_betas == betas && e->VTb != nullptr;
-    if (!ok) {
+    if (!(e->st.stored_forward_is(x6d, betas) && e->VTb != nullptr)) {
       jrr_set_error("refine_run_after_j_step: the previous call on this engine was not jrr_j_regressor_grad on the same pose buffers");
       return JRR_ERR_STATE;
     }
@@ -365,20 +364,19 @@ static int refine_run_impl(jrr_engine_t* e, float* x6d, float* betas, const floa
   bool reuse_next = reuse_first;      // the J step before this iteration left its forward (v_posed, skinning transforms, vertices) of exactly these poses
   bool h2t_ready = false;             // (iter_support_step)
   for (int it = 0; it < n_iters; ++it) {
-    const bool folded = e->folded && e->fold_valid;
+    const bool folded = e->st.folded_active();
     const bool listed = use_tile_list(e);
     const bool supv = use_sup_vertices(e);
     const bool sil = e->sil_mask != nullptr && !folded;
     int rc;
     if (supv) {
       // its forward costs less than re-regressing the stored vertices: a pending reuse is dropped, not taken
-      e->fwd_cached = false; reuse_next = false;
+      e->st.workspace_overwritten(); reuse_next = false;
       rc = knobs().support_fused == 2 ? iter_support_split(c) : iter_support_step(c, it + 1 == n_iters, h2t_ready);
     } else {
-      const bool reuse = reuse_next && e->fwd_cached && !folded && e->sil_mask == nullptr &&
-                         !(e->verts_partial && !(e->have_jsup && e->jsup_fits_known));
+      const bool reuse = reuse_next && e->st.fwd_cached() && !folded && e->sil_mask == nullptr && e->st.stored_verts_usable();
       reuse_next = false;
-      e->fwd_cached = false;
+      e->st.workspace_overwritten();
       rc = folded ? iter_folded(c) : iter_chain(c, listed, reuse, sil);
     }
     if (rc) return rc;
@@ -414,7 +412,7 @@ extern "C" int jrr_refine_run_j_steps(jrr_engine_t* e, float* x6d, float* betas,
 
 extern "C" int jrr_refine_aux_losses(jrr_engine_t* e, float* pose_disc_sq, float* shape_disc_sq, void* stream) {
   if (!e) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   hipStream_t s = (hipStream_t)stream;
   if (pose_disc_sq) {
     if (!((e->flags & JRR_FLAG_POSE_DISC) && e->have_pd)) { jrr_set_error("pose discriminator term not active"); return JRR_ERR_STATE; }
@@ -445,19 +443,19 @@ __global__ void k_djn_reduce(const float* __restrict__ P, int nslab, float* __re
 // dJ from the joint adjoint dJT [3][18][BP] (already in the engine) and the stored vertices VTb [3][VP][BP]
 int jrr::j_grad_from_verts(jrr_engine* e, float* dJ, hipStream_t s, float* dJs) {
   if (!(e->flags & JRR_FLAG_KEEP_VERTS)) { jrr_set_error("dJ requires an engine created with JRR_FLAG_KEEP_VERTS"); return JRR_ERR_STATE; }
-  if (e->verts_partial && !(e->have_jsup && e->jsup_fits_known)) {
+  if (!e->st.stored_verts_usable()) {
     jrr_set_error("dJ: the stored vertices are those of a J step over the regressor's support; run jrr_find_joints_forward first");
     return JRR_ERR_STATE;
   }
   // over the regressor's support when its lists fit (jreg.hip, "J step over the regressor's SUPPORT"), else the dense product
-  const int* sflag = e->have_jsup ? e->jsup.flag : nullptr;
-  if (e->have_jsup) launch_jgrad_sparse(e->jsup, e->dJT, e->VTb, e->dJn, e->BP, s);
-  if (!(e->have_jsup && e->jsup_fits_known)) {      // (known to fit: the dense product and its slab sum are not even enqueued)
+  const int* sflag = e->st.have_jsup() ? e->jsup.flag : nullptr;
+  if (e->st.have_jsup()) launch_jgrad_sparse(e->jsup, e->dJT, e->VTb, e->dJn, e->BP, s);
+  if (!e->st.support_known()) {      // (known to fit: the dense product and its slab sum are not even enqueued)
     int rc = launch_jgrad_q(e->dJT, e->VTb, e->dJnp, e->BP, e->nsplitJ, s, sflag);
     if (rc) return rc;
     hipLaunchKernelGGL(k_djn_reduce, dim3((NH * VP + 255) / 256), dim3(256), 0, s, e->dJnp, 3 * e->nsplitJ, e->dJn, sflag);
   }
-  launch_jreg_bwd(e->Jraw, e->have_mask ? e->Jmask : nullptr, e->Jn, e->rowsum, e->dJn, VP, dJ, e->m.v2p, s,
+  launch_jreg_bwd(e->Jraw, e->st.have_mask() ? e->Jmask : nullptr, e->Jn, e->rowsum, e->dJn, VP, dJ, e->m.v2p, s,
                   dJs ? &e->jsup : nullptr, e->m.p2v, dJs);      // dJs: the same gradient on the support lists, same launch
   CHECK_LAUNCH();
   return JRR_OK;
@@ -466,7 +464,7 @@ int jrr::j_grad_from_verts(jrr_engine* e, float* dJ, hipStream_t s, float* dJs) 
 extern "C" int jrr_j_regressor_grad(jrr_engine_t* e, const float* x6d, const float* betas, const float* gt_mm,
                                     float* dJ, float* sqerr, float* joints, void* stream) {
   if (!e || !x6d || !betas || !gt_mm || !dJ) return JRR_ERR_ARG;
-  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
+  if (!e->st.have_J()) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
   if (!(e->flags & JRR_FLAG_KEEP_VERTS)) { jrr_set_error("J step requires JRR_FLAG_KEEP_VERTS"); return JRR_ERR_STATE; }
   return j_step_local(e, x6d, betas, gt_mm, dJ, sqerr, (hipStream_t)stream, joints);
 }
@@ -475,10 +473,8 @@ extern "C" int jrr_j_regressor_grad(jrr_engine_t* e, const float* x6d, const flo
 // joints the driver evaluates after the step (scripts/optimize.py:317-321) without a second SMPL forward
 extern "C" int jrr_find_joints_after_j_step(jrr_engine_t* e, const float* x6d, const float* betas, float* joints, void* stream) {
   if (!e || !x6d || !betas || !joints) { jrr_set_error("find_joints_after_j_step: null"); return JRR_ERR_ARG; }
-  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
-  const bool ok = e->fwd_cached && e->fc_x6d == x6d && e->fc_betas == betas && e->VTb != nullptr &&
-                  !(e->verts_partial && !(e->have_jsup && e->jsup_fits_known));
-  if (!ok) {
+  if (!e->st.have_J()) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
+  if (!(e->st.stored_forward_is(x6d, betas) && e->VTb != nullptr && e->st.stored_verts_usable())) {
     jrr_set_error("find_joints_after_j_step: the previous forward on this engine was not a J step (jrr_j_regressor_grad*) on the same pose buffers");
     return JRR_ERR_STATE;
   }
@@ -486,7 +482,7 @@ extern "C" int jrr_find_joints_after_j_step(jrr_engine_t* e, const float* x6d, c
   int rc = joints_from_stored_verts(e, s);
   if (rc) return rc;
   launch_joints_loss(e->dFTp, e->nsplit, nullptr, nullptr, 0.f, joints, nullptr, nullptr, e->B, e->BP, s, nullptr, 32,
-                     e->have_jsup ? e->jsup.flag : nullptr);
+                     e->st.have_jsup() ? e->jsup.flag : nullptr);
   CHECK_LAUNCH();
   return JRR_OK;
 }
@@ -494,7 +490,7 @@ extern "C" int jrr_find_joints_after_j_step(jrr_engine_t* e, const float* x6d, c
 // ---- the J step's all-reduce payload restricted to the regressor's support (include/jrr.h) ----
 extern "C" int jrr_j_support_info(jrr_engine_t* e, int32_t* counts_host, int32_t* fits_host, void* stream) {
   if (!e || !fits_host) return JRR_ERR_ARG;
-  if (!e->have_jsup || !e->have_J) { jrr_set_error("j_support_info: needs JRR_FLAG_KEEP_VERTS and a regressor"); return JRR_ERR_STATE; }
+  if (!e->st.have_jsup() || !e->st.have_J()) { jrr_set_error("j_support_info: needs JRR_FLAG_KEEP_VERTS and a regressor"); return JRR_ERR_STATE; }
   int32_t cnt[32] = {0}, flag = 0;
   JRR_HIP(hipStreamSynchronize((hipStream_t)stream));
   JRR_HIP(hipMemcpy(cnt, e->jsup.cnt, NH * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -506,7 +502,7 @@ extern "C" int jrr_j_support_info(jrr_engine_t* e, int32_t* counts_host, int32_t
     JRR_HIP(hipMemcpy(&err, e->jsup.flag + JSUP_ERR, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (err) {
       JRR_HIP(hipMemset(e->jsup.flag + JSUP_ERR, 0, 2 * sizeof(int32_t)));      // error word and KNOWN
-      e->jsup_fits_known = false; e->act_valid = false; e->sup_valid = false; e->fwd_cached = false;
+      e->st.support_grew_unannounced();
       jrr_set_error("the J_regressor's support GREW behind the engine's back (%s): J or its mask was edited in place after "
                     "jrr_j_support_info; results since then are invalid -- announce a changed regressor with jrr_engine_set_j_regressor",
                     (err & 2) ? "a row no longer fits the support lists" : "entries outside the reported tiles");
@@ -515,8 +511,7 @@ extern "C" int jrr_j_support_info(jrr_engine_t* e, int32_t* counts_host, int32_t
   }
   if (counts_host) for (int i = 0; i < NH; ++i) counts_host[i] = cnt[i];
   *fits_host = flag;
-  e->jsup_fits_known = flag != 0;      // stays true under J steps (ReLU' = 0: Adam never re-activates an entry); cleared by set_j_regressor
-  e->act_valid = false; e->sup_valid = false;
+  e->st.support_reported(flag != 0);
   {   // the baseline the device checks later supports against (k_jsup_tilemask)
     const int32_t known = flag ? 1 : 0;
     if (flag) JRR_HIP(hipMemcpy(e->jsup.tknown, e->jsup.tmask, VT * sizeof(int32_t), hipMemcpyDeviceToDevice));
@@ -529,7 +524,7 @@ extern "C" int jrr_j_support_info(jrr_engine_t* e, int32_t* counts_host, int32_t
     for (int t = 0; t < VT; ++t) if (tm[t]) list[n++] = t;
     if (n > 0) {
       JRR_HIP(hipMemcpy(e->act_list, list, n * sizeof(int32_t), hipMemcpyHostToDevice));
-      e->nact = n; e->act_valid = true;
+      e->st.tile_list_built(n);
     }
     // the support's VERTICES (union of the rows' lists): up to SUP_NSV of them run the per-vertex iteration (supk.h).  J steps only
     // shrink the support, so the set stays a superset; the regressor's values are read live (Jn_vi) at every iteration.
@@ -550,7 +545,7 @@ extern "C" int jrr_j_support_info(jrr_engine_t* e, int32_t* counts_host, int32_t
         JRR_HIP(hipMemcpy(e->sup.rows, rows.data(), rows.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         launch_sup_gather(e->m, e->sup, (int)rows.size(), (hipStream_t)stream);
         JRR_HIP(hipStreamSynchronize((hipStream_t)stream));
-        e->sup_nsv = (int)rows.size(); e->sup_valid = true;
+        e->st.support_tables_built((int)rows.size());
       }
     }
   }
@@ -560,23 +555,23 @@ extern "C" int jrr_j_support_info(jrr_engine_t* e, int32_t* counts_host, int32_t
 extern "C" int jrr_engine_support_tiles(const jrr_engine_t* e, int32_t* n_tiles_host) {
   if (!e) return JRR_ERR_ARG;
   const bool on = use_tile_list(e);
-  if (n_tiles_host) *n_tiles_host = on ? e->nact : VT;
+  if (n_tiles_host) *n_tiles_host = on ? e->st.nact() : VT;
   return on ? 1 : 0;
 }
 
 extern "C" int jrr_engine_support_vertices(const jrr_engine_t* e, int32_t* n_vertices_host) {
   if (!e) return JRR_ERR_ARG;
   const bool on = use_sup_vertices(e);
-  if (n_vertices_host) *n_vertices_host = on ? e->sup_nsv : 0;
+  if (n_vertices_host) *n_vertices_host = on ? e->st.sup_nsv() : 0;
   return on ? 1 : 0;
 }
 
 extern "C" int jrr_j_regressor_grad_support(jrr_engine_t* e, const float* x6d, const float* betas, const float* gt_mm,
                                             float* dJs, float* sqerr, float* joints, void* stream) {
   if (!e || !x6d || !betas || !gt_mm || !dJs) return JRR_ERR_ARG;
-  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
+  if (!e->st.have_J()) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
   if (!(e->flags & JRR_FLAG_KEEP_VERTS)) { jrr_set_error("J step requires JRR_FLAG_KEEP_VERTS"); return JRR_ERR_STATE; }
-  if (!e->jsup_fits_known) { jrr_set_error("j_regressor_grad_support: call jrr_j_support_info first (it must report fits = 1)"); return JRR_ERR_STATE; }
+  if (!e->st.support_known()) { jrr_set_error("j_regressor_grad_support: call jrr_j_support_info first (it must report fits = 1)"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
   return j_step_local(e, x6d, betas, gt_mm, e->dJraw, sqerr, s, joints, dJs, true);
 }
@@ -584,7 +579,7 @@ extern "C" int jrr_j_regressor_grad_support(jrr_engine_t* e, const float* x6d, c
 extern "C" int jrr_j_step_apply_support(jrr_engine_t* e, float* J, const float* dJs, float* m, float* v, int32_t* step, float lr,
                                         const float* mask, void* stream) {
   if (!e || !J || !dJs || !m || !v || !step) { jrr_set_error("j_step_apply_support: null"); return JRR_ERR_ARG; }
-  if (!(e->flags & JRR_FLAG_KEEP_VERTS) || !e->jsup_fits_known) { jrr_set_error("j_step_apply_support: call jrr_j_support_info first (KEEP_VERTS engine, fits = 1)"); return JRR_ERR_STATE; }
+  if (!e->st.support_known()) { jrr_set_error("j_step_apply_support: call jrr_j_support_info first (KEEP_VERTS engine, fits = 1)"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
   // the dense gradient the optimiser sees: zero outside the support (exactly what the dense path holds there), the
   // all-reduced values on it (scattered inside the update kernel).  Adam itself stays dense: entries that left the support
@@ -604,21 +599,17 @@ extern "C" int jrr_j_step_apply(jrr_engine_t* e, float* J, const float* dJ, floa
 
 int jrr::j_step_apply(jrr_engine* e, float* J, const float* dJ, float* m, float* v, int32_t* step, float lr, const float* mask, hipStream_t s,
                       const float* dJs) {
-  const bool cached = e->fwd_cached, known = e->jsup_fits_known && mask == e->jsup_mask;
-  if (!known && e->have_jsup) JRR_HIP(hipMemsetAsync(e->jsup.flag + JSUP_KNOWN, 0, sizeof(int32_t), s));   // (another mask: no baseline to hold the new support against)
-  if (e->have_jsup && e->have_J && e->tab_static) {
+  if (!e->st.support_known_under(mask) && e->st.have_jsup()) JRR_HIP(hipMemsetAsync(e->jsup.flag + JSUP_KNOWN, 0, sizeof(int32_t), s));   // (another mask: no baseline to hold the new support against)
+  if (e->st.have_jsup() && e->st.have_J() && e->st.tab_static()) {
     // Adam, the engine's copy, the row sums, the normalised layouts and the support lists in ONE launch (jreg.hip k_jstep_update)
     JStepUpdate a;
     a.J = J; a.dJ = dJ; a.dJs = dJs; a.m = m; a.v = v; a.step = step; a.lr = lr;
     a.mask = mask; a.Jraw = e->Jraw; a.Jmask = e->Jmask; a.rowsum = e->rowsum; a.Jn = e->Jn; a.Jn_vi = e->Jn_vi; a.Jn_iv = e->Jn_iv;
-    a.Jn_q = e->Jn_q; a.p2v = e->m.p2v; a.v2p = e->m.v2p; a.r16 = (e->m.kjs && e->m.bwd16) ? 1 : 0;
+    a.Jn_q = e->Jn_q; a.p2v = e->m.p2v; a.v2p = e->m.v2p; a.r16 = uses_r16(e->m) ? 1 : 0;
     a.sup = e->jsup; a.sync = e->jsup.flag + 1;
     launch_jstep_update(a, s);
-    e->have_mask = mask != nullptr;
-    e->jsup_mask = mask;
-    e->jsup_fits_known = known;      // the stepped regressor's support is a subset of the old one (ReLU' = 0 outside it; same mask)
-    e->fold_valid = false;
-    if (e->folded) { int rcf = fold_rebuild(e, s); if (rcf) return rcf; }
+    e->st.regressor_stepped(mask);
+    if (e->st.folded()) { int rcf = fold_rebuild(e, s); if (rcf) return rcf; }
     CHECK_LAUNCH();
     return JRR_OK;
   }
@@ -629,10 +620,7 @@ int jrr::j_step_apply(jrr_engine* e, float* J, const float* dJ, float* m, float*
   }
   // Adam with step + 1; the counter itself is incremented by the normalisation's first launch (one launch less per J step)
   launch_adam_flat(J, dJ, m, v, (size_t)NH * V, step, lr, 0.9f, 0.999f, 1e-8f, s, 1);
-  int rc = set_j_regressor_impl(e, J, mask, (void*)s, step);
-  e->fwd_cached = cached;
-  e->jsup_fits_known = known;      // the stepped regressor's support is a subset of the old one (ReLU' = 0 outside it; same mask)
-  return rc;
+  return set_j_regressor_impl(e, J, mask, (void*)s, step);      // (step != NULL: the rules of a J step, EngineState::regressor_stepped)
 }
 
 int jrr::j_step_local(jrr_engine* e, const float* x6d, const float* betas, const float* gt_mm, float* dJ, float* sqerr, hipStream_t s,
@@ -641,10 +629,10 @@ int jrr::j_step_local(jrr_engine* e, const float* x6d, const float* betas, const
   // the step is the engine's own -- the in-call J steps and the support-sized pair): when the regressor's support is known to fit
   // the lists, both consumers (k_jgrad_sparse here, k_rejoints_sparse in the reusing iteration) read support rows only -- the forward
   // stores the tiles that hold one (a few dozen of 216) instead of 340 MB at 4096 poses
-  const bool few = support_verts && e->have_jsup && e->jsup_fits_known;
+  const bool few = support_verts && e->st.support_known();
   const bool listed = use_tile_list(e);             // ... and with JRR_FLAG_SUPPORT_TILES nothing but those tiles is computed (any caller: the engine was created for it)
-  smpl_forward(e, x6d, nullptr, betas, true, true, nullptr, s, few ? e->jsup.tmask : nullptr, listed ? e->act_list : nullptr, listed ? e->nact : 0);
-  e->fwd_cached = true; e->fc_x6d = x6d; e->fc_betas = betas;
+  smpl_forward(e, x6d, nullptr, betas, true, true, nullptr, s, few ? e->jsup.tmask : nullptr, listed ? e->act_list : nullptr, listed ? e->st.nact() : 0);
+  e->st.forward_stored(x6d, betas);
   const float scale = (float)(2.0 * 1.0 / ((double)e->bnorm * 51.0));   // optimize.py:307 unweighted MSE
   launch_joints_loss(e->JP, e->nvc, gt_mm, nullptr, scale, joints ? joints : e->joints, sqerr ? sqerr : e->sqerr, e->dJT, e->B, e->BP, s);
   return j_grad_from_verts(e, dJ, s, dJs);

@@ -736,7 +736,7 @@ extern "C" int jrr_silhouette_forward(jrr_engine_t* e, const float* verts, const
   int rc = sil_check(e);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   launch_sil_project(verts, V * 3, cam, e->ndc, e->B, s, e->sil);
   launch_sil_raster(e->ndc, e->m.faces_pk, e->m.nfaces, e->cover, e->ncover, alpha, e->B, s, e->sil);
   CHECK_LAUNCH();
@@ -748,7 +748,7 @@ extern "C" int jrr_silhouette_backward(jrr_engine_t* e, const float* galpha, flo
   int rc = sil_check(e);
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   launch_sil_bwd(e->ndc, e->m.faces, e->cover, e->ncover, nullptr, galpha, 0.f, dverts, V * 3, dcam, 0, e->B, s, e->sil);
   CHECK_LAUNCH();
   return JRR_OK;
@@ -758,6 +758,7 @@ extern "C" int jrr_silhouette_pix_to_face(jrr_engine_t* e, int32_t* p2f, void* s
   if (!e || !p2f) return JRR_ERR_ARG;
   int rc = sil_check(e);
   if (rc) return rc;
+  // (reads the coverage lists and writes the caller's buffer only: a J step's stored forward stays)
   launch_sil_pix_to_face(e->cover, e->ncover, p2f, e->B, (hipStream_t)stream, e->sil);
   CHECK_LAUNCH();
   return JRR_OK;
@@ -765,7 +766,7 @@ extern "C" int jrr_silhouette_pix_to_face(jrr_engine_t* e, int32_t* p2f, void* s
 
 extern "C" int jrr_engine_set_silhouette(jrr_engine_t* e, const float* mask, float* cam, float* cam_m, float* cam_v) {
   if (!e) return JRR_ERR_ARG;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   if (mask) {
     int rc = sil_check(e);
     if (rc) return rc;
@@ -778,7 +779,7 @@ extern "C" int jrr_engine_set_silhouette(jrr_engine_t* e, const float* mask, flo
     e->cam = cam; e->cam_m = cam_m; e->cam_v = cam_v;
   }
   e->sil_mask = mask;
-  e->smask_valid = false;          // sum(mask^2) per pose: recomputed on the stream of the next jrr_refine_run
+  e->st.silhouette_mask_changed();          // sum(mask^2) per pose: recomputed on the stream of the next jrr_refine_run
   return JRR_OK;
 }
 
@@ -790,13 +791,13 @@ extern "C" int jrr_silhouette_loss_grad(jrr_engine_t* e, const float* x6d, const
   if (!e || !x6d || !betas || !cam || !mask) { jrr_set_error("silhouette_loss_grad: null"); return JRR_ERR_ARG; }
   int rc = sil_check(e);
   if (rc) return rc;
-  if (!e->have_J) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
+  if (!e->st.have_J()) { jrr_set_error("J_regressor not set"); return JRR_ERR_STATE; }
   if (!e->VTb) { jrr_set_error("silhouette_loss_grad needs JRR_FLAG_KEEP_VERTS"); return JRR_ERR_STATE; }
   hipStream_t s = (hipStream_t)stream;
-  e->fwd_cached = false;
+  e->st.workspace_overwritten();
   smpl_forward(e, x6d, nullptr, betas, true, true, nullptr, s, nullptr, nullptr, 0, true);      // vertices pose-major, as in the loop
   launch_mask_sq(mask, e->smask, e->B, s, e->sil);
-  e->smask_valid = false;
+  e->st.silhouette_mask_changed();
   const float silscale = (float)(2.0 * 100.0 / ((double)e->bnorm * (double)e->sil * (double)e->sil));      // optimize.py:252 weight 100
   { int rcs = launch_sil_raster_adj(e->VTb, e->BP, cam, e->m.faces_int_pk ? e->m.faces_int_pk : e->m.faces_pk, e->m.nfaces, mask, e->smask, e->cover,
                                     e->ncover, e->sqsil, silscale, e->gcam, 0, e->B, s, e->sil, e->VPM);

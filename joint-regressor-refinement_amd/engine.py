@@ -6,6 +6,7 @@ engine workspace, and kernels are enqueued on torch's current stream.
 from __future__ import annotations
 
 import ctypes
+import functools
 from ctypes import byref, c_int32, c_void_p
 from typing import Dict, Optional
 
@@ -112,6 +113,17 @@ class DeviceModel:
             pass
 
 
+def overwrites_forward_state(method):
+    """Marks a RefineEngine wrapper whose call overwrites what the adjoint entry points read of the MOST RECENT forward
+    (RefineEngine.generation): the counter is bumped before the call, so a call that raises has bumped it too."""
+    @functools.wraps(method)
+    def wrapper(self, *args, **kwargs):
+        self.generation += 1
+        return method(self, *args, **kwargs)
+    wrapper.overwrites_forward_state = True
+    return wrapper
+
+
 class RefineEngine:
     """Per-batch plan over a caller-owned (torch) workspace: jrr_engine_*."""
 
@@ -127,7 +139,7 @@ class RefineEngine:
         self.sil = 32 * ((self.flags >> 16) & 15) or (256 if (self.flags & FLAG_SIL_256) else SIL)      # silhouette image size of this engine
         # Forward-generation counter: the adjoint entry points read the engine's internal state of the MOST RECENT
         # forward (include/jrr.h: "must follow it"), while autograd defers backward.  Every call that overwrites that
-        # state bumps the counter; the autograd wrappers compare it with the value saved at forward time and re-run
+        # state bumps the counter (@overwrites_forward_state); the autograd wrappers compare it with the value saved at forward time and re-run
         # the forward from their saved inputs when it has moved (utils._FindJointsFn, smpl._SMPLVerticesFn,
         # discriminator._PoseDiscFn).
         self.generation = 0
@@ -171,26 +183,27 @@ class RefineEngine:
         """refine_run through the folded regressor tables (engine must have FLAG_FOLDED)"""
         check(self.lib.jrr_engine_set_folded(self.handle, int(bool(enabled)), self._s()), 'set_folded')
 
+    @overwrites_forward_state
     def set_j_regressor(self, J: torch.Tensor, mask: Optional[torch.Tensor] = None):
-        self.generation += 1
         J = J.detach().to(self.device, torch.float32).contiguous()      # any stride / device tag
         self._chk(J, (NUM_H36M, NUM_VERTS), 'J_regressor')
         if mask is not None:
             mask = self._chk(mask.detach().to(self.device, torch.float32).contiguous(), (NUM_H36M, NUM_VERTS), 'mask')
         check(self.lib.jrr_engine_set_j_regressor(self.handle, ptr(J), ptr(mask), self._s()), 'set_j_regressor')
 
+    @overwrites_forward_state
     def set_pose_disc(self, flat: torch.Tensor):
-        self.generation += 1
         flat = self._chk(flat.detach().to(self.device, torch.float32).contiguous(), (DISC_PARAMS,), 'disc params')
         check(self.lib.jrr_engine_set_pose_disc(self.handle, ptr(flat), self._s()), 'set_pose_disc')
 
     def set_shape_disc(self, flat: torch.Tensor):
+        # no generation bump: the upload overwrites the parameter block Ps alone, and no shape-D operator keeps forward state
         flat = self._chk(flat.detach().to(self.device, torch.float32).contiguous(), (SHAPE_DISC_PARAMS,), 'shape disc params')
         check(self.lib.jrr_engine_set_shape_disc(self.handle, ptr(flat), self._s()), 'set_shape_disc')
 
     # -- operators --------------------------------------------------------------------------
+    @overwrites_forward_state
     def find_joints_forward(self, betas, x6d=None, R=None, return_verts=False):
-        self.generation += 1
         B = self.batch
         self._chk(betas, (B, NUM_BETAS), 'betas')
         if x6d is not None:
@@ -214,8 +227,8 @@ class RefineEngine:
                                                 ptr(db), ptr(dJ), self._s()), 'find_joints_backward')
         return (dx if x6d is not None else dR), db, dJ
 
+    @overwrites_forward_state
     def pose_disc_forward(self, x6d):
-        self.generation += 1
         self._chk(x6d, (self.batch, NUM_JOINTS, 6), 'x6d')
         out = torch.empty(self.batch, 25, device=self.device)
         check(self.lib.jrr_pose_disc_forward(self.handle, ptr(x6d), ptr(out), self._s()), 'pose_disc_forward')
@@ -227,9 +240,9 @@ class RefineEngine:
                                                     self._s()), 'pose_disc_backward_input')
         return dx
 
+    @overwrites_forward_state
     def pose_disc_backward_params(self, x6d, target: float, dparams: torch.Tensor):
         """dparams += d mean((D(x)-target)^2)/d weights; returns per-pose sum_k (D-target)^2"""
-        self.generation += 1
         self._chk(x6d, (self.batch, NUM_JOINTS, 6), 'x6d')
         self._chk(dparams, (DISC_PARAMS,), 'dparams')
         sq = torch.empty(self.batch, device=self.device)
@@ -245,9 +258,9 @@ class RefineEngine:
               'shape_disc_backward_params')
         return sq
 
+    @overwrites_forward_state
     def pose_disc_vjp_params(self, x6d, gout, dparams: torch.Tensor):
         """dparams += (dD/dweights)^T gout for an upstream gradient gout (B,25); runs its own forward"""
-        self.generation += 1
         self._chk(x6d, (self.batch, NUM_JOINTS, 6), 'x6d')
         self._chk(gout, (self.batch, 25), 'gout')
         self._chk(dparams, (DISC_PARAMS,), 'dparams')
@@ -331,16 +344,16 @@ class RefineEngine:
         self._reproj_refs = (gt_j2d, cam, cam_m, cam_v)
         check(self.lib.jrr_engine_set_reprojection(self.handle, ptr(gt_j2d), ptr(cam), ptr(cam_m), ptr(cam_v)), 'set_reprojection')
 
+    @overwrites_forward_state
     def camera_prefit(self, x6d, betas, gt_j2d, cam, n_steps: int = 1000, lr: float = 1e-2):
-        self.generation += 1
         sq = torch.empty(self.batch, device=self.device)
         check(self.lib.jrr_camera_prefit(self.handle, ptr(x6d), ptr(betas), ptr(gt_j2d), ptr(cam), int(n_steps), float(lr),
                                          ptr(sq), self._s()), 'camera_prefit')
         return sq
 
+    @overwrites_forward_state
     def silhouette_forward(self, verts, cam):
         """render_mesh alpha channel: verts (B,6890,3) in SMPL space, cam (B,3) -> (B,S,S), S = 224 (256 with FLAG_SIL_256)"""
-        self.generation += 1
         self._chk(verts, (self.batch, NUM_VERTS, 3), 'verts')
         self._chk(cam, (self.batch, 3), 'cam')
         alpha = torch.empty(self.batch, self.sil, self.sil, device=self.device)
@@ -360,10 +373,10 @@ class RefineEngine:
         check(self.lib.jrr_silhouette_pix_to_face(self.handle, ptr(p2f), self._s()), 'silhouette_pix_to_face')
         return p2f
 
+    @overwrites_forward_state
     def silhouette_loss_grad(self, x6d, betas, cam, mask, want_dverts=True):
         """the silhouette term as the fused loop evaluates it: per-pose sum (silhouette - mask)^2, d/dverts (B,6890,3) and
         d/dcam (B,3) of 100 * mean((silhouette - mask)^2)  (jrr_silhouette_loss_grad)"""
-        self.generation += 1
         B = self.batch
         self._chk(x6d, (B, NUM_JOINTS, 6), 'x6d'); self._chk(betas, (B, NUM_BETAS), 'betas')
         self._chk(cam, (B, 3), 'cam'); self._chk(mask, (B, self.sil, self.sil), 'mask')
@@ -392,24 +405,24 @@ class RefineEngine:
         self._chk(adam_v, (B, 154), 'adam_v')
         assert step.dtype == torch.int32 and step.is_cuda
 
+    @overwrites_forward_state
     def refine_run(self, x6d, betas, gt_centred_mm, adam_m, adam_v, step, lr: float, n_iters: int, sqerr=None,
                    after_j_step: bool = False):
         """n_iters inner iterations in ONE C call.  after_j_step=True (jrr_refine_run_after_j_step): the caller states that
         the previous call on this engine was j_regressor_grad (+ j_step_apply) on these very buffers; the first iteration
         then reuses that forward.  A mismatch the engine can detect raises instead of reusing a stale forward."""
-        self.generation += 1
         self._refine_args(x6d, betas, gt_centred_mm, adam_m, adam_v, step)
         fn = self.lib.jrr_refine_run_after_j_step if after_j_step else self.lib.jrr_refine_run
         check(fn(self.handle, ptr(x6d), ptr(betas), ptr(gt_centred_mm), ptr(adam_m), ptr(adam_v),
                  ptr(step), float(lr), int(n_iters), ptr(sqerr), self._s()), 'refine_run')
 
+    @overwrites_forward_state
     def refine_run_j_steps(self, x6d, betas, gt_centred_mm, adam_m, adam_v, step, lr: float, n_iters: int, j_every: int,
                            J, J_m, J_v, J_step, j_lr: float, mask=None, sqerr=None, j_sqerr=None, after_j_step: bool = False,
                            reuse_forward: bool = True):
         """the inner loop with a J step after every j_every-th iteration, all inside ONE C call (single process only:
         there is no collective between the two halves of a J step); J / J_m / J_v / J_step are updated in place.
         reuse_forward=False: the iteration after a J step repeats its SMPL forward (include/jrr.h, after_j_step bit 1)"""
-        self.generation += 1
         self._refine_args(x6d, betas, gt_centred_mm, adam_m, adam_v, step)
         for t, n in ((J, 'J'), (J_m, 'J_m'), (J_v, 'J_v')):
             self._chk(t, (NUM_H36M, NUM_VERTS), n)
@@ -420,9 +433,9 @@ class RefineEngine:
                                               int(bool(after_j_step)) | (0 if reuse_forward else 2),
                                               self._s()), 'refine_run_j_steps')
 
+    @overwrites_forward_state
     def j_step_apply(self, J, dJ, J_m, J_v, J_step, lr: float, mask=None):
         """second half of the J step: Adam on the raw regressor with the (all-reduced) gradient + re-normalisation, one call"""
-        self.generation += 1
         for t, n in ((J, 'J'), (dJ, 'dJ'), (J_m, 'J_m'), (J_v, 'J_v')):
             self._chk(t, (NUM_H36M, NUM_VERTS), n)
         assert J_step.dtype == torch.int32 and J_step.is_cuda
@@ -490,16 +503,16 @@ class RefineEngine:
             check(rc, 'support_vertices')
         return bool(rc), int(n.value)
 
+    @overwrites_forward_state
     def j_regressor_grad_support(self, x6d, betas, gt_centred_mm, out, sqerr=None, joints=None):
         """j_regressor_grad with the gradient delivered on the support only: out (17,128)"""
-        self.generation += 1
         self._chk(out, (NUM_H36M, self.J_SUPPORT_CAP), 'dJs')
         check(self.lib.jrr_j_regressor_grad_support(self.handle, ptr(x6d), ptr(betas), ptr(gt_centred_mm), ptr(out), ptr(sqerr),
                                                     ptr(joints), self._s()), 'j_regressor_grad_support')
         return out
 
+    @overwrites_forward_state
     def j_step_apply_support(self, J, dJs, J_m, J_v, J_step, lr: float, mask=None):
-        self.generation += 1
         for t, n in ((J, 'J'), (J_m, 'J_m'), (J_v, 'J_v')):
             self._chk(t, (NUM_H36M, NUM_VERTS), n)
         self._chk(dJs, (NUM_H36M, self.J_SUPPORT_CAP), 'dJs')
@@ -507,10 +520,10 @@ class RefineEngine:
         check(self.lib.jrr_j_step_apply_support(self.handle, ptr(J), ptr(dJs), ptr(J_m), ptr(J_v), ptr(J_step), float(lr), ptr(mask),
                                                 self._s()), 'j_step_apply_support')
 
+    @overwrites_forward_state
     def j_regressor_grad(self, x6d, betas, gt_centred_mm, sqerr=None, out=None, joints=None):
         """local dJ (first half of the J step); `out` (17,6890): write into a caller-owned buffer (e.g. a slice of the flat
         all-reduce bucket) instead of allocating; `joints` (B,17,3): receives the joints of this forward (old regressor)"""
-        self.generation += 1
         dJ = out if out is not None else torch.empty(NUM_H36M, NUM_VERTS, device=self.device)
         self._chk(dJ, (NUM_H36M, NUM_VERTS), 'dJ')
         if joints is not None:
