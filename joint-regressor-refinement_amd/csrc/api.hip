@@ -1,5 +1,5 @@
 // The engine behind the C ABI (include/jrr.h): error plumbing, run-time knobs, engine / workspace planning, the regressor upload, the
-// SMPL operators, and the small operators whose kernels live in the hot-path file prep.hip.  Every other entry point sits in the file
+// SMPL operators, and the small operators whose kernels live in rot.hip, chain.hip, loss.hip and flat.hip.  Every other entry point sits in the file
 // of the kernels it launches; the body-model re-layout is model.hip, the fused inner loop and the J step refine.hip (shared: engine.h).
 #include <algorithm>
 #include <cstdarg>

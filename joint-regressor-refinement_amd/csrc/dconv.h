@@ -1,5 +1,5 @@
 // Per-joint shared MLP of the pose discriminator on the matrix cores: device bodies shared by the stand-alone kernels
-// (disc.hip) and the horizontally fused launches of the inner loop (prep.hip).
+// (disc.hip) and the horizontally fused and composed launches of the inner loop (chain.hip, supk.h).
 #pragma once
 #include "jrr_common.h"
 #include "kernels.h"

@@ -36,7 +36,7 @@ struct jrr_engine {
   float* hist; int hist_cap, hist_every, hist_n; long long hist_iter;   // loss history (jrr_engine_set_loss_history)
   float *VTb;       // [3][VP][BP] vertices / transposed vertex adjoint (KEEP_VERTS or SILHOUETTE)
   float *dVTb, *dJnp, *dJn;   // transposed external vertex adjoint [3][VP][BP]; J-gradient partial slabs [3*nsplitJ][32][VP]
-  int32_t* step_scratch;      // arrival counter of k_sup_step's step-count protocol (prep.hip), its only user
+  int32_t* step_scratch;      // arrival counter of k_sup_step's step-count protocol (chain.hip), its only user
   bool profiling;
   // JRR_FLAG_SUPPORT_TILES: the 32-vertex tiles that hold an entry of the regressor's support (ascending), taken when
   // jrr_j_support_info reports that the support fits; J steps only shrink the support, so the list stays a superset

@@ -1,9 +1,10 @@
-// Internal launcher interface: the launch_* functions that cross a translation unit, i.e. the kernels of prep / lbs_fwd / lbs_bwd / jreg / gemm / sup / fold
-// and the few of disc / sil that the engine (api.hip) and the fused loop (refine.hip) launch.  A launcher with no caller outside the file
-// of its kernel is static there and is not listed; the feature files (image, report, shade, export, eval, evalrep, regrep, smooth, views, accel) keep
-// their include/jrr.h entry points beside their kernels and declare nothing here.
+// Internal launcher interface: the launch_* functions that cross a translation unit, i.e. the kernels of rot / chain / loss / flat / lbs_fwd / lbs_bwd /
+// jreg / gemm / sup / fold and the few of disc / sil that the engine (api.hip) and the fused loop (refine.hip) launch.  A launcher with no caller
+// outside the file of its kernel is static there and is not listed; the feature files (image, report, shade, export, eval, evalrep, regrep, smooth,
+// views, accel) keep their include/jrr.h entry points beside their kernels and declare nothing here.
 #pragma once
 #include "jrr_common.h"
+#include "proj.h"      // Reproj: the 2-D reprojection term of the joint loss, as the launchers and their kernels take it
 
 namespace jrr {
 
@@ -35,29 +36,35 @@ struct GemmArgs {
   float* dot_out = nullptr;          // [(M/BM) * WAVES_M][ldo] partial column dots (EPI_BIAS_RELU_DOT)
 };
 
-struct PrepBwdLaunch {
-  const float* x6d_in = nullptr; const float* R_in = nullptr; const float* betas_in = nullptr;
+// The per-pose update that closes the chain adjoint (chaink.h, pose_update_*): the argument k_chain_bwd and k_sup_step take by value.
+// A PrepBwdLaunch IS one, so its callers fill these fields once and the launchers pass the base sub-object on.
+struct PoseUpdateArgs {
+  const float* x6d_in = nullptr;      // (B,24,6) or NULL (R mode)
+  const float* gx_extra = nullptr; const float* gb_extra = nullptr;
+  float* dx6d = nullptr; float* dR = nullptr; float* dbetas = nullptr;                 // gradient outputs (nullable)
+  float* x6d_io = nullptr; float* betas_io = nullptr; float* adam_m = nullptr; float* adam_v = nullptr;
+  const int32_t* step = nullptr;                                                         // Adam (x6d_io nullable)
+  float lr = 0, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f;
+  const float* gcam = nullptr; float* cam_io = nullptr; float* cam_m = nullptr; float* cam_v = nullptr;     // camera translation (2-D term), nullable: it steps with the poses
+};
+
+struct PrepBwdLaunch : PoseUpdateArgs {
+  const float* R_in = nullptr; const float* betas_in = nullptr;
   const float* dATp = nullptr; const float* dFTp = nullptr;    // adjoints dA^T [nslabA][288][BP] (partial slabs, summed
   int nslabA = 1; size_t strideA = 0;                           // by k_chain_bwd), dF^T [224][BP] (reduced)
   const unsigned* dmaskA = nullptr;                             // [nslabA][BP / 64] valid-joint masks of the slabs (NULL: all rows valid)
   const float* FT = nullptr; const float* R0T = nullptr; const float* AT = nullptr;   // saved by k_prep_fwd
   float* dRT = nullptr; float* dbT = nullptr;                   // scratch [216][BP], [10][BP]
-  const float* gx_extra = nullptr; const float* gb_extra = nullptr;
-  float* dx6d = nullptr; float* dR = nullptr; float* dbetas = nullptr;
-  float* x6d_io = nullptr; float* betas_io = nullptr; float* adam_m = nullptr; float* adam_v = nullptr;
-  const int32_t* step = nullptr;
-  float lr = 0, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f;
   int B = 0, BP = 0;
-  const float* gcam = nullptr; float* cam_io = nullptr; float* cam_m = nullptr; float* cam_v = nullptr;
 };
 
-struct ReprojLaunch { const float* gt_j2d; const float* cam; float* gcam; float* sq2d; float scale2d; };
-
-// prep.hip
+// rot.hip
 int launch_rot6d_fwd(const float* x, float* R, int n, hipStream_t s);
 int launch_rot6d_bwd(const float* x, const float* dR, float* dx, int n, hipStream_t s);
 int launch_rodrigues_fwd(const float* aa, float* R, int n, hipStream_t s);
 int launch_rodrigues_bwd(const float* aa, const float* dR, float* daa, int n, hipStream_t s);
+
+// chain.hip (bodies: chaink.h; launch_sup_step, the composed launch of the default iteration, is declared with the support tables below)
 // FT: blend features row-major [KFP][BP] (chain adjoint, folded product); FTq: the same in K-quads [KFP/4][BP][4] (k_lbs_fwd)
 int launch_prep_fwd(const Model& m, const float* x6d, const float* Rin, const float* betas, float* FT, float* FTq, float* AT,
                     float* R0T, int B, int BP, int32_t* step_inc, hipStream_t s);
@@ -65,28 +72,32 @@ int launch_posed_joints(const Model& m, const float* AT, const float* betas, flo
 // its adjoint: dj24 (B,24,3) -> dA^T [288][BP] (one slab) and the direct shape term gb (B,10)
 int launch_posed_joints_bwd(const Model& m, const float* AT, const float* betas, const float* dj24, float* dA, float* gb, int B, int BP,
                             hipStream_t s);
-// horizontally fused launches of the inner loop (prep.hip): chain forward || per-joint MLP forward, and
+// horizontally fused launches of the inner loop: chain forward || per-joint MLP forward, and
 // per-joint MLP adjoint || dF^T slab sum
 int launch_prep_fwd_dconv(const Model& m, const float* x6d, const float* betas, float* FT, float* FTq, float* AT, float* R0T, int B,
                           int BP, int32_t* step_inc, const float* img, float* H2T, float* out, hipStream_t s);
 int launch_dconv_bwd_reduce(const float* img, const float* x6d, const float* dH2T, const float* gout, float scale, float target,
                             float* gx, float* sqj, int B, int BP, const float* P, int nslab, size_t stride, float* out, size_t n,
                             hipStream_t s);
+int launch_prep_bwd(const PrepBwdLaunch& L, const Model& m, hipStream_t s);
+
+// loss.hip (rp.gt_j2d == NULL, the default: no 2-D reprojection term)
 int launch_joints_loss(const float* JP, int nvc, const float* gt_mm, const float* djoints_in, float scale,
                        float* joints_out, float* sqerr, float* dJT, int B, int BP, hipStream_t s,
-                       const ReprojLaunch* r = nullptr, int jp_rows = NH, const int* one_slab_flag = nullptr);
-int launch_step_inc(int32_t* step, hipStream_t s);
+                       const Reproj& rp = Reproj{}, int jp_rows = NH, const int* one_slab_flag = nullptr);
 int launch_project_joints(const float* joints, const float* cam, float* out, int B, hipStream_t s);
 int launch_camera_fit(const float* joints, const float* gt_j2d, float* cam, float scale2d, int nsteps, float lr, float* sq2d,
                       int B, hipStream_t s);
 int launch_joint_loss_plain(const float* joints, const float* gt_mm, float scale, float* sqerr, float* djoints, int B,
                             hipStream_t s);
-int launch_prep_bwd(const PrepBwdLaunch& L, const Model& m, hipStream_t s);
+
+// flat.hip
+int launch_step_inc(int32_t* step, hipStream_t s);
+int launch_adam_flat(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step, float lr, float b1,
+                     float b2, float eps, hipStream_t s, int step_plus = 0);
 int launch_reduce_slabs(const float* P, int nslab, size_t stride, float* out, size_t n, hipStream_t s, int accumulate = 0);
 int launch_reduce_slabs2(const float* P1, int nslab1, size_t stride1, float* out1, size_t n1, const float* P2, int nslab2,
                          size_t stride2, float* out2, size_t n2, hipStream_t s);
-int launch_adam_flat(float* p, const float* g, float* m, float* v, size_t n, const int32_t* step, float lr, float b1,
-                     float b2, float eps, hipStream_t s, int step_plus = 0);
 
 // lbs_fwd.hip
 int launch_lbs_fwd(const Model& m, const float* Jn_vi, const float* FT, const float* AT, float* VPb, float* JP,
@@ -184,9 +195,9 @@ int launch_sup_gather(const Model& m, const SupTables& t, int nsv, hipStream_t s
 // one joint-loss forward + backward of the pose groups: F^T (K-quads) / A^T of k_prep_fwd in, joints / squared error / dA^T [288][BP] /
 // dF^T [224][BP] out (what k_chain_bwd reads as ONE slab)
 int launch_sup_iter(const SupTables& t, int nsv, const float* Jn_vi, const float* FTq, const float* AT, const float* gt_mm, float scale,
-                    float* joints_out, float* sqerr, float* dA, float* dF, int B, int BP, hipStream_t s, const ReprojLaunch* r = nullptr);
+                    float* joints_out, float* sqerr, float* dA, float* dF, int B, int BP, hipStream_t s, const Reproj& rp = Reproj{});
 
-// ONE inner iteration per 32-pose group in one launch (prep.hip k_sup_step): chain forward, support-vertex forward / loss / backward,
+// ONE inner iteration per 32-pose group in one launch (chain.hip k_sup_step): chain forward, support-vertex forward / loss / backward,
 // [per-joint MLP adjoint], chain adjoint + Adam, [per-joint MLP forward of the next iteration].  The pose-update half takes a PrepBwdLaunch
 // (x6d_in / betas_in / gx_extra / gb_extra / x6d_io / betas_io / Adam state / step / lr / B / BP).
 struct SupStepLaunch {
@@ -195,8 +206,7 @@ struct SupStepLaunch {
   const float* conv_img = nullptr; const float* dH2T = nullptr; float dscale = 0.f; float* gx = nullptr; float* dsq = nullptr;
   float* H2T_next = nullptr;
   int32_t* step = nullptr; int* arrive = nullptr;      // Adam's step counter (incremented once per launch) and the arrival counter
-  // 2-D reprojection term (nullable gt_j2d: off); the camera's Adam state travels in the PrepBwdLaunch (gcam / cam_io / cam_m / cam_v)
-  const float* gt_j2d = nullptr; const float* cam = nullptr; float* gcam = nullptr; float* sq2d = nullptr; float scale2d = 0.f;
+  Reproj rp;      // 2-D reprojection term (gt_j2d NULL: off); the camera's Adam state travels in the PrepBwdLaunch (gcam / cam_io / cam_m / cam_v)
 };
 // phase 0: the whole iteration; 1 / 2: its halves before / after the point where the discriminator GEMMs' results are read
 int launch_sup_step(const Model& m, const SupStepLaunch& q, const PrepBwdLaunch& L, hipStream_t s, int phase = 0);

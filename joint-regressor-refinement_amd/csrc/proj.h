@@ -1,7 +1,7 @@
 // Perspective projection of the regressed joints and its adjoint (scripts/renderer.py:35-49 with pytorch3d 0.3.0 PerspectiveCameras,
 // R = I, T = cam, focal 5000/224 in NDC, principal point 0, 224x224 screen):
 //   X = -2x + tx, Y = -2y + ty, Z = 2z + tz ;  x_ndc = f X / Z ;  x_screen = (W-1)/2 (1 - x_ndc)  (same for y).
-// Shared by k_joints_loss (prep.hip) and the support-vertex iteration (supk.h).
+// Shared by k_joints_loss (loss.hip) and the support-vertex iteration (supk.h).
 #pragma once
 #include "jrr_common.h"
 
@@ -30,12 +30,13 @@ __device__ __forceinline__ void project_point_bwd(float gxs, float gys, float in
   gt[0] += gX; gt[1] += gY; gt[2] += gZ;
 }
 
+// the 2-D reprojection term as the launchers (kernels.h) and the kernels take it; Reproj{} is the term switched off
 struct Reproj {
-  const float* gt_j2d;   // (B,17,2) or NULL (term disabled)
-  const float* cam;      // (B,3)
-  float* gcam;           // (B,3) out: dL/dcam
-  float* sq2d;           // (B) out: sum of squared 2-D errors (nullable)
-  float scale2d;         // 2*weight/(batch_norm*34)
+  const float* gt_j2d = nullptr;   // (B,17,2) or NULL (term disabled)
+  const float* cam = nullptr;      // (B,3)
+  float* gcam = nullptr;           // (B,3) out: dL/dcam
+  float* sq2d = nullptr;           // (B) out: sum of squared 2-D errors (nullable)
+  float scale2d = 0.f;             // 2*weight/(batch_norm*34)
 };
 
 }  // namespace jrr

@@ -68,6 +68,12 @@ struct RefineCtx {
 };
 
 // ---- pieces every iteration shape is made of ----
+// the 2-D reprojection term (weight 1/100) as the joint-loss kernels take it; without 2-D ground truth it is off
+static Reproj reproj_term(const RefineCtx& c) {
+  jrr_engine* e = c.e;
+  return e->gt_j2d ? Reproj{e->gt_j2d, e->cam, e->gcam, e->sq2d, c.scale2d} : Reproj{};
+}
+
 // pose-D forward + input adjoint (four GEMMs) and the shape-D launch.  conv_done: the per-joint MLP forward is in H2T already;
 // skip_conv: its adjoint runs in a later launch of the caller's
 static int adversarial_terms(const RefineCtx& c, bool conv_done, bool skip_conv) {
@@ -143,7 +149,7 @@ static int ensure_side_stream(jrr_engine* e) {
 
 // ---- iteration shapes ----
 // Support-vertex iteration (supk.h): forward, loss, backward and pose update of a 32-pose group in ONE launch per iteration
-// (+ the four discriminator GEMMs before it): prep.hip k_sup_step.  h2t_ready: the previous iteration's launch left the per-joint
+// (+ the four discriminator GEMMs before it): chain.hip k_sup_step.  h2t_ready: the previous iteration's launch left the per-joint
 // MLP forward of the current poses in H2T; `last`: no iteration of this call follows.
 static int iter_support_step(const RefineCtx& c, bool last, bool& h2t_ready) {
   jrr_engine* e = c.e;
@@ -170,7 +176,7 @@ static int iter_support_step(const RefineCtx& c, bool last, bool& h2t_ready) {
     q.H2T_next = last ? nullptr : e->H2T;
   }
   q.step = c.step; q.arrive = e->step_scratch;
-  if (e->gt_j2d) { q.gt_j2d = e->gt_j2d; q.cam = e->cam; q.gcam = e->gcam; q.sq2d = e->sq2d; q.scale2d = c.scale2d; }      // 2-D term, weight 1/100
+  q.rp = reproj_term(c);
   PrepBwdLaunch L;
   fill_chain_adjoint(c, L, false);
   if (overlap) {
@@ -192,7 +198,7 @@ static int iter_support_step(const RefineCtx& c, bool last, bool& h2t_ready) {
 }
 
 // chain forward (+ Adam's step count) of the chain iterations; with the pose discriminator its per-joint MLP rides in the same launch
-// (two independent latency-bound kernels side by side: prep.hip).  reuse: the forward of the J step before stands; only the count moves.
+// (two independent latency-bound kernels side by side: chain.hip).  reuse: the forward of the J step before stands; only the count moves.
 static void chain_forward(const RefineCtx& c, bool reuse) {
   jrr_engine* e = c.e;
   prof_mark(e, 0, c.s);
@@ -205,9 +211,7 @@ static void chain_forward(const RefineCtx& c, bool reuse) {
 // joints from `nslab` partial slabs of `rows` rows, joint (+ 2-D) loss and the joint adjoint dJT
 static void joints_loss(const RefineCtx& c, const float* partials, int nslab, int rows, const int* one_slab_flag) {
   jrr_engine* e = c.e;
-  ReprojLaunch rl{e->gt_j2d, e->cam, e->gcam, e->sq2d, c.scale2d};   // weight 1/100
-  launch_joints_loss(partials, nslab, c.gt_mm, nullptr, c.jscale, e->joints, c.sqerr, e->dJT, e->B, e->BP, c.s, e->gt_j2d ? &rl : nullptr, rows,
-                     one_slab_flag);
+  launch_joints_loss(partials, nslab, c.gt_mm, nullptr, c.jscale, e->joints, c.sqerr, e->dJT, e->B, e->BP, c.s, reproj_term(c), rows, one_slab_flag);
 }
 
 // the pose update from COMPLETE adjoints dA^T / dF^T (L.dATp / L.dFTp set by the caller) and the forward the chain kept
@@ -262,9 +266,8 @@ static int iter_support_split(const RefineCtx& c) {
   hipStream_t s = c.s;
   chain_forward(c, false);
   prof_mark(e, 1, s);
-  ReprojLaunch rl{e->gt_j2d, e->cam, e->gcam, e->sq2d, c.scale2d};
   int rc = launch_sup_iter(e->sup, e->st.sup_nsv(), e->Jn_vi, e->FTq, e->AT, c.gt_mm, c.jscale, e->joints, c.sqerr, e->dA, e->dF, e->B, e->BP, s,
-                           e->gt_j2d ? &rl : nullptr);
+                           reproj_term(c));
   if (rc) return rc;
   prof_mark(e, 1, s);
   for (int cls = 2; cls <= 4; ++cls) { prof_mark(e, cls, s); prof_mark(e, cls, s); }
@@ -481,7 +484,7 @@ extern "C" int jrr_find_joints_after_j_step(jrr_engine_t* e, const float* x6d, c
   hipStream_t s = (hipStream_t)stream;
   int rc = joints_from_stored_verts(e, s);
   if (rc) return rc;
-  launch_joints_loss(e->dFTp, e->nsplit, nullptr, nullptr, 0.f, joints, nullptr, nullptr, e->B, e->BP, s, nullptr, 32,
+  launch_joints_loss(e->dFTp, e->nsplit, nullptr, nullptr, 0.f, joints, nullptr, nullptr, e->B, e->BP, s, Reproj{}, 32,
                      e->st.have_jsup() ? e->jsup.flag : nullptr);
   CHECK_LAUNCH();
   return JRR_OK;

@@ -1,5 +1,6 @@
 // 6-D rotation representation -> rotation matrix (rot6d_to_rotmat, /root/reference/scripts/utils.py:190-204): the ONE definition
-// shared by the loop's kernels (prep.hip) and the pose export (export.hip), which must see the matrices the loop saw.
+// shared by the loop's kernels (chaink.h, rot.hip) and the pose export (export.hip), which must see the matrices the loop saw.  Its
+// adjoint rot6d_bwd serves the operator (rot.hip) and the fused pose update (chaink.h).
 #pragma once
 
 namespace jrr {
@@ -33,6 +34,50 @@ __device__ __forceinline__ void rot6d_fwd(const float x[6], float R[9], Rot6& c)
     R[r * 3 + 1] = c.b2[r];
     R[r * 3 + 2] = b3[r];
   }
+}
+
+__device__ __forceinline__ void rot6d_bwd(const Rot6& c, const float dR[9], float dx[6]) {
+  const float eps = 1e-12f;
+  float db1[3], db2[3], db3[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) { db1[r] = dR[r * 3 + 0]; db2[r] = dR[r * 3 + 1]; db3[r] = dR[r * 3 + 2]; }
+  // b3 = b1 x b2
+  db1[0] += c.b2[1] * db3[2] - c.b2[2] * db3[1];
+  db1[1] += c.b2[2] * db3[0] - c.b2[0] * db3[2];
+  db1[2] += c.b2[0] * db3[1] - c.b2[1] * db3[0];
+  db2[0] += db3[1] * c.b1[2] - db3[2] * c.b1[1];
+  db2[1] += db3[2] * c.b1[0] - db3[0] * c.b1[2];
+  db2[2] += db3[0] * c.b1[1] - db3[1] * c.b1[0];
+  // b2 = u / max(|u|, eps)
+  float du[3];
+  if (c.nu >= eps) {
+    float t = c.b2[0] * db2[0] + c.b2[1] * db2[1] + c.b2[2] * db2[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) du[i] = (db2[i] - c.b2[i] * t) / c.nu;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) du[i] = db2[i] / eps;
+  }
+  // u = a2 - (b1.a2) b1
+  float t2 = c.b1[0] * du[0] + c.b1[1] * du[1] + c.b1[2] * du[2];
+  float da2[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    da2[i] = du[i] - c.b1[i] * t2;
+    db1[i] += -c.a2[i] * t2 - c.s * du[i];
+  }
+  // b1 = a1 / max(|a1|, eps)
+  float da1[3];
+  if (c.n1 >= eps) {
+    float t = c.b1[0] * db1[0] + c.b1[1] * db1[1] + c.b1[2] * db1[2];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) da1[i] = (db1[i] - c.b1[i] * t) / c.n1;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) da1[i] = db1[i] / eps;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) { dx[2 * i] = da1[i]; dx[2 * i + 1] = da2[i]; }
 }
 
 }  // namespace jrr

@@ -17,7 +17,7 @@
 //   dF [224][32] = Ds^T . dvp                       7 row tiles x 96 matrix instructions
 //
 // Everything is summed in a fixed order (bitwise reproducible).  Inputs F^T (K-quads) / A^T and outputs dA^T / dF^T are the
-// arrays k_prep_fwd writes and k_chain_bwd reads: the body composes with them inside one launch (prep.hip, k_sup_step) or runs
+// arrays k_prep_fwd writes and k_chain_bwd reads: the body composes with them inside one launch (chain.hip, k_sup_step) or runs
 // between them as a launch of its own (sup.hip, k_sup_iter).
 #pragma once
 #include "jrr_common.h"
@@ -157,7 +157,7 @@ __device__ __forceinline__ void sup_body(float* __restrict__ lds, int blk, const
   }
   __syncthreads();
 
-  // ---- joints (ascending vertex row), pelvis-centred squared error and its adjoint (k_joints_loss, prep.hip) ----
+  // ---- joints (ascending vertex row), pelvis-centred squared error and its adjoint (k_joints_loss, loss.hip) ----
   float j3[3] = {0.f, 0.f, 0.f}, g3[3] = {0.f, 0.f, 0.f};
   if (jt < NH) {
 #pragma unroll
@@ -190,7 +190,7 @@ __device__ __forceinline__ void sup_body(float* __restrict__ lds, int blk, const
       red[(jt * 8 + c) * 32 + p] = g3[c];
     }
     float e2 = 0.f, gc[3] = {0.f, 0.f, 0.f};
-    if (a.rp.gt_j2d && ok) {      // k_joints_loss's statements (prep.hip)
+    if (a.rp.gt_j2d && ok) {      // k_joints_loss's statements (loss.hip)
       float t[3] = {a.rp.cam[(size_t)b * 3], a.rp.cam[(size_t)b * 3 + 1], a.rp.cam[(size_t)b * 3 + 2]};
       float xs, ys, invZ, X, Y;
       project_point(j3, t, xs, ys, invZ, X, Y);

@@ -25,7 +25,7 @@ def asm():
     with tempfile.TemporaryDirectory(prefix='jrr_asm_') as tmp:
         jobs = {src: subprocess.Popen([b._hipcc()] + b.FLAGS + ['--cuda-device-only', '-S', os.path.join(b.CSRC, src), '-o',
                                                                os.path.join(tmp, src + '.s')], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-                for src in ('lbs_fwd.hip', 'gemm.hip', 'prep.hip')}
+                for src in ('lbs_fwd.hip', 'gemm.hip', 'chain.hip')}
         for src, p in jobs.items():
             _, err = p.communicate()
             assert p.returncode == 0, err[-2000:]

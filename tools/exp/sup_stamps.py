@@ -1,4 +1,4 @@
-"""Phase stamps of the composed support-vertex kernel k_sup_step (prep.hip, supk.h): workgroup 0's phase boundaries on the 100 MHz
+"""Phase stamps of the composed support-vertex kernel k_sup_step (chain.hip, supk.h): workgroup 0's phase boundaries on the 100 MHz
 counter.  The shipped library carries no stamps: this script builds tools/probe/libjrr_supstamp.so (build_variant.py: the shipped
 kernel + wall_clock64() stamps into a device symbol, read back through jrr_debug_read), loads it through JRR_LIB and prints them.
 
@@ -44,7 +44,7 @@ PAIRS += [
 
 
 def build_variant():
-    subprocess.check_call([sys.executable, os.path.join(HERE, 'build_variant.py'), 'supstamp', 'prep.hip'] + PAIRS)
+    subprocess.check_call([sys.executable, os.path.join(HERE, 'build_variant.py'), 'supstamp', 'chain.hip'] + PAIRS)
 
 
 def main():
