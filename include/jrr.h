@@ -162,6 +162,26 @@ enum {
   JRR_DISCS_MAX_POINTS = 256
 };
 
+/* jrr_point_mesh_depth / jrr_depth_accumulate: the depth of points below a mesh surface, and the row of its table: JRR_DEPTH_ACC_ROW
+ * int64 per group, offsets in int64, then the trailer of the evaluation table behind the last row.  Layout version 1.
+ * Overflow: a depth below the cap 1.0e3f gives |llrintf(depth * 2^24)| < 2^34, so a sum stays below 2^63 for 5e8 poses in one word.
+ * Counts and bins are at most the number of poses. */
+enum {
+  JRR_DEPTH_ACC_LAYOUT_VERSION = 1,
+  JRR_DEPTH_MAX_POINTS = 64,        /* points per pose of one call: one lane of a wave each */
+  JRR_DEPTH_MAX_VERTS = 8192,       /* vertices per pose: 96 KiB of the 160 KiB of LDS, beside the reduction scratch */
+  JRR_DEPTH_STATUS_INDEX = 1,       /* status bit 0: a face with an index outside [0, n_verts); that face is skipped */
+  JRR_DEPTH_ACC_ROW = 4290,
+  JRR_DEPTH_ACC_COUNT = 0,          /* poses counted */
+  JRR_DEPTH_ACC_BAD = 1,            /* poses of this group left out: one of their 2 n_points values is non-finite, or a dist fails d < 1.0e3f */
+  JRR_DEPTH_ACC_OUTSIDE = 2,        /* [64]: poses whose point k is outside: !(fabsf(wind) > 0.5f) */
+  JRR_DEPTH_ACC_UNSURE = 66,        /* [64]: poses with fabsf(|wind| - rintf(|wind|)) > 0.1f: the surface is not closed around point k, or k lies on it */
+  JRR_DEPTH_ACC_SUM = 130,          /* [64]: sum of llrintf(depth * 2^24), depth = inside ? dist : -dist (units of 2^-24 m) */
+  JRR_DEPTH_ACC_HIST = 194,         /* [64][64]: histogram of depth, bin max(0, min(63, (int)floorf((depth + 0.064f) * 250.0f))) */
+  JRR_DEPTH_ACC_BINS = 64,          /* 4-mm bins over [-64, +192) mm; bin 0 also holds everything below, bin 63 everything above */
+  JRR_DEPTH_ACC_TRAILER = 2         /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
+};
+
 /* jrr_accel_error: the acceleration error along each video sequence, and the row of its table: JRR_ACCEL_ACC_ROW int64 per group,
  * offsets in int64, then the trailer of the evaluation table behind the last row.  Layout version 1.
  * Overflow: a value below the cap 1.0e3f gives llrintf(v * 2^24) < 2^34, so a sum stays below 2^63 for 5e8 triples in one word. */
@@ -787,6 +807,57 @@ int jrr_regressor_shift_accumulate(const float* joints_a_dev, const float* joint
  * inputs alone.                                                                                                              */
 int jrr_draw_discs(uint8_t* rgb_dev, int batch, int h, int w, const float* points_dev, const float* radius_dev, float radius,
                    const uint8_t* colours_host, int n_sets, int n_pts, void* stream);
+
+/* ---- depth below the skin (`--regressor_report_depth`): is a regressed joint inside the body, and how deep -------------------
+ * No reference counterpart: a row of the regressor lies on the simplex, so its joint lies in the convex hull of its support vertices,
+ * which is not the body; scripts/test.py:107-123 regresses the joints and never asks where they are.
+ *
+ * jrr_point_mesh_depth: for each pose b of verts_dev (batch,n_verts,3) fp32 metres and each point p of points_dev (batch,n_points,3),
+ * against the triangles faces_dev (n_faces,3) int32 that all poses share -- with a face's corners a, b, c and A = a - p, B = b - p,
+ * C = c - p, everything in fp32 unless said otherwise (products may be fused into sums):
+ *   dist_dev (batch,n_points)  the minimum over the faces of the Euclidean distance from p to the closest point of the closed
+ *       triangle, >= 0.  The closest point lies in one of seven regions -- corner a, b or c, edge ab, ac or bc, the interior -- found
+ *       from d1 = ab . ap, d2 = ac . ap, d3 = ab . bp, d4 = ac . bp, d5 = ab . cp, d6 = ac . cp (ab = b - a, ac = c - a, ap = -A,
+ *       bp = -B, cp = -C), vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4; the first region that holds, in this order:
+ *         a: d1 <= 0 and d2 <= 0;  b: d3 >= 0 and d4 <= d3;  ab: vc <= 0, d1 >= 0, d3 <= 0, at a + ab d1 / (d1 - d3);
+ *         c: d6 >= 0 and d5 <= d6;  ac: vb <= 0, d2 >= 0, d6 <= 0, at a + ac d2 / (d2 - d6);
+ *         bc: va <= 0, d4 - d3 >= 0, d5 - d6 >= 0, at b + (c - b) (d4 - d3) / ((d4 - d3) + (d5 - d6));
+ *         interior: a + ab vb / (va + vb + vc) + ac vc / (va + vb + vc).
+ *       A corner region takes A, B or C itself as the offset, the others A + v ab + u ac.  The value compared between faces is the
+ *       squared length of the offset; dist is the square root of the smallest.
+ *   face_dev (batch,n_points)  a face that attains it: among equal computed squared lengths the smallest index.  A face whose
+ *       computed value is NaN (zero area: 0 / 0) never wins.  -1 when no face gave a value.
+ *   wind_dev (batch,n_points)  the winding number of the surface around p, (sum over the faces of Omega) / 4 pi with
+ *       Omega = 2 atan2f(A . (B x C), |A||B||C| + (A . B)|C| + (B . C)|A| + (C . A)|B|)   (van Oosterom and Strackee).
+ *       Each Omega is formed in fp32; the Omega are summed in double and the quotient is rounded to float once.  The order of the
+ *       sum is a function of n_faces alone: face f goes to partial sum f mod 16, each partial sum adds its faces in ascending order,
+ *       and the sixteen are added as the balanced tree ((s0 + s1) + (s2 + s3)) + ... .  Nothing depends on batch, on the pose's
+ *       position in the batch, on n_points or on the point's index: a pose gives the same bits alone and inside a batch, a point the
+ *       same bits in any column.  A closed surface gives an integer, 0 outside; the callers' rule is inside <=> fabsf(wind) > 0.5f.
+ *       The sign is the orientation of the faces (the synthetic body gives -1 inside): nothing may assume +1.
+ *   Any of the three outputs may be NULL (not all three).
+ * A face with an index outside [0, n_verts) is skipped for both quantities and sets bit 0 (JRR_DEPTH_STATUS_INDEX) of status_dev[0],
+ * which the caller zeroes and reads at its next synchronise.  A pose with a non-finite value among its n_verts vertices gives NaN
+ * dist, NaN wind and face -1 for all of its points; a point with a non-finite coordinate gives them for itself.  Neither disturbs
+ * another pose or another point.
+ * Limits: 1 <= n_points <= JRR_DEPTH_MAX_POINTS, 1 <= n_verts <= JRR_DEPTH_MAX_VERTS, 1 <= n_faces; verts_dev 8-byte aligned.
+ * JRR_ERR_ARG with a message, and no launch: a NULL input or status, all three outputs NULL, a size out of range, a misaligned pointer.
+ * batch == 0 returns JRR_OK without a launch.  No engine is touched.                                                          */
+int jrr_point_mesh_depth(const float* verts_dev, int batch, int n_verts, const int32_t* faces_dev, int n_faces, const float* points_dev,
+                         int n_points, float* dist_dev, float* wind_dev, int32_t* face_dev, int32_t* status_dev, void* stream);
+/* jrr_depth_accumulate ADDS the poses of dist_dev / wind_dev (batch,n_points), as jrr_point_mesh_depth wrote them, to rows group_dev[b]
+ * of acc_dev: int64 [n_groups][JRR_DEPTH_ACC_ROW] + JRR_DEPTH_ACC_TRAILER words, layout above; the caller zeroes it once per report.
+ * group_dev NULL: every pose in group 0.  group < 0 counts in trailer word 0 only, group >= n_groups in trailer word 1 only, as in
+ * jrr_eval_accumulate; 1 <= n_groups <= JRR_EVAL_ACC_MAX_GROUPS, 1 <= n_points <= JRR_DEPTH_MAX_POINTS.
+ * A pose counts in JRR_DEPTH_ACC_BAD only, and adds nothing else, when one of its 2 n_points values is non-finite or one of its dist
+ * fails d < 1.0e3f (the project's overflow cap, no tolerance).  Otherwise COUNT += 1 and per point column k < n_points, every
+ * operation rounded once in fp32 in the order written: inside = fabsf(wind) > 0.5f; depth = inside ? dist : -dist;
+ * OUTSIDE[k] += !inside; UNSURE[k] += fabsf(fabsf(wind) - rintf(fabsf(wind))) > 0.1f; SUM[k] += llrintf(depth * 2^24);
+ * HIST[k][max(0, min(63, (int)floorf((depth + 0.064f) * 250.0f)))] += 1.  Columns k >= n_points are not touched.
+ * Integer atomics only: the table is a function of the multiset of (pose, group) pairs -- not of the order, the split into calls or
+ * the sharding over ranks (sum the ranks' tables).                                                                          */
+int jrr_depth_accumulate(const float* dist_dev, const float* wind_dev, const int32_t* group_dev, int batch, int n_points, int n_groups,
+                         int64_t* acc_dev, void* stream);
 
 /* ---- 2-D reprojection --------------------------------------------
  * return_2d_joints core, scripts/renderer.py:35-49 (pytorch3d 0.3.0 PerspectiveCameras, R = I,

@@ -84,6 +84,8 @@ SIGNATURES = {
     'jrr_bootstrap_sums': (c_int, [_P, c_int, _P, _P, c_int, ctypes.c_uint64, c_int, c_int, _P, _P]),
     'jrr_regressor_shift_accumulate': (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
     'jrr_draw_discs': (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, _P, c_int, c_int, _P]),
+    'jrr_point_mesh_depth': (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P, _P]),
+    'jrr_depth_accumulate': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P]),
     'jrr_project_joints': (c_int, [_P, _P, _P, c_int, _P]),
     'jrr_engine_set_reprojection': (c_int, [_P, _P, _P, _P, _P]),
     'jrr_camera_prefit': (c_int, [_P, _P, _P, _P, _P, c_int, c_float, _P, _P]),

@@ -165,6 +165,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--regressor_report_images', type=int, default=8, help='--regressor_report: pose pictures (the first scored poses of rank 0)')
     parser.add_argument('--regressor_report_size', type=int, default=256,
                         help='--regressor_report: height S of the (S, 2S) pictures, a size the rasteriser takes (a multiple of 32 up to 256)')
+    parser.add_argument('--regressor_report_depth', action='store_true',
+                        help='with --regressor_report DIR: also write DIR/depth.json and DIR/depth.md, the depth of each joint below the skin '
+                             'of the evaluated meshes -- the joints of both regressors and the ground truth, per group and joint the mean '
+                             'signed depth, the share of poses in which the joint is outside the body (winding number of the surface, no '
+                             'face normals), median and 5th percentile; needs the faces of the body model: --smpl_dir or --synthetic')
     parser.add_argument('--camera_iters', type=int, default=1000, help='camera pre-fit Adam steps (optimize.py:190)')
     parser.add_argument('--save_j_regressor', type=str, default=None,
                         help='write the trained regressor in the models/retrained_J_Regressor.pt format')

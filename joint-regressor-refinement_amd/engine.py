@@ -1096,6 +1096,60 @@ def draw_discs(rgb: torch.Tensor, points: torch.Tensor, colours, radius: float =
     return rgb
 
 
+DEPTH_MAX_POINTS, DEPTH_MAX_VERTS = 64, 8192   # include/jrr.h: JRR_DEPTH_MAX_POINTS, JRR_DEPTH_MAX_VERTS
+DEPTH_ACC_ROW, DEPTH_ACC_TRAILER = 4290, 2      # include/jrr.h: JRR_DEPTH_ACC_ROW, JRR_DEPTH_ACC_TRAILER
+DEPTH_STATUS_INDEX = 1
+
+
+def point_mesh_depth(verts: torch.Tensor, faces: torch.Tensor, points: torch.Tensor, status: torch.Tensor, want_dist: bool = True,
+                     want_wind: bool = True, want_face: bool = True):
+    """jrr_point_mesh_depth: for the poses verts (B,n_verts,3) float32 m, the triangles faces (n_faces,3) int32 they share and the points
+    (B,n_points,3) -- the distance to the surface (B,n_points) >= 0, the winding number of the surface around each point (inside <=>
+    |wind| > 0.5; the sign is the faces' orientation) and a face that attains the distance, int32.  An output that is not wanted is None.
+    status: one zeroed int32 word on the device; bit 0 is set when a face names a vertex outside [0, n_verts), read it after a
+    synchronise.  One launch, nothing read back."""
+    lib = _lib.load()
+    if not (torch.is_tensor(verts) and verts.dim() == 3 and verts.shape[2] == 3 and verts.dtype == torch.float32 and verts.is_cuda):
+        raise ValueError('point_mesh_depth: verts must be a float32 device tensor (B,n_verts,3)')
+    dev, B, n_verts = verts.device, int(verts.shape[0]), int(verts.shape[1])
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32 or faces.device != dev:
+        raise ValueError(f'point_mesh_depth: faces must be int32 (n_faces,3) on {dev}, got {tuple(faces.shape)} {faces.dtype} on {faces.device}')
+    if points.dim() != 3 or points.shape[0] != B or points.shape[2] != 3 or points.dtype != torch.float32 or points.device != dev:
+        raise ValueError(f'point_mesh_depth: points must be float32 ({B},n_points,3) on {dev}, got {tuple(points.shape)} {points.dtype}')
+    if status.dtype != torch.int32 or status.numel() != 1 or status.device != dev:
+        raise ValueError(f'point_mesh_depth: status must be one int32 word on {dev}')
+    if not (want_dist or want_wind or want_face):
+        raise ValueError('point_mesh_depth: no output wanted')
+    verts, faces, points = verts.contiguous(), faces.contiguous(), points.contiguous()
+    n_points, n_faces = int(points.shape[1]), int(faces.shape[0])
+    dist = torch.empty((B, n_points), dtype=torch.float32, device=dev) if want_dist else None
+    wind = torch.empty((B, n_points), dtype=torch.float32, device=dev) if want_wind else None
+    face = torch.empty((B, n_points), dtype=torch.int32, device=dev) if want_face else None
+    if B == 0:                                      # an empty tensor has no address to pass
+        return dist, wind, face
+    check(lib.jrr_point_mesh_depth(ptr(verts), B, n_verts, ptr(faces), n_faces, ptr(points), n_points, ptr(dist), ptr(wind), ptr(face),
+                                   ptr(status), stream_ptr(dev)), 'point_mesh_depth')
+    return dist, wind, face
+
+
+def depth_accumulate(dist: torch.Tensor, wind: torch.Tensor, group: Optional[torch.Tensor], n_groups: int, acc: torch.Tensor) -> None:
+    """jrr_depth_accumulate: ADD the signed depths of dist / wind (B,n_points), as point_mesh_depth returned them, to rows `group` (B,
+    int32; None: group 0) of the int64 table `acc` (n_groups * 4290 + 2 words, include/jrr.h JRR_DEPTH_ACC_*)"""
+    lib = _lib.load()
+    B = int(dist.shape[0])
+    dist, wind = dist.contiguous(), wind.contiguous()
+    assert dist.dim() == 2 and wind.shape == dist.shape and dist.dtype == torch.float32 and wind.dtype == torch.float32
+    assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.numel() == int(n_groups) * DEPTH_ACC_ROW + DEPTH_ACC_TRAILER
+    assert dist.is_cuda and wind.device == dist.device and acc.device == dist.device
+    if group is not None:
+        group = group.contiguous()
+        assert group.shape == (B,) and group.dtype == torch.int32 and group.device == dist.device
+    if B == 0:
+        return
+    check(lib.jrr_depth_accumulate(ptr(dist), ptr(wind), ptr(group), B, int(dist.shape[1]), int(n_groups), ptr(acc), stream_ptr(dist.device)),
+          'depth_accumulate')
+
+
 def project_joints(joints: torch.Tensor, cam: torch.Tensor) -> torch.Tensor:
     """return_2d_joints core (scripts/renderer.py:35-49): (B,17,3), (B,3) -> screen xy (B,17,2)"""
     lib = _lib.load()

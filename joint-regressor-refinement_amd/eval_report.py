@@ -351,12 +351,12 @@ def evaluate_vertices(log=print) -> Optional[dict]:
                 pve.add(dv, dq, joints[0][:, 0, :].contiguous(), root_table.regress(dq)[0][:, 0, :].contiguous(), di)
     initial, retrained = (args.j_regressor_init, sha16(args.j_regressor_init, J_np)), (path, sha16(path))
     if shift is not None:      # the body model is for the pictures alone: only when --smpl_dir resolves, or --synthetic allows the synthetic one
-        model_np = regressor_report.resolve_body_model(args.smpl_dir, args.synthetic) if rank == 0 else None
+        model_np = (shift.depth_model or regressor_report.resolve_body_model(args.smpl_dir, args.synthetic)) if rank == 0 else None      # the depth section resolved it already
         shift_doc = shift.finish(initial, retrained, model_np, log=log)
         if reports is None:
             return shift_doc
     results = {k: r.finish() for k, r in reports.items()}
-    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(args._get()))), initial,
+    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', regressor_report.flags_doc(ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(args._get())))), initial,
                 retrained)
     accel_doc = None
     if track is not None:      # every mesh is present and every rank knows it: the float all-reduce, the launches, the integer all-reduce

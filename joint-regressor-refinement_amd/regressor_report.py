@@ -17,6 +17,13 @@ the normalised rows, the heaviest vertices and the shift on the template body.
 side with A's joints in green, B's in blue and the ground truth in red (jrr_draw_discs over jrr_mesh_shade, framed by
 report.frame_camera), and weights_%02d_<Joint>.png, the template body with discs at the support vertices of A (green) and B (blue),
 radius 1.5 + 6 sqrt(weight) pixels, and the two regressed joints in the pale colours on top.
+
+`DepthReport` (`--regressor_report_depth`) asks what the displacement cannot say: is a joint still under the skin?  A row of the regressor
+lies on the simplex, so its joint lies in the convex hull of its support vertices -- and the hull of a hand and a thigh vertex is mostly
+air.  Per batch one jrr_point_mesh_depth on the vertices with 51 points per pose (the joints of A, of B, and the ground truth placed at A's
+pelvis as in `Pictures.pose_pictures`), then one jrr_depth_accumulate into an int64 table (include/jrr.h, JRR_DEPTH_ACC_*); `finish()` is one
+sum-all-reduce and one read-back, `derive_depth()` the numbers, `write_depth()` DIR/depth.json and DIR/depth.md.  The other files keep
+their bytes.
 """
 from __future__ import annotations
 
@@ -117,6 +124,188 @@ def derive(table: np.ndarray, names: Sequence[str]) -> dict:
         raise RuntimeError(f'regressor-shift table: {bad_group} poses carried a group id outside [0, {G}); they were not counted')
     rows = table[:G * ROW].reshape(G, ROW)
     return {'groups': {name: _stats(rows[i]) for i, name in enumerate(names)}, ALL: _stats(rows.sum(0)), 'ignored': ignored}
+
+
+# ---- the depth below the skin ------------------------------------------------------------------------------------------------
+DEPTH_LAYOUT_VERSION = 1      # include/jrr.h: JRR_DEPTH_ACC_LAYOUT_VERSION and the offsets below
+D_ROW, D_OUTSIDE, D_UNSURE, D_SUM, D_HIST, D_BINS, D_COLS = 4290, 2, 66, 130, 194, 64, 64
+D_BIN_MM, D_LOW_MM = 4.0, -64.0
+DEPTH_SETS = ('initial', 'retrained', 'ground_truth')      # point columns 0..16, 17..33, 34..50
+DEPTH_KEYS = ('mean_mm', 'outside', 'unsure', 'median_mm', 'p05_mm')
+
+
+class DepthReport:
+    """the int64 table of the depth section and the faces it is measured against, on one device"""
+
+    def __init__(self, group_names: Sequence[str], device, faces):
+        self.names = [str(g) for g in group_names]
+        if not 1 <= len(self.names) <= MAX_GROUPS:
+            raise ValueError(f'{len(self.names)} groups: 1 .. {MAX_GROUPS}')
+        faces = np.asarray(faces)
+        if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+            raise ValueError(f'depth section: faces (n_faces,3) expected, got {faces.shape}')
+        self.device = torch.device(device)
+        self.faces = torch.from_numpy(np.ascontiguousarray(faces.astype(np.int32))).to(self.device)
+        self.acc = torch.zeros(len(self.names) * D_ROW + TRAILER, dtype=torch.int64, device=self.device)
+        self.status = torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def add(self, verts: torch.Tensor, joints_a: torch.Tensor, joints_b: torch.Tensor, gt_centred_mm: torch.Tensor,
+            group_ids: Optional[torch.Tensor] = None) -> None:
+        """verts (B,V,3) m; joints_a / joints_b (B,17,3) m as regressed on them; gt_centred_mm (B,17,3) pelvis-centred, placed at A's
+        pelvis; group_ids (B,) int32 on the device (None: group 0).  Two launches, nothing read back."""
+        from . import engine as _engine
+        ja = joints_a.detach().float()
+        points = torch.cat([ja, joints_b.detach().float(), gt_centred_mm.detach().float() / 1000.0 + ja[:, :1]], dim=1).contiguous()
+        dist, wind, _ = _engine.point_mesh_depth(verts.detach().float(), self.faces, points, self.status, want_face=False)
+        _engine.depth_accumulate(dist, wind, group_ids, len(self.names), self.acc)
+
+    def finish(self, reduce: bool = True) -> dict:
+        """the ONE all-reduce (the status word rides behind the table), the one read-back, the derivation"""
+        import torch.distributed as dist
+        table = torch.cat([self.acc, self.status.to(torch.int64)])
+        if reduce and dist.is_available() and dist.is_initialized():
+            if table.is_cuda and dist.get_backend() == 'gloo':
+                table = table.cpu()
+            dist.all_reduce(table, op=dist.ReduceOp.SUM)
+        table = table.cpu().numpy()
+        if int(table[-1]) != 0:
+            raise RuntimeError('depth section: a face of the body model names a vertex outside the meshes; it was skipped (status bit 0)')
+        return derive_depth(table[:-1], self.names)
+
+
+def _depth_quantile_mm(hist: np.ndarray, n: int, p: float) -> float:
+    """upper edge in mm of the first 4-mm bin at which the cumulated histogram reaches p * n; bin 0 (everything below -60 mm) reports
+    -60, the open last bin (>= 188 mm) its nominal edge, 192"""
+    k = int(np.searchsorted(np.cumsum(hist.astype(np.float64)), p * n, side='left'))
+    return float(D_LOW_MM + (min(k, D_BINS - 1) + 1) * D_BIN_MM)
+
+
+def _depth_stats(row: np.ndarray, n_sets: int) -> dict:
+    n, n_bad = int(row[COUNT]), int(row[BAD])
+    out = {'n': n, 'n_bad': n_bad, 'sets': {}}
+    hist = row[D_HIST:D_HIST + D_COLS * D_BINS].reshape(D_COLS, D_BINS)
+    for s in range(n_sets):
+        cols = slice(s * NJ, (s + 1) * NJ)
+        if n == 0:
+            out['sets'][DEPTH_SETS[s]] = {k: None for k in DEPTH_KEYS}
+            continue
+        out['sets'][DEPTH_SETS[s]] = {
+            'mean_mm': (row[D_SUM:D_SUM + D_COLS][cols].astype(np.float64) / FIXED / n * 1000.0).tolist(),
+            'outside': (row[D_OUTSIDE:D_OUTSIDE + D_COLS][cols].astype(np.float64) / n).tolist(),
+            'unsure': (row[D_UNSURE:D_UNSURE + D_COLS][cols].astype(np.float64) / n).tolist(),
+            'median_mm': [_depth_quantile_mm(hist[k], n, 0.5) for k in range(s * NJ, (s + 1) * NJ)],
+            'p05_mm': [_depth_quantile_mm(hist[k], n, 0.05) for k in range(s * NJ, (s + 1) * NJ)]}
+    return out
+
+
+def derive_depth(table: np.ndarray, names: Sequence[str], n_sets: int = 3) -> dict:
+    """the numbers of the int64 table (n_groups * 4290 + 2 words), per group and for `all`, in float64, for each set (point columns
+    17 s .. 17 s + 16) and joint: the mean signed depth in mm (positive: under the skin) = sum / 2^24 / n * 1000, the share of poses in
+    which the joint is outside, the share in which the winding number is no integer within 0.1, the median and the 5th percentile of the
+    depth from the 4-mm histogram (bin upper edges), n and n_bad.  Raises when a pose carried a group id >= n_groups."""
+    table = np.asarray(table)
+    G = len(names)
+    if table.dtype != np.int64 or table.shape != (G * D_ROW + TRAILER,):
+        raise ValueError(f'depth table: {G * D_ROW + TRAILER} int64 expected for {G} groups, got {table.dtype} {table.shape}')
+    if not 1 <= n_sets <= D_COLS // NJ:
+        raise ValueError(f'depth table: {n_sets} sets of {NJ} columns: 1 .. {D_COLS // NJ}')
+    ignored, bad_group = int(table[G * D_ROW]), int(table[G * D_ROW + 1])
+    if bad_group:
+        raise RuntimeError(f'depth table: {bad_group} poses carried a group id outside [0, {G}); they were not counted')
+    rows = table[:G * D_ROW].reshape(G, D_ROW)
+    return {'groups': {name: _depth_stats(rows[i], n_sets) for i, name in enumerate(names)}, ALL: _depth_stats(rows.sum(0), n_sets),
+            'ignored': ignored}
+
+
+def template_depth(model_np: Dict[str, np.ndarray], J_a, J_b, mask, device) -> dict:
+    """both regressors' joints on v_template, which needs no data: one launch of batch 1 with 34 points, read back.  Per regressor and
+    joint the signed depth in mm, the winding number and the nearest face; `orientation`: the sign of the windings of the points inside
+    (0: none is inside)"""
+    from . import engine as _engine
+    vt = np.asarray(model_np['v_template'], dtype=np.float32)
+    pts = np.concatenate([normalised(J, mask) @ vt.astype(np.float64) for J in (J_a, J_b)]).astype(np.float32)
+    dev = torch.device(device)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    faces = torch.from_numpy(np.ascontiguousarray(np.asarray(model_np['faces']).astype(np.int32))).to(dev)
+    dist, wind, face = _engine.point_mesh_depth(torch.from_numpy(vt[None]).to(dev), faces, torch.from_numpy(pts[None]).to(dev), status)
+    dist, wind, face = dist.cpu().numpy()[0].astype(np.float64), wind.cpu().numpy()[0].astype(np.float64), face.cpu().numpy()[0]
+    if int(status.item()) != 0:
+        raise RuntimeError('depth section: a face of the body model names a vertex outside v_template (status bit 0)')
+    inside = np.abs(wind) > 0.5
+    depth = np.where(inside, dist, -dist) * 1000.0
+    out = {'orientation': int(np.sign(wind[inside].sum())) if inside.any() else 0}
+    for s, name in enumerate(DEPTH_SETS[:2]):
+        k = slice(s * NJ, (s + 1) * NJ)
+        out[name] = {'depth_mm': depth[k].tolist(), 'wind': wind[k].tolist(), 'face': [int(f) for f in face[k]]}
+    return out
+
+
+def newly_outside(data: dict) -> List[int]:
+    """the joints that the retrained regressor puts outside the body in some pose and the initial one in none (over all groups)"""
+    sets = data[ALL]['sets']
+    if sets['retrained']['outside'] is None:
+        return []
+    return [j for j in range(NJ) if sets['retrained']['outside'][j] > 0 and sets['initial']['outside'][j] == 0]
+
+
+def depth_markdown(doc: dict) -> str:
+    data, tpl = doc['data'], doc['template']
+    orient = {1: 'outward normals by the right-hand rule (winding +1 inside)', -1: 'inward normals by the right-hand rule (winding -1 inside)',
+              0: 'unknown (no template joint is inside)'}[tpl['orientation']]
+    lines = [f'# Depth of the joints below the skin ({doc["source"]})', '',
+             'Signed distance from each joint to the nearest point of the mesh surface, in mm: positive under the skin, negative outside.  '
+             'Inside and outside come from the winding number of the surface around the point, not from face normals.', '',
+             f'Mesh orientation: {orient}.', '',
+             f'{data[ALL]["n"]} poses ({data[ALL]["n_bad"]} with a non-finite value or beyond the cap, {data["ignored"]} not scored).', '']
+    flagged = doc['newly_outside']
+    if flagged:
+        lines += ['**Joints the retrained regressor puts outside the body in some pose and the initial one in none: ' +
+                  ', '.join(JOINT_NAMES[j] for j in flagged) + '.**', '']
+    else:
+        lines += ['No joint is outside the body under the retrained regressor alone.', '']
+    for name, title in zip(DEPTH_SETS, ('A, the initial regressor', 'B, the retrained regressor', 'The ground truth, placed at A\'s pelvis')):
+        r = data[ALL]['sets'][name]
+        lines += [f'## {title}', '', '| joint | mean | median | 5th percentile | outside % | unsure % | on the template |', '|---|---|---|---|---|---|---|']
+        for j in range(NJ):
+            g = lambda key: None if r[key] is None else r[key][j]
+            pct = lambda key: '-' if r[key] is None else format(100.0 * r[key][j], '.2f')
+            t = _f(tpl[name]['depth_mm'][j]) if name in tpl else '-'
+            mark = ' **!**' if name == 'retrained' and j in flagged else ''
+            lines.append(f'| {JOINT_NAMES[j]}{mark} | {_f(g("mean_mm"))} | {_f(g("median_mm"), ".0f")} | {_f(g("p05_mm"), ".0f")} | {pct("outside")} | '
+                         f'{pct("unsure")} | {t} |')
+        lines.append('')
+    lines += ['Share of poses with the retrained regressor\'s joint outside, per group, %:', '', '| group | n | ' + ' | '.join(JOINT_NAMES) + ' |',
+              '|---|---|' + '---|' * NJ]
+    for name in doc['groups']:
+        r = data['groups'][name]
+        o = r['sets']['retrained']['outside']
+        cells = ['-'] * NJ if o is None else [format(100.0 * x, '.1f') for x in o]
+        lines.append(f'| {name} | {r["n"]} | ' + ' | '.join(cells) + ' |')
+    return '\n'.join(lines) + '\n'
+
+
+def write_depth(directory: str, data: dict, template: dict, group_names: Sequence[str], source: str, body_model: Optional[str]) -> Optional[dict]:
+    """DIR/depth.json and DIR/depth.md; rank 0 alone writes (the others return None)"""
+    if _rank() != 0:
+        return None
+    doc = {'layout_version': DEPTH_LAYOUT_VERSION, 'source': source, 'groups': list(group_names), 'joint_names': list(JOINT_NAMES),
+           'sets': list(DEPTH_SETS), 'bin_mm': D_BIN_MM, 'bin_low_mm': D_LOW_MM, 'orientation': template['orientation'],
+           'sign': 'depth > 0: under the skin; inside <=> |winding number| > 0.5', 'data': data, 'template': template,
+           'newly_outside': newly_outside(data), 'body_model': body_model}
+    os.makedirs(directory, exist_ok=True)
+    with open(os.path.join(directory, 'depth.json'), 'w') as f:
+        json.dump(doc, f, indent=1, sort_keys=True, default=str)
+    with open(os.path.join(directory, 'depth.md'), 'w', encoding='utf-8') as f:
+        f.write(depth_markdown(doc))
+    return doc
+
+
+def load_depth(directory: str) -> dict:
+    with open(os.path.join(directory, 'depth.json')) as f:
+        doc = json.load(f)
+    if doc.get('layout_version') != DEPTH_LAYOUT_VERSION:
+        raise ValueError(f'{directory}: depth table layout version {doc.get("layout_version")!r}, this build reads version {DEPTH_LAYOUT_VERSION}')
+    return doc
 
 
 # ---- the two regressors, without data ----------------------------------------------------------------------------------------
@@ -356,8 +545,24 @@ def _rank() -> int:
     return jdist.env_rank_world()[0]
 
 
-def check_flags(ns) -> None:
-    """what the flags of the report must satisfy, before anything is launched"""
+_OWN_FLAGS = ('regressor_report_depth',)
+
+
+def flags_doc(flags) -> dict:
+    """the flags as the existing output files record them: `regressor_report_depth` changes none of those files, so it is not among them"""
+    flags = flags if isinstance(flags, dict) else vars(flags)
+    return {k: v for k, v in flags.items() if k not in _OWN_FLAGS}
+
+
+def check_flags(ns, have_model: bool = False) -> None:
+    """what the flags of the report must satisfy, before anything is launched.  have_model: the driver holds a body model of its own
+    (the parameter path always does), so the depth section need not resolve one"""
+    if getattr(ns, 'regressor_report_depth', False):
+        if ns.regressor_report is None:
+            raise ValueError('--regressor_report_depth needs --regressor_report DIR (where depth.json / depth.md go)')
+        if not have_model and not body_model_available(ns.smpl_dir, ns.synthetic):
+            raise ValueError('--regressor_report_depth needs the faces of the body model on every rank: --smpl_dir with SMPL_NEUTRAL.npz / '
+                             '.pkl, or --synthetic')
     if ns.regressor_report is None:
         return
     if int(ns.regressor_report_images) < 0:
@@ -367,11 +572,19 @@ def check_flags(ns) -> None:
         raise ValueError(f'--regressor_report_size {S}: a size the rasteriser takes, a multiple of 32 up to 256')
 
 
+_MODEL_FILES = ('SMPL_NEUTRAL.npz', 'SMPL_NEUTRAL.pkl', 'smpl_neutral.npz')
+
+
+def body_model_available(smpl_dir: Optional[str], synthetic: bool) -> bool:
+    """whether resolve_body_model would find a body model, without reading one"""
+    return bool(synthetic) or bool(smpl_dir and any(os.path.exists(os.path.join(smpl_dir, n)) for n in _MODEL_FILES))
+
+
 def resolve_body_model(smpl_dir: Optional[str], synthetic: bool) -> Optional[Dict[str, np.ndarray]]:
     """the body model for the pictures of a run that needs none otherwise (`--eval_vertices`): the files of --smpl_dir when they exist,
     the synthetic body under --synthetic, else None (numbers only)"""
     from . import smpl_model
-    if smpl_dir and any(os.path.exists(os.path.join(smpl_dir, n)) for n in ('SMPL_NEUTRAL.npz', 'SMPL_NEUTRAL.pkl', 'smpl_neutral.npz')):
+    if smpl_dir and any(os.path.exists(os.path.join(smpl_dir, n)) for n in _MODEL_FILES):
         return smpl_model.load_smpl_model(smpl_dir, allow_synthetic=False)
     if synthetic:
         m = smpl_model.synthetic_smpl()
@@ -384,26 +597,41 @@ class Run:
     """`--regressor_report` of one evaluation: the table, the kept poses, and at the end the files.  The drivers call add() per
     batch and finish() once; every rank calls both (finish holds the all-reduce), rank 0 writes."""
 
-    def __init__(self, ns, group_names: Sequence[str], device, J_a, J_b, mask, source: str):
-        check_flags(ns)
+    def __init__(self, ns, group_names: Sequence[str], device, J_a, J_b, mask, source: str, model_np: Optional[Dict[str, np.ndarray]] = None):
+        """model_np: the body model where the driver has one already; the depth section needs its faces on every rank and resolves the
+        model itself otherwise"""
+        check_flags(ns, have_model=model_np is not None)
         self.ns, self.names, self.device, self.source = ns, list(group_names), torch.device(device), source
         self.J_a, self.J_b = np.asarray(J_a, dtype=np.float32), np.asarray(J_b, dtype=np.float32)
         self.mask = None if mask is None else np.asarray(mask, dtype=np.float32)
         self.table = ShiftReport(self.names, device)
         self.keeper = PoseKeeper(ns.regressor_report_images if _rank() == 0 else 0)
+        self.depth, self.depth_model = None, None
+        if getattr(ns, 'regressor_report_depth', False):
+            self.depth_model = model_np if model_np is not None else resolve_body_model(ns.smpl_dir, ns.synthetic)
+            self.depth = DepthReport(self.names, device, self.depth_model['faces'])
 
     def add(self, verts, joints_a, joints_b, gt_centred_mm, group_ids, scored: Optional[np.ndarray] = None) -> None:
         self.table.add(joints_a, joints_b, group_ids)
+        if self.depth is not None:
+            if verts is None:
+                raise ValueError('--regressor_report_depth: the driver kept no vertices')
+            self.depth.add(verts, joints_a, joints_b, gt_centred_mm, group_ids)
         if verts is not None:
             self.keeper.offer(verts, joints_a, joints_b, gt_centred_mm, scored)
 
     def finish(self, initial, retrained, model_np=None, device_model=None, reduce: bool = True, log=print) -> Optional[dict]:
         """model_np / device_model: the body model for the pictures (device_model None: uploaded here); model_np None: numbers only"""
         data = self.table.finish(reduce=reduce)
+        depth_data = self.depth.finish(reduce=reduce) if self.depth is not None else None
         if _rank() != 0:
             return None
         d = self.ns.regressor_report
         os.makedirs(d, exist_ok=True)
+        if depth_data is not None:
+            write_depth(d, depth_data, template_depth(self.depth_model, self.J_a, self.J_b, self.mask, self.device), self.names, self.source,
+                        str(self.depth_model.get('provenance', 'caller-supplied arrays')))
+            log(f'regressor report, depth below the skin: {os.path.join(d, "depth.md")}')
         joints = compare_regressors(self.J_a, self.J_b, self.mask, None if model_np is None else model_np['v_template'])
         if model_np is None or model_np.get('faces') is None:
             pictures = 'skipped: no body model'
@@ -423,7 +651,7 @@ class Run:
                 for i in range(n_pose):
                     _report.write_png(os.path.join(d, f'pose_{i:05d}.png'), p[i])
             pictures = f'{NJ} weight pictures, {n_pose} pose pictures, {pics.size} x {2 * pics.size}'
-        doc = write(d, data, joints, self.names, self.source, ci_report.flags_doc(self.ns), initial, retrained, pictures,
+        doc = write(d, data, joints, self.names, self.source, flags_doc(ci_report.flags_doc(self.ns)), initial, retrained, pictures,
                     None if model_np is None else str(model_np.get('provenance', 'caller-supplied arrays')))
         log(f'regressor report: {os.path.join(d, "regressor.md")}')
         return doc

@@ -85,6 +85,7 @@ def _batch_groups(batch, group_ids, B: int, device) -> torch.Tensor:
 
 
 def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> Dict[str, float]:
+    regressor_report.check_flags(args._get(), have_model=True)      # this path builds its own body model below; refuses before any launch
     accel_paths = _accel_paths() if args.eval_accel else None                                            # refuses before any launch
     ci_units = _ci_units() if args.eval_ci else None                                                     # likewise
     device = torch.device(args.device)
@@ -102,7 +103,8 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     shift = None
     if args.regressor_report:  # what the retrained regressor did to each joint: one more launch per batch, the vertices of its forward kept
         names, group_ids = _groups()
-        shift = regressor_report.Run(args._get(), names, device, J_np, J_regressor.cpu().numpy(), j_reg_mask.cpu().numpy(), 'parameters')
+        depth_model = {'model_np': smpl.model_np} if args.regressor_report_depth else {}      # --regressor_report_depth: the faces are here already
+        shift = regressor_report.Run(args._get(), names, device, J_np, J_regressor.cpu().numpy(), j_reg_mask.cpu().numpy(), 'parameters', **depth_model)
     if args.eval_report:       # per group / per joint / PCK next to the four printed means: two more launches per evaluate, no read-back
         names, group_ids = _groups()
         reports = {'before': eval_report.EvalReport(names, device), 'after': eval_report.EvalReport(names, device)}
@@ -158,7 +160,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     if reports is not None:    # this function runs in ONE process (main.py: rank 0) on whole batches: nothing to reduce
         results = {k: r.finish(reduce=False) for k, r in reports.items()}
         rep['eval_report'] = eval_report.write(args.eval_report, results, names, args.eval_groups if group_ids is not None else 'none', 'parameters',
-                                               ci_report.flags_doc(accel_report.flags_doc(args._get())), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
+                                               regressor_report.flags_doc(ci_report.flags_doc(accel_report.flags_doc(args._get()))), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
                                                (path, eval_report.sha16(path)))
     if track is not None:      # one launch per regressor over the whole split's time order, one read-back
         rep['accel_report'] = accel_report.write(args.eval_report, track.finish(accel_paths, group_ids, names, ('before', 'after'), reduce=False),
