@@ -221,6 +221,43 @@ enum {
   JRR_PVE_ACC_TRAILER = 2           /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
 };
 
+/* jrr_bone_error / jrr_bone_accumulate: bone length and direction errors of the 17-joint skeleton.  The per-pose values are ONE
+ * packed (batch, JRR_BONE_VALS) fp32 array, offsets in floats; bone b = 1 .. 16 sits at index b - 1 of its block of 16, joint j at
+ * index j of its block of 17.  The table: JRR_BONE_ACC_ROW int64 per group, offsets in int64, then the trailer of the evaluation table
+ * behind the last row.  Layout version 1.
+ * Overflow: a value below the cap 1.0e3f gives llrintf(v * 2^24) < 2^34, so a SUM word stays below 2^63 for 5e8 poses.  A length
+ * below 1.0e3f m gives q = llrintf(len * 65536.f) < 2^26 and q * q < 2^52: a SUM_SQ word holds more than 10^3 poses AT the cap (2^11
+ * of them), and 2^29 poses of bones shorter than 2 m (q < 2^17, q * q < 2^34). */
+enum {
+  JRR_BONE_ACC_LAYOUT_VERSION = 1,
+  JRR_BONE_BONES = 16,              /* bone b joins joint b to its parent, b = 1 .. 16 */
+  JRR_BONE_PAIRS = 6,               /* left / right pairs of bones */
+  JRR_BONE_VALS = 98,               /* floats per pose: 4 x 16 + 2 x 17 */
+  JRR_BONE_LEN_PRED = 0,            /* 16: len_pred_b, metres */
+  JRR_BONE_LEN_GT = 16,             /* 16: len_gt_b, metres */
+  JRR_BONE_ANG = 32,                /* 16: ang_b, radians */
+  JRR_BONE_ANG_PA = 48,             /* 16: ang_pa_b, radians */
+  JRR_BONE_ERR_DIR = 64,            /* 17: e_dir_j, metres */
+  JRR_BONE_ERR_LEN = 81,            /* 17: e_len_j, metres */
+  JRR_BONE_ACC_ROW = 192,
+  JRR_BONE_ACC_COUNT = 0,           /* poses counted */
+  JRR_BONE_ACC_BAD = 1,             /* poses of this group left out: one of their 98 values fails v < 1.0e3f (NaN, inf, absurd) */
+  JRR_BONE_ACC_SUM_LEN_PRED = 2,    /* 16: sum over the poses of llrintf(len_pred_b * 2^24), per bone (units of 2^-24 m) */
+  JRR_BONE_ACC_SUM_LEN_GT = 18,     /* 16: the same for len_gt_b */
+  JRR_BONE_ACC_SUM_ABS_DLEN = 34,   /* 16: the same for fabsf(len_pred_b - len_gt_b) */
+  JRR_BONE_ACC_SUM_ANG = 50,        /* 16: the same for ang_b (units of 2^-24 rad) */
+  JRR_BONE_ACC_SUM_ANG_PA = 66,     /* 16: the same for ang_pa_b */
+  JRR_BONE_ACC_SUM_SQ_PRED = 82,    /* 16: sum over the poses of q * q in int64, q = llrintf(len_pred_b * 65536.f) (units of 2^-32 m^2) */
+  JRR_BONE_ACC_SUM_SQ_GT = 98,      /* 16: the same for len_gt_b */
+  JRR_BONE_ACC_SUM_Q_PRED = 114,    /* 16: sum over the poses of that q itself (units of 2^-16 m): n SUM_SQ - SUM_Q^2 is n^2 x the variance, exactly */
+  JRR_BONE_ACC_SUM_Q_GT = 130,      /* 16: the same for len_gt_b */
+  JRR_BONE_ACC_SUM_ERR_DIR = 146,   /* 17: sum over the poses of llrintf(e_dir_j * 2^24), per joint */
+  JRR_BONE_ACC_SUM_ERR_LEN = 163,   /* 17: the same for e_len_j */
+  JRR_BONE_ACC_SUM_ASYM_PRED = 180, /* 6: sum over the poses of llrintf(fabsf(len_pred_left - len_pred_right) * 2^24), per pair */
+  JRR_BONE_ACC_SUM_ASYM_GT = 186,   /* 6: the same for len_gt */
+  JRR_BONE_ACC_TRAILER = 2          /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
+};
+
 /* The paired bootstrap of the evaluation report (`--eval_ci`): jrr_paired_units fills two int64 tables, jrr_bootstrap_sums resamples
  * the first.  Layout version 1.
  *   units  [n_units][JRR_BOOT_UNIT_ROW]: per resampling unit (a video sequence, or a frame) the sums over its counted poses.
@@ -858,6 +895,54 @@ int jrr_point_mesh_depth(const float* verts_dev, int batch, int n_verts, const i
  * the sharding over ranks (sum the ranks' tables).                                                                          */
 int jrr_depth_accumulate(const float* dist_dev, const float* wind_dev, const int32_t* group_dev, int batch, int n_points, int n_groups,
                          int64_t* acc_dev, void* stream);
+
+/* ---- bone length and direction errors (`--eval_bones`) -------------------------------------------------------------------------
+ * The points-based reports say how far the joints are; these two calls say what the SKELETON is: how long its bones are and where
+ * they point.  No reference code pins the definition, so this text is the specification (tests/bone_cases.py restates it).
+ * Joints in the order of the evaluation report (Pelvis, R_Hip, R_Knee, R_Ankle, L_Hip, L_Knee, L_Ankle, Torso, Neck, Nose, Head,
+ * L_Shoulder, L_Elbow, L_Wrist, R_Shoulder, R_Elbow, R_Wrist); the parent of joint j is
+ *   parent = { -1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 9, 8, 11, 12, 8, 14, 15 }
+ * and bone b = 1 .. 16 joins joint b to parent[b].  The six (left, right) pairs of bones are (4,1), (5,2), (6,3), (11,14), (12,15),
+ * (13,16): pelvis-hip, thigh, shin, neck-shoulder, upper arm, forearm.
+ * Per pose, with pred P (17,3) in metres and target G (17,3) in millimetres, as jrr_evaluate_joints takes them:
+ *   x = P - P[0],  q = G / 1000.f,  y = q - q[0]                                  (both centred on the pelvis)
+ *   u_b = x_b - x_parent,  v_b = y_b - y_parent
+ *   |w| = sqrtf((w0 w0 + w1 w1) + w2 w2),  a . b = (a0 b0 + a1 b1) + a2 b2,
+ *   a x b = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0)
+ *   len_pred_b = |u_b|,  len_gt_b = |v_b|
+ *   ang_b      = atan2f(|u_b x v_b|, u_b . v_b)      radians in [0, pi]; this form and not acosf, so that small angles keep their digits
+ *   ang_pa_b   = the same between R u_b and v_b, (R u)_r = (R[r][0] u0 + R[r][1] u1) + R[r][2] u2, with R the rotation of the similarity
+ *                fit of x to y (csrc/procfit.h, its rank-2 / 1 / 0 rules included) from moments formed as jrr_evaluate_joints forms them:
+ *                mu1 = (sum_i x_i) / 17 and mu2 likewise, i ascending; then per joint i ascending x1 = x_i - mu1, x2 = y_i - mu2,
+ *                var1 += x1[c] x1[c] for c = 0, 1, 2, and K[r][c] += x1[r] x2[c], r outer.  Scale and translation do not enter a direction.
+ *                Where pred or target lie on a line the rotation about that line is free, and so is ang_pa.
+ *   direction-only skeleton (the predicted directions with the true lengths):
+ *                xd_0 = 0,  xd_b = xd_parent + u_b * (len_gt_b / len_pred_b),  e_dir_j = |xd_j - y_j|,  e_dir_0 = 0
+ *   length-only skeleton (the true directions with the predicted lengths):
+ *                xl_0 = 0,  xl_b = xl_parent + v_b * (len_pred_b / len_gt_b),  e_len_j = |xl_j - y_j|,  e_len_0 = 0
+ * Every operation is rounded once in fp32 in the order written, nothing is fused into a sum.  A bone of length 0 in either skeleton
+ * gives 0 / 0 = NaN along its chain, a NaN input NaN where it enters; neither disturbs another pose.
+ *
+ * jrr_bone_error writes vals_dev (batch, JRR_BONE_VALS) fp32, layout above.  One pose per thread, no value crosses lanes: a pose's 98
+ * values do not depend on the batch, its neighbours or the launch.  batch == 0 returns JRR_OK without a launch.  JRR_ERR_ARG with a
+ * message, and no launch: a NULL input, vals_dev NULL (there is no other output), batch < 0, a pointer that is not 4-byte aligned.
+ * No engine is touched.                                                                                                        */
+int jrr_bone_error(const float* pred_j3d_dev, const float* target_j3d_mm_dev, int batch, float* vals_dev, void* stream);
+/* jrr_bone_accumulate ADDS the poses of vals_dev (batch, JRR_BONE_VALS), as jrr_bone_error wrote them, to rows group_dev[b] of
+ * acc_dev: int64 [n_groups][JRR_BONE_ACC_ROW] + JRR_BONE_ACC_TRAILER words, layout above; the caller zeroes it once per report.
+ * group_dev NULL: every pose in group 0.  1 <= n_groups <= JRR_EVAL_ACC_MAX_GROUPS.  A pose adds to exactly one class of words:
+ *   group < 0: trailer word 0 only;  group >= n_groups: trailer word 1 only;
+ *   one of its 98 values fails v < 1.0e3f (NaN, inf -- hence a bone of length 0 in either skeleton, a constant pred -- or absurd;
+ *   the project's overflow cap, no tolerance): BAD += 1 only;
+ *   otherwise COUNT += 1 and, with fixed24(v) = llrintf(v * 2^24), per bone b: SUM_LEN_PRED += fixed24(len_pred), SUM_LEN_GT +=
+ *   fixed24(len_gt), SUM_ABS_DLEN += fixed24(fabsf(len_pred - len_gt)), SUM_ANG += fixed24(ang), SUM_ANG_PA += fixed24(ang_pa),
+ *   SUM_SQ_PRED += q * q and SUM_Q_PRED += q with q = llrintf(len_pred * 65536.f), SUM_SQ_GT and SUM_Q_GT likewise (exact integers: the
+ *   variance of the lengths from them, (n SUM_SQ - SUM_Q^2) / n^2, is exact whatever the order); per joint j: SUM_ERR_DIR += fixed24(e_dir), SUM_ERR_LEN += fixed24(e_len); per pair (l, r):
+ *   SUM_ASYM_PRED += fixed24(fabsf(len_pred_l - len_pred_r)), SUM_ASYM_GT likewise.
+ * Integer atomics only: the table is a function of the multiset of (pose, group) pairs -- not of the order, the split into calls or
+ * the sharding over ranks (sum the ranks' tables).  batch == 0 returns JRR_OK without a launch; JRR_ERR_ARG with a message for a NULL
+ * vals_dev or acc_dev, batch < 0, n_groups out of range, vals_dev / group_dev not 4-byte or acc_dev not 8-byte aligned.            */
+int jrr_bone_accumulate(const float* vals_dev, const int32_t* group_dev, int batch, int n_groups, int64_t* acc_dev, void* stream);
 
 /* ---- 2-D reprojection --------------------------------------------
  * return_2d_joints core, scripts/renderer.py:35-49 (pytorch3d 0.3.0 PerspectiveCameras, R = I,

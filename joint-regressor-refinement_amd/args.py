@@ -139,6 +139,11 @@ def build_parser() -> argparse.ArgumentParser:
                              'acceleration error of both regressors\' joints along each video sequence -- per run of consecutive frames of '
                              'one camera, from the frame paths (images.pkl; paths.txt) -- in mm per sampled frame^2 (accel_report.py); with '
                              '--smooth_refined / --fuse_refined: the per-sample accel_err_mm_* arrays of the raw and the processed rows')
+    parser.add_argument('--eval_bones', action='store_true',
+                        help='with --eval_report DIR (the evaluation, --eval_vertices): also write DIR/bones.json and DIR/bones.md, the bone '
+                             'length and direction errors of both regressors\' joints (bones_report.py): per bone the mean length, |length '
+                             'difference|, bias and direction error, the MPJPE with the true lengths and with the true directions, per '
+                             'subject (from the frame paths) the rigidity of each bone, and the left / right asymmetry')
     parser.add_argument('--eval_pve', action='store_true',
                         help='with --eval_vertices DIR --eval_report OUT: also write OUT/pve.json, OUT/pve.md and OUT/pve_per_vertex.npy, the '
                              'per-vertex error (PVE / MPVPE) and its Procrustes-aligned form of the meshes of DIR/vertices.npy against '

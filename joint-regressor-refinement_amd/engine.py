@@ -1150,6 +1150,44 @@ def depth_accumulate(dist: torch.Tensor, wind: torch.Tensor, group: Optional[tor
           'depth_accumulate')
 
 
+BONE_VALS, BONE_ACC_ROW, BONE_ACC_TRAILER = 98, 192, 2      # include/jrr.h: JRR_BONE_VALS, JRR_BONE_ACC_ROW, JRR_BONE_ACC_TRAILER
+
+
+def bone_error(pred: torch.Tensor, gt_mm: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """jrr_bone_error: the (B,98) bone values of pred (B,17,3) m against gt_mm (B,17,3) mm -- 16 predicted and 16 true bone lengths
+    (m), 16 angles and 16 Procrustes-rotated angles (rad), the 17 per-joint errors of the direction-only and of the length-only
+    skeleton (m); include/jrr.h JRR_BONE_* has the layout and the definition.  `out`: the (B,98) tensor to fill."""
+    lib = _lib.load()
+    B = int(pred.shape[0])
+    pred, gt_mm = pred.contiguous(), gt_mm.contiguous()
+    assert pred.shape == (B, 17, 3) and gt_mm.shape == (B, 17, 3) and pred.dtype == torch.float32 and gt_mm.dtype == torch.float32
+    assert pred.is_cuda and gt_mm.device == pred.device
+    if out is None:
+        out = torch.empty(B, BONE_VALS, device=pred.device)
+    assert out.shape == (B, BONE_VALS) and out.dtype == torch.float32 and out.is_contiguous() and out.device == pred.device
+    if B == 0:                                      # an empty tensor has no address to pass
+        return out
+    check(lib.jrr_bone_error(ptr(pred), ptr(gt_mm), B, ptr(out), stream_ptr(pred.device)), 'bone_error')
+    return out
+
+
+def bone_accumulate(vals: torch.Tensor, group: Optional[torch.Tensor], n_groups: int, acc: torch.Tensor) -> None:
+    """jrr_bone_accumulate: ADD the poses of vals (B,98), as bone_error returned them, to rows `group` (B, int32; None: group 0) of the
+    int64 table `acc` (n_groups * 192 + 2 words, include/jrr.h JRR_BONE_ACC_*)"""
+    lib = _lib.load()
+    B = int(vals.shape[0])
+    vals = vals.contiguous()
+    assert vals.shape == (B, BONE_VALS) and vals.dtype == torch.float32 and vals.is_cuda
+    assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.numel() == int(n_groups) * BONE_ACC_ROW + BONE_ACC_TRAILER
+    assert acc.device == vals.device
+    if group is not None:
+        group = group.contiguous()
+        assert group.shape == (B,) and group.dtype == torch.int32 and group.device == vals.device
+    if B == 0:
+        return
+    check(lib.jrr_bone_accumulate(ptr(vals), ptr(group), B, int(n_groups), ptr(acc), stream_ptr(vals.device)), 'bone_accumulate')
+
+
 def project_joints(joints: torch.Tensor, cam: torch.Tensor) -> torch.Tensor:
     """return_2d_joints core (scripts/renderer.py:35-49): (B,17,3), (B,3) -> screen xy (B,17,2)"""
     lib = _lib.load()

@@ -272,17 +272,30 @@ def open_vertices_dir(directory: str, kind: str = 'action'):
     return verts, gt, names, ids
 
 
+def read_optional_paths(directory: str, n: int) -> Optional[List[str]]:
+    """the frame paths of an --eval_vertices directory (`paths.txt`, one line per mesh), None when the file is absent"""
+    p = os.path.join(directory, 'paths.txt')
+    if not os.path.isfile(p):
+        return None
+    with open(p) as f:
+        paths = [line.rstrip('\n') for line in f]
+    if len(paths) != n:
+        raise ValueError(f'{p}: {len(paths)} lines for {n} meshes')
+    return paths
+
+
 def evaluate_vertices(log=print) -> Optional[dict]:
     """`--eval_vertices DIR --eval_report OUT`: rank r takes shard_bounds(N, r, world) of the meshes in chunks of --batch_size
     (pinned uploads), both regressors on one read of the vertices, one all-reduce per report at the end.  `--eval_pve`: the target
     meshes of gt_vertices.npy ride the same loop on a third pinned buffer into vertex_report.VertexReport."""
-    from . import accel_report, checkpoint, ci_report, engine as _engine, regressor_report, smpl_model, utils, vertex_report
+    from . import accel_report, bones_report, checkpoint, ci_report, engine as _engine, regressor_report, smpl_model, utils, vertex_report
     from .args import args
     if not args.eval_report and not args.regressor_report:
         raise ValueError('--eval_vertices needs --eval_report or --regressor_report DIR (where eval.json / eval.md, regressor.json / '
                          'regressor.md go)')
     regressor_report.check_flags(args._get())
     accel_report.check_flags(args._get())
+    bones_report.check_flags(args._get())
     vertex_report.check_flags(args._get())
     ci_report.check_flags(args._get())
     verts, gt, names, ids = open_vertices_dir(args.eval_vertices, args.eval_groups)          # before any launch
@@ -311,6 +324,10 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     shift = regressor_report.Run(args._get(), names, device, J_np, J_after.cpu().numpy(), mask_np, 'vertices') if args.regressor_report else None
     N = verts.shape[0]
     track = accel_report.JointTrack(N, 2, device) if accel_paths is not None else None
+    bones, subject_ids = None, None
+    if args.eval_bones:        # subjects from paths.txt when present; without it the rigidity section says so
+        subject_names, subject_ids = bones_report.subjects_of(read_optional_paths(args.eval_vertices, verts.shape[0]))
+        bones = bones_report.BoneReport(names, subject_names, device)
     ci = ci_report.PairedBootstrap(names, *ci_report.unit_ids(args.eval_ci_unit, N, ci_paths), device, ids) if args.eval_ci else None
     pve = vertex_report.VertexReport(names, device, 6890, part_np, 0 if part_np is None else model_parts['lbs_weights'].shape[1]) if gt_verts is not None else None
     root_table = _engine.JointRegressorTable(Js[:1], utils.find_j_reg_mask(Js[0])) if pve is not None else None      # joint 0 of the INITIAL regressor centres both meshes
@@ -343,6 +360,10 @@ def evaluate_vertices(log=print) -> Optional[dict]:
                 reports['after'].add(joints[1], gtc, di)
             if track is not None:
                 track.add(np.arange(a, b), (joints[0], joints[1]), gtc)
+            if bones is not None:
+                ds = torch.from_numpy(np.where(ids[a:b] >= 0, subject_ids[a:b], -1).astype(np.int32)).to(device) if subject_ids is not None else None
+                bones.add('before', joints[0], gtc, di, ds)
+                bones.add('after', joints[1], gtc, di, ds)
             if ci is not None:
                 ci.add(joints[0], joints[1], gtc, di, np.arange(a, b))
             if shift is not None:
@@ -356,12 +377,13 @@ def evaluate_vertices(log=print) -> Optional[dict]:
         if reports is None:
             return shift_doc
     results = {k: r.finish() for k, r in reports.items()}
-    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', regressor_report.flags_doc(ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(args._get())))), initial,
+    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(args._get()))))), initial,
                 retrained)
     accel_doc = None
     if track is not None:      # every mesh is present and every rank knows it: the float all-reduce, the launches, the integer all-reduce
         accel_doc = accel_report.write(args.eval_report, track.finish(accel_paths, ids, names, ('before', 'after'), present=np.ones(N, dtype=bool)),
                                        args.eval_groups, 'vertices')
+    bones_doc = bones_report.write(args.eval_report, bones.finish(), args.eval_groups, 'vertices', results) if bones is not None else None
     ci_doc = ci_report.write(args.eval_report, ci.finish(args.eval_ci_reps, args.seed, args.eval_ci_level, args.eval_ci_unit), names, args.eval_groups,
                              'vertices') if ci is not None else None
     pve_doc = vertex_report.write(args.eval_report, pve.finish(), names, args.eval_groups, 'vertices', initial) if pve is not None else None
@@ -371,6 +393,8 @@ def evaluate_vertices(log=print) -> Optional[dict]:
             log(f'{k}: n {r["n"]} (bad {r["n_bad"]})  MPJPE {_fmt(r["mpjpe_mm"], ".4f")}  PAMPJPE {_fmt(r["pampjpe_mm"], ".4f")}')
         if accel_doc is not None:
             log(accel_report.summary_line(accel_doc))
+        if bones_doc is not None:
+            log(bones_report.summary_line(bones_doc))
         if pve_doc is not None:
             log(vertex_report.summary_line(pve_doc))
         if ci_doc is not None:

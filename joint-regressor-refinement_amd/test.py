@@ -18,7 +18,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import accel_report, batches, checkpoint, ci_report, engine as _engine, eval_report, regressor_report, smpl_model, utils
+from . import accel_report, batches, bones_report, checkpoint, ci_report, engine as _engine, eval_report, regressor_report, smpl_model, utils
 from .args import args
 from .smpl import SMPL
 
@@ -32,13 +32,18 @@ def validation_batches(model_np, J_np, device, with_index: bool = False):
     return batches.synthetic_batches(model_np, J_np, args.batch_size, args.synthetic_batches, args.seed + 7919)
 
 
+def _split_paths():
+    """the whole split's frame paths, None for synthetic batches and for a split without images.pkl"""
+    if not args.data_root:
+        return None
+    from . import data as jdata
+    return jdata.split_image_paths(jdata.split_location('validation', args.data_root))
+
+
 def _groups():
     """(group names, int32 id per dataset sample or None): from the whole split's frame paths; synthetic batches and a split without
     images.pkl form the single group `all`"""
-    paths = None
-    if args.data_root:
-        from . import data as jdata
-        paths = jdata.split_image_paths(jdata.split_location('validation', args.data_root))
+    paths = _split_paths()
     if paths is None:
         return [eval_report.ALL], None
     return eval_report.assign_groups(paths, args.eval_groups)
@@ -88,6 +93,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     regressor_report.check_flags(args._get(), have_model=True)      # this path builds its own body model below; refuses before any launch
     accel_paths = _accel_paths() if args.eval_accel else None                                            # refuses before any launch
     ci_units = _ci_units() if args.eval_ci else None                                                     # likewise
+    bones_report.check_flags(args._get())                                                                # likewise
     device = torch.device(args.device)
     torch.cuda.set_device(device)
     smpl = SMPL(args.smpl_dir, batch_size=1, allow_synthetic=args.synthetic or args.smpl_dir == 'SPIN/data/smpl').to(device)   # :40-43
@@ -109,6 +115,10 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
         names, group_ids = _groups()
         reports = {'before': eval_report.EvalReport(names, device), 'after': eval_report.EvalReport(names, device)}
     track = accel_report.JointTrack(len(accel_paths), 2, device) if accel_paths is not None else None
+    bones, subject_ids = None, None
+    if args.eval_bones:        # the skeleton beside the points: one launch per regressor and one per table, no read-back
+        subject_names, subject_ids = bones_report.subjects_of(_split_paths())
+        bones = bones_report.BoneReport(names, subject_names, device)
     ci, ci_seen = None, 0      # --eval_ci: the paired bootstrap's unit table, opened at the first batch (frame units: one per sample of the split)
 
     mpjpe_before, pampjpe_before, mpjpe_after, pampjpe_after = [], [], [], []
@@ -143,6 +153,10 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
                 reports['after'].add(joints, gt, gid)
             if track is not None:
                 track.add(batch['index'], (joints_before, joints), gt, batch.get('valid'))
+            if bones is not None:
+                sid = _batch_groups(batch, subject_ids, B, device) if subject_ids is not None else None
+                bones.add('before', joints_before, gt, gid, sid)
+                bones.add('after', joints, gt, gid, sid)
             if args.eval_ci:   # three more launches: both regressors' per-joint errors, then the units; nothing read back
                 if ci is None:
                     unit_of_row, n_units = ci_units or ci_report.unit_ids('frame', int(batch.get('n_samples', args.synthetic_batches * B)))
@@ -160,11 +174,14 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     if reports is not None:    # this function runs in ONE process (main.py: rank 0) on whole batches: nothing to reduce
         results = {k: r.finish(reduce=False) for k, r in reports.items()}
         rep['eval_report'] = eval_report.write(args.eval_report, results, names, args.eval_groups if group_ids is not None else 'none', 'parameters',
-                                               regressor_report.flags_doc(ci_report.flags_doc(accel_report.flags_doc(args._get()))), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
+                                               bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(accel_report.flags_doc(args._get())))), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
                                                (path, eval_report.sha16(path)))
     if track is not None:      # one launch per regressor over the whole split's time order, one read-back
         rep['accel_report'] = accel_report.write(args.eval_report, track.finish(accel_paths, group_ids, names, ('before', 'after'), reduce=False),
                                                  args.eval_groups, 'parameters')
+    if bones is not None:      # the one read-back of both regressors' tables
+        rep['bones_report'] = bones_report.write(args.eval_report, bones.finish(reduce=False), args.eval_groups if group_ids is not None else 'none',
+                                                 'parameters', results)
     if ci is not None:         # the read-back of the unit table, one launch for all replicates, the read-back of their sums
         rep['ci_report'] = ci_report.write(args.eval_report, ci.finish(args.eval_ci_reps, args.seed, args.eval_ci_level, args.eval_ci_unit, reduce=False),
                                            names, args.eval_groups if group_ids is not None else 'none', 'parameters')
@@ -183,6 +200,8 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     log(f"{rep['pampjpe_after']:.4f}")
     if track is not None:
         log(accel_report.summary_line(rep['accel_report']))
+    if bones is not None:
+        log(bones_report.summary_line(rep['bones_report']))
     if ci is not None:
         log(ci_report.summary_line(rep['ci_report']))
     return rep

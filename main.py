@@ -11,6 +11,7 @@ networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evalu
 `--fit_regressor OUT --fit_from PATH` (regressor_fit.py) fits the regressor on a table of fixed meshes and exits; with `--fit_solve`
 (regressor_solve.py) it solves that fit exactly from the table's second moments instead of taking Adam epochs.
 `--eval_accel` (accel_report.py) adds the acceleration error along each video sequence to the evaluations and to those two commands.
+`--eval_bones` (bones_report.py) adds bone length and direction errors to the evaluations.
 `--eval_ci` (ci_report.py) adds paired bootstrap intervals of before, after and their difference to the evaluations."""
 import importlib
 import os
@@ -35,6 +36,7 @@ if __name__ == '__main__':
     utils.set_seed(0)
     importlib.import_module(PKG + '.regressor_report').check_flags(args._get())   # --regressor_report: refused before anything runs
     importlib.import_module(PKG + '.accel_report').check_flags(args._get())       # --eval_accel: likewise
+    importlib.import_module(PKG + '.bones_report').check_flags(args._get())       # --eval_bones: likewise
     importlib.import_module(PKG + '.regressor_fit').check_flags(args._get())      # --fit_regressor: likewise
     importlib.import_module(PKG + '.vertex_report').check_flags(args._get())      # --eval_pve: likewise
     importlib.import_module(PKG + '.ci_report').check_flags(args._get())          # --eval_ci: likewise
