@@ -182,6 +182,27 @@ enum {
   JRR_DEPTH_ACC_TRAILER = 2         /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
 };
 
+/* jrr_mesh_winding / jrr_penetration_accumulate: the winding number of a mesh around many points per pose, and the row of the
+ * self-penetration table: JRR_PEN_ACC_ROW int64 per group, offsets in int64, then the trailer of the evaluation table behind the last
+ * row.  Layout version 1.  Every word is a count: at most poses * vertices. */
+enum {
+  JRR_PEN_ACC_LAYOUT_VERSION = 1,
+  JRR_WINDING_MAX_POINTS = 65536,   /* points per pose of one call; vertices per pose of jrr_penetration_accumulate */
+  JRR_PEN_ACC_ROW = 55,
+  JRR_PEN_ACC_COUNT = 0,            /* poses counted */
+  JRR_PEN_ACC_BAD = 1,              /* poses of this group with a non-finite wind value; such a pose adds nothing else */
+  JRR_PEN_ACC_POSES_PEN = 2,        /* poses with n_pen >= 1 */
+  JRR_PEN_ACC_POSES_PEN8 = 3,       /* poses with n_pen >= 8: a few vertices can be mesh noise */
+  JRR_PEN_ACC_SUM_PEN = 4,          /* sum of n_pen */
+  JRR_PEN_ACC_SUM_THIN = 5,         /* sum of n_thin */
+  JRR_PEN_ACC_SUM_UNSURE = 6,       /* sum of n_unsure */
+  JRR_PEN_ACC_HIST = 7,             /* [16]: histogram of n_pen per pose, bin min(15, number of bits of n_pen): 0, 1, 2-3, 4-7, 8-15, ... */
+  JRR_PEN_ACC_BINS = 16,
+  JRR_PEN_ACC_PART = 23,            /* [32]: penetrating vertices by part[v]; a label outside [0, 32) goes to word 31, NULL parts to word 0 */
+  JRR_PEN_ACC_PARTS = 32,
+  JRR_PEN_ACC_TRAILER = 2           /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
+};
+
 /* jrr_accel_error: the acceleration error along each video sequence, and the row of its table: JRR_ACCEL_ACC_ROW int64 per group,
  * offsets in int64, then the trailer of the evaluation table behind the last row.  Layout version 1.
  * Overflow: a value below the cap 1.0e3f gives llrintf(v * 2^24) < 2^34, so a sum stays below 2^63 for 5e8 triples in one word. */
@@ -895,6 +916,47 @@ int jrr_point_mesh_depth(const float* verts_dev, int batch, int n_verts, const i
  * the sharding over ranks (sum the ranks' tables).                                                                          */
 int jrr_depth_accumulate(const float* dist_dev, const float* wind_dev, const int32_t* group_dev, int batch, int n_points, int n_groups,
                          int64_t* acc_dev, void* stream);
+
+/* ---- self-penetration of a mesh (`--eval_penetration`): is it a possible body at all -----------------------------------------------
+ * No reference counterpart.  A vertex pushed a little under the skin, x - offset * (outward normal), has an integer winding number of
+ * the closed surface around it: 1 for sound skin, 2 or more where that piece of skin lies inside another piece of the body (an arm
+ * through the chest), 0 where the body is thinner than the push.  No closest face, no part heuristics, no tree: the winding number at
+ * every vertex, n_verts * n_faces solid angles per pose.
+ *
+ * jrr_mesh_winding: wind_dev (batch,n_points) = the `wind` of jrr_point_mesh_depth for the poses verts_dev (batch,n_verts,3), the
+ * triangles faces_dev (n_faces,3) int32 they share and the points points_dev (batch,n_points,3), many points per pose: the same Omega
+ * (van Oosterom and Strackee, each Omega formed in fp32, products may be fused into sums), summed in double, divided by 4 pi and
+ * rounded to float once.  The order of the sum is a function of n_faces alone: face f goes to partial sum f mod 4, each partial sum
+ * adds its faces in ascending order, and the four are added as (s0 + s1) + (s2 + s3).  (jrr_point_mesh_depth sums in another order:
+ * the two calls agree within rounding, not in bits.)  Nothing depends on batch, on the pose's position in the batch, on n_points, on
+ * the point's index or on how the launch tiles the points: a point gives the same bits alone and inside a batch, in any column.  The
+ * sign is the orientation of the faces (the synthetic body gives -1 inside): nothing may assume +1.
+ * A face with an index outside [0, n_verts) is skipped and sets bit 0 (JRR_DEPTH_STATUS_INDEX) of status_dev[0], which the caller
+ * zeroes and reads at its next synchronise.  A pose with a non-finite value among its n_verts vertices gives NaN for all of its
+ * points; a point with a non-finite coordinate gives NaN for itself.  Neither disturbs another pose or another point.
+ * Limits: 1 <= n_points <= JRR_WINDING_MAX_POINTS (n_points need not be n_verts), 1 <= n_verts <= JRR_DEPTH_MAX_VERTS, 1 <= n_faces.
+ * JRR_ERR_ARG with a message, and no launch: a NULL pointer, batch < 0, a size out of range, a pointer not 4-byte aligned.
+ * batch == 0 returns JRR_OK without a launch.  No engine is touched.                                                          */
+int jrr_mesh_winding(const float* verts_dev, int batch, int n_verts, const int32_t* faces_dev, int n_faces, const float* points_dev,
+                     int n_points, float* wind_dev, int32_t* status_dev, void* stream);
+/* jrr_penetration_accumulate: wind_dev (batch,n_verts) as jrr_mesh_winding wrote it for the pushed vertices.  Per value w, in fp32,
+ * every operation rounded once: aw = fabsf(w), k = rintf(aw); PENETRATING: k >= 2.f; THIN: k == 0.f; UNSURE: fabsf(aw - k) > 0.1f (a
+ * NaN is none of the three).  n_pen_dev, n_thin_dev, n_unsure_dev (batch) int32, each nullable: the counts of the pose's vertices,
+ * written for EVERY pose, whatever its group.
+ * The pose is then ADDED to row group_dev[b] of acc_dev: int64 [n_groups][JRR_PEN_ACC_ROW] + JRR_PEN_ACC_TRAILER words, layout above;
+ * the caller zeroes it once per report.  group_dev NULL: every pose in group 0.  group < 0 counts in trailer word 0 only,
+ * group >= n_groups in trailer word 1 only, as in jrr_depth_accumulate; 1 <= n_groups <= JRR_EVAL_ACC_MAX_GROUPS,
+ * 1 <= n_verts <= JRR_WINDING_MAX_POINTS.  A pose with a non-finite wind value counts in JRR_PEN_ACC_BAD only.  Otherwise COUNT += 1,
+ * POSES_PEN += n_pen >= 1, POSES_PEN8 += n_pen >= 8, SUM_PEN += n_pen, SUM_THIN += n_thin, SUM_UNSURE += n_unsure,
+ * HIST[min(15, number of bits of n_pen)] += 1 (bin 0: n_pen == 0), and for every penetrating vertex v: PART[l] += 1 with l = part_dev[v]
+ * (n_verts int32; a label outside [0, 32) counts as 31; part_dev NULL: 0) and per_vertex_dev[v] += 1 (n_verts int64, nullable, zeroed
+ * by the caller once per report).
+ * Integer atomics only: the tables are functions of the multiset of (pose, group) pairs -- not of the order, the split into calls or
+ * the sharding over ranks (sum the ranks' tables).  JRR_ERR_ARG with a message, and no launch: wind_dev or acc_dev NULL, batch < 0, a
+ * size out of range, a table not 8-byte or another pointer not 4-byte aligned.  batch == 0 returns JRR_OK without a launch.    */
+int jrr_penetration_accumulate(const float* wind_dev, const int32_t* part_dev, const int32_t* group_dev, int batch, int n_verts,
+                               int n_groups, int64_t* acc_dev, int64_t* per_vertex_dev, int32_t* n_pen_dev, int32_t* n_thin_dev,
+                               int32_t* n_unsure_dev, void* stream);
 
 /* ---- bone length and direction errors (`--eval_bones`) -------------------------------------------------------------------------
  * The points-based reports say how far the joints are; these two calls say what the SKELETON is: how long its bones are and where

@@ -86,6 +86,8 @@ SIGNATURES = {
     'jrr_draw_discs': (c_int, [_P, c_int, c_int, c_int, _P, _P, c_float, _P, c_int, c_int, _P]),
     'jrr_point_mesh_depth': (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P, _P, _P]),
     'jrr_depth_accumulate': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    'jrr_mesh_winding': (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, _P, _P, _P]),
+    'jrr_penetration_accumulate': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     'jrr_bone_error': (c_int, [_P, _P, c_int, _P, _P]),
     'jrr_bone_accumulate': (c_int, [_P, _P, c_int, c_int, _P, _P]),
     'jrr_project_joints': (c_int, [_P, _P, _P, c_int, _P]),

@@ -152,6 +152,15 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--eval_pve_parts', action='store_true',
                         help='with --eval_pve: per-part means as well, a vertex belonging to the SMPL joint with its largest skinning weight; '
                              'needs the body model (--smpl_dir, or the synthetic one under --synthetic)')
+    parser.add_argument('--eval_penetration', action='store_true',
+                        help='with --eval_vertices DIR --eval_report OUT: also write OUT/penetration.json, OUT/penetration.md, '
+                             'OUT/penetration_per_vertex.npy and OUT/penetration.npz, the self-penetration of the meshes of DIR/vertices.npy '
+                             '(penetration_report.py): every vertex is pushed under the skin along its normal and asked for the winding '
+                             'number of the whole surface -- 1 sound, 2 or more inside another piece of the body, 0 thinner than the push; '
+                             'per group the share of penetrating poses, per body part and per vertex the counts, per mesh n_pen / n_thin / '
+                             'n_unsure; no joint regressor is scored; needs the body model: --smpl_dir or --synthetic')
+    parser.add_argument('--eval_penetration_offset_mm', type=float, default=2.0, metavar='MM',
+                        help='--eval_penetration: how far a vertex is pushed under the skin, 0 < MM <= 10')
     parser.add_argument('--eval_ci', action='store_true',
                         help='with --eval_report DIR (the evaluation, --eval_vertices): also write DIR/ci.json and DIR/ci.md, paired bootstrap '
                              'intervals of MPJPE / PA-MPJPE before, after and of their difference, per group (ci_report.py): how sure the '

@@ -1,7 +1,7 @@
 // Internal launcher interface: the launch_* functions that cross a translation unit, i.e. the kernels of rot / chain / loss / flat / lbs_fwd / lbs_bwd /
 // jreg / gemm / sup / fold and the few of disc / sil that the engine (api.hip) and the fused loop (refine.hip) launch.  A launcher with no caller
 // outside the file of its kernel is static there and is not listed; the feature files (image, report, shade, export, eval, evalrep, regrep, smooth,
-// views, accel) keep their include/jrr.h entry points beside their kernels and declare nothing here.
+// views, accel, depth, pen) keep their include/jrr.h entry points beside their kernels and declare nothing here.
 #pragma once
 #include "jrr_common.h"
 #include "proj.h"      // Reproj: the 2-D reprojection term of the joint loss, as the launchers and their kernels take it

@@ -1150,7 +1150,57 @@ def depth_accumulate(dist: torch.Tensor, wind: torch.Tensor, group: Optional[tor
           'depth_accumulate')
 
 
-BONE_VALS, BONE_ACC_ROW, BONE_ACC_TRAILER = 98, 192, 2      # include/jrr.h: JRR_BONE_VALS, JRR_BONE_ACC_ROW, JRR_BONE_ACC_TRAILER
+WINDING_MAX_POINTS = 65536                      # include/jrr.h: JRR_WINDING_MAX_POINTS
+PEN_ACC_ROW, PEN_ACC_TRAILER = 55, 2            # include/jrr.h: JRR_PEN_ACC_ROW, JRR_PEN_ACC_TRAILER
+
+
+def mesh_winding(verts: torch.Tensor, faces: torch.Tensor, points: torch.Tensor, status: torch.Tensor) -> torch.Tensor:
+    """jrr_mesh_winding: the winding number (B,n_points) of the surface -- the poses verts (B,n_verts,3) float32 m with the triangles
+    faces (n_faces,3) int32 they share -- around each of the points (B,n_points,3), up to 65 536 per pose.  The sign is the faces'
+    orientation.  status: one zeroed int32 word on the device; bit 0 is set when a face names a vertex outside [0, n_verts), read it
+    after a synchronise.  One launch, nothing read back."""
+    lib = _lib.load()
+    if not (torch.is_tensor(verts) and verts.dim() == 3 and verts.shape[2] == 3 and verts.dtype == torch.float32 and verts.is_cuda):
+        raise ValueError('mesh_winding: verts must be a float32 device tensor (B,n_verts,3)')
+    dev, B, n_verts = verts.device, int(verts.shape[0]), int(verts.shape[1])
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32 or faces.device != dev:
+        raise ValueError(f'mesh_winding: faces must be int32 (n_faces,3) on {dev}, got {tuple(faces.shape)} {faces.dtype} on {faces.device}')
+    if points.dim() != 3 or points.shape[0] != B or points.shape[2] != 3 or points.dtype != torch.float32 or points.device != dev:
+        raise ValueError(f'mesh_winding: points must be float32 ({B},n_points,3) on {dev}, got {tuple(points.shape)} {points.dtype}')
+    if status.dtype != torch.int32 or status.numel() != 1 or status.device != dev:
+        raise ValueError(f'mesh_winding: status must be one int32 word on {dev}')
+    verts, faces, points = verts.contiguous(), faces.contiguous(), points.contiguous()
+    wind = torch.empty((B, int(points.shape[1])), dtype=torch.float32, device=dev)
+    if B == 0:                                      # an empty tensor has no address to pass
+        return wind
+    check(lib.jrr_mesh_winding(ptr(verts), B, n_verts, ptr(faces), int(faces.shape[0]), ptr(points), int(points.shape[1]), ptr(wind), ptr(status),
+                               stream_ptr(dev)), 'mesh_winding')
+    return wind
+
+
+def penetration_accumulate(wind: torch.Tensor, part: Optional[torch.Tensor], group: Optional[torch.Tensor], n_groups: int, acc: torch.Tensor,
+                           per_vertex: Optional[torch.Tensor] = None, n_pen: Optional[torch.Tensor] = None,
+                           n_thin: Optional[torch.Tensor] = None, n_unsure: Optional[torch.Tensor] = None) -> None:
+    """jrr_penetration_accumulate: classify the winding numbers wind (B,n_verts) of the pushed vertices (penetrating, thin, unsure), write
+    the per-pose counts into n_pen / n_thin / n_unsure (B, int32; each optional) and ADD the poses to rows `group` (B, int32; None: group
+    0) of the int64 table `acc` (n_groups * 55 + 2 words, include/jrr.h JRR_PEN_ACC_*), by part label `part` (n_verts, int32; None: all
+    part 0), and the penetrating vertices to `per_vertex` (n_verts, int64; optional)."""
+    lib = _lib.load()
+    assert wind.dim() == 2 and wind.dtype == torch.float32 and wind.is_cuda and wind.is_contiguous()
+    B, n, dev = int(wind.shape[0]), int(wind.shape[1]), wind.device
+    assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.device == dev and acc.numel() == int(n_groups) * PEN_ACC_ROW + PEN_ACC_TRAILER
+    assert part is None or (part.shape == (n,) and part.dtype == torch.int32 and part.is_contiguous() and part.device == dev)
+    assert group is None or (group.shape == (B,) and group.dtype == torch.int32 and group.is_contiguous() and group.device == dev)
+    assert per_vertex is None or (per_vertex.shape == (n,) and per_vertex.dtype == torch.int64 and per_vertex.is_contiguous() and per_vertex.device == dev)
+    for c in (n_pen, n_thin, n_unsure):
+        assert c is None or (c.shape == (B,) and c.dtype == torch.int32 and c.is_contiguous() and c.device == dev)
+    if B == 0:
+        return
+    check(lib.jrr_penetration_accumulate(ptr(wind), ptr(part), ptr(group), B, n, int(n_groups), ptr(acc), ptr(per_vertex), ptr(n_pen), ptr(n_thin),
+                                         ptr(n_unsure), stream_ptr(dev)), 'penetration_accumulate')
+
+
+BONE_VALS, BONE_ACC_ROW, BONE_ACC_TRAILER = 98, 192, 2     # include/jrr.h: JRR_BONE_VALS, JRR_BONE_ACC_ROW, JRR_BONE_ACC_TRAILER
 
 
 def bone_error(pred: torch.Tensor, gt_mm: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

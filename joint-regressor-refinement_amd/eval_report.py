@@ -287,8 +287,9 @@ def read_optional_paths(directory: str, n: int) -> Optional[List[str]]:
 def evaluate_vertices(log=print) -> Optional[dict]:
     """`--eval_vertices DIR --eval_report OUT`: rank r takes shard_bounds(N, r, world) of the meshes in chunks of --batch_size
     (pinned uploads), both regressors on one read of the vertices, one all-reduce per report at the end.  `--eval_pve`: the target
-    meshes of gt_vertices.npy ride the same loop on a third pinned buffer into vertex_report.VertexReport."""
-    from . import accel_report, bones_report, checkpoint, ci_report, engine as _engine, regressor_report, smpl_model, utils, vertex_report
+    meshes of gt_vertices.npy ride the same loop on a third pinned buffer into vertex_report.VertexReport.  `--eval_penetration`: the
+    same device copy of the meshes goes through penetration_report.PenetrationReport, three more launches per chunk."""
+    from . import accel_report, bones_report, checkpoint, ci_report, engine as _engine, penetration_report, regressor_report, smpl_model, utils, vertex_report
     from .args import args
     if not args.eval_report and not args.regressor_report:
         raise ValueError('--eval_vertices needs --eval_report or --regressor_report DIR (where eval.json / eval.md, regressor.json / '
@@ -298,6 +299,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     bones_report.check_flags(args._get())
     vertex_report.check_flags(args._get())
     ci_report.check_flags(args._get())
+    penetration_report.check_flags(args._get())
     verts, gt, names, ids = open_vertices_dir(args.eval_vertices, args.eval_groups)          # before any launch
     gt_verts = vertex_report.open_gt_vertices(args.eval_vertices, verts.shape[0]) if args.eval_pve else None
     part_np = None
@@ -306,6 +308,10 @@ def evaluate_vertices(log=print) -> Optional[dict]:
         if model_parts is None:
             raise ValueError('--eval_pve_parts needs the body model: --smpl_dir with SMPL_NEUTRAL.npz / .pkl, or --synthetic')
         part_np = vertex_report.part_labels(model_parts['lbs_weights'])
+    pen_model, pen_sign = None, 0
+    if args.eval_penetration:      # the faces and the part labels of the body model; the orientation of the faces from the first finite mesh, on every rank alike
+        pen_model = regressor_report.resolve_body_model(args.smpl_dir, args.synthetic)
+        pen_sign = penetration_report.orientation(verts, pen_model['faces'])
     accel_paths = accel_report.read_paths(args.eval_vertices, verts.shape[0]) if args.eval_accel else None
     ci_paths = ci_report.read_paths(args.eval_vertices, verts.shape[0]) if args.eval_ci and args.eval_ci_unit == 'sequence' else None
     jdist.init(args.dist_backend)
@@ -331,6 +337,8 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     ci = ci_report.PairedBootstrap(names, *ci_report.unit_ids(args.eval_ci_unit, N, ci_paths), device, ids) if args.eval_ci else None
     pve = vertex_report.VertexReport(names, device, 6890, part_np, 0 if part_np is None else model_parts['lbs_weights'].shape[1]) if gt_verts is not None else None
     root_table = _engine.JointRegressorTable(Js[:1], utils.find_j_reg_mask(Js[0])) if pve is not None else None      # joint 0 of the INITIAL regressor centres both meshes
+    pen = penetration_report.PenetrationReport(names, device, pen_model['faces'], N, args.eval_penetration_offset_mm, pen_sign,
+                                               vertex_report.part_labels(pen_model['lbs_weights']), pen_model['lbs_weights'].shape[1]) if pen_model is not None else None
     lo, hi = jdist.shard_bounds(N, rank, world)
     bs = max(1, int(args.batch_size))
     stage = [(torch.empty((bs, 6890, 3), dtype=torch.float32).pin_memory(), torch.empty((bs, NJ, 3), dtype=torch.float32).pin_memory(),
@@ -370,6 +378,8 @@ def evaluate_vertices(log=print) -> Optional[dict]:
                 shift.add(dv, joints[0], joints[1], gtc, di, ids[a:b] >= 0)
             if pve is not None:
                 pve.add(dv, dq, joints[0][:, 0, :].contiguous(), root_table.regress(dq)[0][:, 0, :].contiguous(), di)
+            if pen is not None:
+                pen.add(dv, di, a)
     initial, retrained = (args.j_regressor_init, sha16(args.j_regressor_init, J_np)), (path, sha16(path))
     if shift is not None:      # the body model is for the pictures alone: only when --smpl_dir resolves, or --synthetic allows the synthetic one
         model_np = (shift.depth_model or regressor_report.resolve_body_model(args.smpl_dir, args.synthetic)) if rank == 0 else None      # the depth section resolved it already
@@ -377,7 +387,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
         if reports is None:
             return shift_doc
     results = {k: r.finish() for k, r in reports.items()}
-    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(args._get()))))), initial,
+    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(args._get())))))), initial,
                 retrained)
     accel_doc = None
     if track is not None:      # every mesh is present and every rank knows it: the float all-reduce, the launches, the integer all-reduce
@@ -387,6 +397,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     ci_doc = ci_report.write(args.eval_report, ci.finish(args.eval_ci_reps, args.seed, args.eval_ci_level, args.eval_ci_unit), names, args.eval_groups,
                              'vertices') if ci is not None else None
     pve_doc = vertex_report.write(args.eval_report, pve.finish(), names, args.eval_groups, 'vertices', initial) if pve is not None else None
+    pen_doc = penetration_report.write(args.eval_report, pen.finish(), names, args.eval_groups, 'vertices', args.eval_penetration_offset_mm, pen_sign) if pen is not None else None
     if rank == 0:
         for k in ('before', 'after'):
             r = results[k][ALL]
@@ -399,5 +410,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
             log(vertex_report.summary_line(pve_doc))
         if ci_doc is not None:
             log(ci_report.summary_line(ci_doc))
+        if pen_doc is not None:
+            log(penetration_report.summary_line(pen_doc))
         log(f'evaluation report: {os.path.join(args.eval_report, "eval.md")}')
     return doc

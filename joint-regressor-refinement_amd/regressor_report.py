@@ -34,7 +34,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import bones_report, ci_report
+from . import bones_report, ci_report, penetration_report
 from . import dist as jdist
 from .eval_report import ALL, JOINT_NAMES, MAX_GROUPS, sha16
 
@@ -651,7 +651,7 @@ class Run:
                 for i in range(n_pose):
                     _report.write_png(os.path.join(d, f'pose_{i:05d}.png'), p[i])
             pictures = f'{NJ} weight pictures, {n_pose} pose pictures, {pics.size} x {2 * pics.size}'
-        doc = write(d, data, joints, self.names, self.source, bones_report.flags_doc(flags_doc(ci_report.flags_doc(self.ns))), initial, retrained, pictures,
+        doc = write(d, data, joints, self.names, self.source, penetration_report.flags_doc(bones_report.flags_doc(flags_doc(ci_report.flags_doc(self.ns)))), initial, retrained, pictures,
                     None if model_np is None else str(model_np.get('provenance', 'caller-supplied arrays')))
         log(f'regressor report: {os.path.join(d, "regressor.md")}')
         return doc

@@ -18,7 +18,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import accel_report, batches, bones_report, checkpoint, ci_report, engine as _engine, eval_report, regressor_report, smpl_model, utils
+from . import accel_report, batches, bones_report, checkpoint, ci_report, engine as _engine, eval_report, penetration_report, regressor_report, smpl_model, utils
 from .args import args
 from .smpl import SMPL
 
@@ -94,6 +94,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     accel_paths = _accel_paths() if args.eval_accel else None                                            # refuses before any launch
     ci_units = _ci_units() if args.eval_ci else None                                                     # likewise
     bones_report.check_flags(args._get())                                                                # likewise
+    penetration_report.check_flags(args._get())                                                          # likewise: --eval_penetration belongs to --eval_vertices
     device = torch.device(args.device)
     torch.cuda.set_device(device)
     smpl = SMPL(args.smpl_dir, batch_size=1, allow_synthetic=args.synthetic or args.smpl_dir == 'SPIN/data/smpl').to(device)   # :40-43
@@ -174,7 +175,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     if reports is not None:    # this function runs in ONE process (main.py: rank 0) on whole batches: nothing to reduce
         results = {k: r.finish(reduce=False) for k, r in reports.items()}
         rep['eval_report'] = eval_report.write(args.eval_report, results, names, args.eval_groups if group_ids is not None else 'none', 'parameters',
-                                               bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(accel_report.flags_doc(args._get())))), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
+                                               penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(accel_report.flags_doc(args._get()))))), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
                                                (path, eval_report.sha16(path)))
     if track is not None:      # one launch per regressor over the whole split's time order, one read-back
         rep['accel_report'] = accel_report.write(args.eval_report, track.finish(accel_paths, group_ids, names, ('before', 'after'), reduce=False),

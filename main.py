@@ -40,6 +40,7 @@ if __name__ == '__main__':
     importlib.import_module(PKG + '.regressor_fit').check_flags(args._get())      # --fit_regressor: likewise
     importlib.import_module(PKG + '.vertex_report').check_flags(args._get())      # --eval_pve: likewise
     importlib.import_module(PKG + '.ci_report').check_flags(args._get())          # --eval_ci: likewise
+    importlib.import_module(PKG + '.penetration_report').check_flags(args._get())  # --eval_penetration: likewise
     if args.fit_regressor:                                                   # Adam steps of the regressor on fixed meshes; no inner loop
         importlib.import_module(PKG + '.regressor_fit').fit_command()
         sys.exit(0)
