@@ -15,7 +15,6 @@ set into its own int64 table (include/jrr.h, JRR_ACCEL_ACC_*); ONE sum all-reduc
 """
 from __future__ import annotations
 
-import json
 import os
 from typing import Dict, List, Optional, Sequence
 
@@ -23,14 +22,14 @@ import numpy as np
 import torch
 
 from . import dist as jdist
-from . import eval_report, refined
+from . import eval_report, group_table, refined
+from .group_table import ALL
 
 LAYOUT_VERSION = 1            # include/jrr.h: JRR_ACCEL_ACC_LAYOUT_VERSION and the offsets below
-ROW, TRAILER = 205, 2
+ROW, TRAILER = 205, group_table.TRAILER
 COUNT, BAD, NO_TRIPLE, SUM_ERR, SUM_PRED, SUM_GT, HIST, BINS = 0, 1, 2, 3, 20, 37, 54, 151
 NJ = 17
 FIXED = float(1 << 24)        # the sums are in units of 2^-24 m per sampled frame^2
-ALL = eval_report.ALL
 UNIT = 'mm per sampled frame^2'
 
 
@@ -98,31 +97,18 @@ class JointTrack:
         G = len(names)
         if len(set_names) != self.n_sets:
             raise ValueError(f'JointTrack.finish: {len(set_names)} names for {self.n_sets} sets')
-        if not 1 <= G <= eval_report.MAX_GROUPS:
-            raise ValueError(f'{G} groups: 1 .. {eval_report.MAX_GROUPS}')
+        group_table.check_groups(G)
         grouped = reduce and dist.is_available() and dist.is_initialized()
         rank, world = (dist.get_rank(), dist.get_world_size()) if grouped else (0, 1)
-        via_host = grouped and self.flat.is_cuda and dist.get_backend() == 'gloo'
-
-        def all_reduce(t, op):
-            if via_host:
-                h = t.cpu()
-                dist.all_reduce(h, op=op)
-                t.copy_(h)
-            else:
-                dist.all_reduce(t, op=op)
-
         have = self.present if present is None else np.asarray(present).astype(bool).reshape(-1)
         if have.shape != (self.n_rows,):
             raise ValueError(f'JointTrack.finish: present should be ({self.n_rows},), is {have.shape}')
         if grouped and present is None and world > 1:
             t = torch.from_numpy(have.astype(np.int32)).to(self.device)
-            all_reduce(t, dist.ReduceOp.MAX)
-            have = t.cpu().numpy().astype(bool)
+            have = group_table.all_reduce(t, op=dist.ReduceOp.MAX).cpu().numpy().astype(bool)
         order, run, frame = refined.sequence_runs(paths, have)
         M = int(order.shape[0])
-        if grouped:
-            all_reduce(self.flat, dist.ReduceOp.SUM)                                  # THE float collective
+        group_table.all_reduce(self.flat, reduce, in_place=True)                      # THE float collective
         lo, hi = jdist.shard_bounds(M, rank, world)
         packed = torch.zeros(self.n_sets * (G * ROW + TRAILER) + 1, dtype=torch.int64, device=self.device)
         if hi > lo:
@@ -134,9 +120,7 @@ class JointTrack:
                 _engine.accel_error(self.pred[s], self.gt, d_order, d_run, status, group=d_group, n_groups=G, acc=acc, begin=lo,
                                     count=hi - lo, rows=False)
             packed[-1:].copy_(status.long())
-        if grouped:
-            all_reduce(packed, dist.ReduceOp.SUM)                                     # THE integer collective
-        host = packed.cpu().numpy()                                                   # ... and the one read-back
+        host = group_table.all_reduce(packed, reduce).cpu().numpy()                   # THE integer collective and the one read-back
         if host[-1]:
             raise RuntimeError('acceleration error: an entry of the time order lies outside the table')
         tables = host[:-1].reshape(self.n_sets, G * ROW + TRAILER)
@@ -182,15 +166,7 @@ def derive(table: np.ndarray, names: Sequence[str]) -> dict:
     """the numbers of one prediction set from its int64 table (n_groups * 205 + 2 words), per group and for `all`: n (triples scored),
     n_bad, n_no_triple, the acceleration error in mm = sum / 2^24 / (17 n) * 1000 in float64, its 17 per-joint means, the mean |a_pred|
     and |a_gt|, the median and the 90th percentile of e_j from the histogram.  Raises when a position carried a group id >= n_groups."""
-    table = np.asarray(table)
-    G = len(names)
-    if table.dtype != np.int64 or table.shape != (G * ROW + TRAILER,):
-        raise ValueError(f'acceleration table: {G * ROW + TRAILER} int64 expected for {G} groups, got {table.dtype} {table.shape}')
-    ignored, bad_group = int(table[G * ROW]), int(table[G * ROW + 1])
-    if bad_group:
-        raise RuntimeError(f'acceleration table: {bad_group} positions carried a group id outside [0, {G}); they were not scored')
-    rows = table[:G * ROW].reshape(G, ROW)
-    return {'groups': {name: _stats(rows[i]) for i, name in enumerate(names)}, ALL: _stats(rows.sum(0)), 'ignored': ignored}
+    return group_table.derive(table, names, ROW, _stats, 'acceleration table', 'positions')
 
 
 def split_stats(run: np.ndarray, frame: np.ndarray) -> dict:
@@ -211,7 +187,7 @@ def split_stats(run: np.ndarray, frame: np.ndarray) -> dict:
 
 
 def _fmt(x, spec='.3f') -> str:
-    return '-' if x is None else format(x, spec)
+    return group_table.fmt(x, spec)
 
 
 def markdown(doc: dict) -> str:
@@ -246,23 +222,12 @@ def markdown(doc: dict) -> str:
 
 def write(directory: str, result: dict, group_kind: str, source: str) -> Optional[dict]:
     """DIR/accel.json and DIR/accel.md from what finish() returned; rank 0 alone writes (the others return None)"""
-    if eval_report._rank() != 0:
-        return None
-    doc = dict(result, layout_version=LAYOUT_VERSION, source=source, group_kind=group_kind, joints=list(eval_report.JOINT_NAMES), unit=UNIT)
-    os.makedirs(directory, exist_ok=True)
-    with open(os.path.join(directory, 'accel.json'), 'w') as f:
-        json.dump(doc, f, indent=1, sort_keys=True, default=str)
-    with open(os.path.join(directory, 'accel.md'), 'w', encoding='utf-8') as f:
-        f.write(markdown(doc))
-    return doc
+    return group_table.write(directory, 'accel', lambda: dict(result, layout_version=LAYOUT_VERSION, source=source, group_kind=group_kind,
+                                                              joints=list(eval_report.JOINT_NAMES), unit=UNIT), markdown)
 
 
 def load(directory: str) -> dict:
-    with open(os.path.join(directory, 'accel.json')) as f:
-        doc = json.load(f)
-    if doc.get('layout_version') != LAYOUT_VERSION:
-        raise ValueError(f'{directory}: table layout version {doc.get("layout_version")!r}, this build reads version {LAYOUT_VERSION}')
-    return doc
+    return group_table.load(directory, 'accel', LAYOUT_VERSION)
 
 
 def summary_line(doc: dict) -> str:

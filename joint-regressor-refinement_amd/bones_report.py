@@ -18,18 +18,17 @@ shards; through the host for gloo), the one read-back, `derive()` in float64 -- 
 """
 from __future__ import annotations
 
-import json
 import math
-import os
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import eval_report
+from . import eval_report, group_table
+from .group_table import ALL, arrow as _arrow, fmt as _fmt
 
 LAYOUT_VERSION = 1            # include/jrr.h: JRR_BONE_ACC_LAYOUT_VERSION and the offsets below
-ROW, TRAILER = 192, 2
+ROW, TRAILER = 192, group_table.TRAILER
 (COUNT, BAD, SUM_LEN_PRED, SUM_LEN_GT, SUM_ABS_DLEN, SUM_ANG, SUM_ANG_PA, SUM_SQ_PRED, SUM_SQ_GT, SUM_Q_PRED, SUM_Q_GT, SUM_ERR_DIR, SUM_ERR_LEN,
  SUM_ASYM_PRED, SUM_ASYM_GT) = 0, 1, 2, 18, 34, 50, 66, 82, 98, 114, 130, 146, 163, 180, 186
 NJ, NB, NP = 17, 16, 6
@@ -39,7 +38,6 @@ PARENT = (-1, 0, 1, 2, 0, 4, 5, 0, 7, 8, 9, 8, 11, 12, 8, 14, 15)
 PAIRS = ((4, 1), (5, 2), (6, 3), (11, 14), (12, 15), (13, 16))
 PAIR_NAMES = ('pelvis-hip', 'thigh', 'shin', 'neck-shoulder', 'upper arm', 'forearm')
 BONE_NAMES = tuple(f'{eval_report.JOINT_NAMES[PARENT[b]]}-{eval_report.JOINT_NAMES[b]}' for b in range(1, NJ))
-ALL = eval_report.ALL
 NO_SUBJECTS = 'no frame paths: the subjects are unknown, the rigidity of a bone over a subject\'s poses is not reported'
 
 
@@ -68,8 +66,7 @@ class BoneReport:
         self.subject_names = None if subject_names is None else [str(s) for s in subject_names]
         self.set_names = [str(s) for s in set_names]
         for what, n in (('groups', len(self.names)), ('subjects', len(self.subject_names or ['-']))):
-            if not 1 <= n <= eval_report.MAX_GROUPS:
-                raise ValueError(f'{n} {what}: 1 .. {eval_report.MAX_GROUPS}')
+            group_table.check_groups(n, what)
         self.device = torch.device(device)
         self.words_g = len(self.names) * ROW + TRAILER
         self.words_s = 0 if self.subject_names is None else len(self.subject_names) * ROW + TRAILER
@@ -97,12 +94,7 @@ class BoneReport:
 
     def finish(self, reduce: bool = True) -> dict:
         """the ONE all-reduce (reduce=False: this process evaluated everything alone), the one read-back, the derivation"""
-        import torch.distributed as dist
-        table = self.acc
-        if reduce and dist.is_available() and dist.is_initialized():
-            if table.is_cuda and dist.get_backend() == 'gloo':
-                table = table.cpu()
-            dist.all_reduce(table, op=dist.ReduceOp.SUM)                              # THE integer collective
+        table = group_table.all_reduce(self.acc, reduce)                              # THE integer collective
         host = table.cpu().numpy().reshape(len(self.set_names), self.words_g + self.words_s)      # ... and the one read-back
         sets, subjects = {}, {}
         for s, name in enumerate(self.set_names):
@@ -152,15 +144,7 @@ def derive(table: np.ndarray, names: Sequence[str]) -> dict:
     before and after the Procrustes rotation in degrees; the means of those over the 16 bones; the MPJPE of the direction-only skeleton
     (`mpjpe_true_lengths_mm`) and of the length-only one (`mpjpe_true_directions_mm`), sum / 2^24 / (17 n) * 1000; per pair the mean
     |left - right| of the predicted and of the true skeleton.  Raises when a pose carried a group id >= n_groups."""
-    table = np.asarray(table)
-    G = len(names)
-    if table.dtype != np.int64 or table.shape != (G * ROW + TRAILER,):
-        raise ValueError(f'bone table: {G * ROW + TRAILER} int64 expected for {G} groups, got {table.dtype} {table.shape}')
-    ignored, bad_group = int(table[G * ROW]), int(table[G * ROW + 1])
-    if bad_group:
-        raise RuntimeError(f'bone table: {bad_group} poses carried a group id outside [0, {G}); they were not scored')
-    rows = table[:G * ROW].reshape(G, ROW)
-    return {'groups': {name: _stats(rows[i]) for i, name in enumerate(names)}, ALL: _stats(rows.sum(0)), 'ignored': ignored}
+    return group_table.derive(table, names, ROW, _stats, 'bone table')
 
 
 def std_mm(n: int, sum_q: int, sum_sq: int) -> Optional[float]:
@@ -178,12 +162,7 @@ def rigidity(tables: Dict[str, np.ndarray], subject_names: Sequence[str], set_na
     S = len(subject_names)
     per = {}
     for name in set_names:
-        t = np.asarray(tables[name])
-        if t.dtype != np.int64 or t.shape != (S * ROW + TRAILER,):
-            raise ValueError(f'bone subject table: {S * ROW + TRAILER} int64 expected for {S} subjects, got {t.dtype} {t.shape}')
-        if int(t[S * ROW + 1]):
-            raise RuntimeError(f'bone subject table: {int(t[S * ROW + 1])} poses carried a subject id outside [0, {S}); they were not scored')
-        per[name] = t[:S * ROW].reshape(S, ROW)
+        per[name], _ = group_table.split(tables[name], S, ROW, 'bone subject table', what='subjects', ident='subject id')
     out = {'per_subject': {}, 'unit': 'mm'}
     for i, subject in enumerate(subject_names):
         entry = {'n': {name: int(per[name][i, COUNT]) for name in set_names}}
@@ -200,14 +179,6 @@ def rigidity(tables: Dict[str, np.ndarray], subject_names: Sequence[str], set_na
 
 
 # ---- the files -------------------------------------------------------------------------------------------------------------
-def _fmt(x, spec='.2f') -> str:
-    return '-' if x is None else format(x, spec)
-
-
-def _arrow(b, a, spec='.2f') -> str:
-    return f'{_fmt(b, spec)} → {_fmt(a, spec)}'
-
-
 def _at(xs, i):
     return None if xs is None else xs[i]
 
@@ -270,7 +241,7 @@ def summary_line(doc: dict) -> str:
 def write(directory: str, result: dict, group_kind: str, source: str, eval_results: Optional[Dict[str, dict]] = None) -> Optional[dict]:
     """DIR/bones.json and DIR/bones.md from what finish() returned; rank 0 alone writes (the others return None).  eval_results: set
     name -> what EvalReport.finish() returned in the same run: each group's MPJPE is put beside the two rebuilt skeletons'."""
-    if eval_report._rank() != 0:
+    if group_table.rank() != 0:        # before the results are joined below
         return None
     doc = dict(result, layout_version=LAYOUT_VERSION, source=source, group_kind=group_kind, joints=list(eval_report.JOINT_NAMES), bones=list(BONE_NAMES),
                parent=list(PARENT), pairs=list(PAIR_NAMES), pair_bones=[list(p) for p in PAIRS])
@@ -280,17 +251,8 @@ def write(directory: str, result: dict, group_kind: str, source: str, eval_resul
                 doc['sets'][name][ALL]['mpjpe_mm'] = res[ALL]['mpjpe_mm']
                 for g, r in doc['sets'][name]['groups'].items():
                     r['mpjpe_mm'] = res['groups'][g]['mpjpe_mm']
-    os.makedirs(directory, exist_ok=True)
-    with open(os.path.join(directory, 'bones.json'), 'w') as f:
-        json.dump(doc, f, indent=1, sort_keys=True, default=str)
-    with open(os.path.join(directory, 'bones.md'), 'w', encoding='utf-8') as f:
-        f.write(markdown(doc))
-    return doc
+    return group_table.write(directory, 'bones', doc, markdown)
 
 
 def load(directory: str) -> dict:
-    with open(os.path.join(directory, 'bones.json')) as f:
-        doc = json.load(f)
-    if doc.get('layout_version') != LAYOUT_VERSION:
-        raise ValueError(f'{directory}: table layout version {doc.get("layout_version")!r}, this build reads version {LAYOUT_VERSION}')
-    return doc
+    return group_table.load(directory, 'bones', LAYOUT_VERSION)

@@ -21,7 +21,6 @@ on the uncertainty.  `derive`, `markdown` and `write` work without a GPU.
 """
 from __future__ import annotations
 
-import json
 import os
 from typing import List, Optional, Sequence, Tuple
 
@@ -29,17 +28,17 @@ import numpy as np
 import torch
 
 from . import dist as jdist
-from . import eval_report
+from . import group_table
+from .group_table import ALL, T_BAD_GROUP, T_IGNORED, fmt as _fmt
 
 LAYOUT_VERSION = 1            # include/jrr.h: JRR_BOOT_LAYOUT_VERSION and the offsets below
 UNIT_ROW, WINS_ROW, WINS_TRAILER = 5, 8, 3
 BEFORE, BEFORE_PA, AFTER, AFTER_PA, UNIT_COUNT = 0, 1, 2, 3, 4
 W_COUNT, W_BAD, W_BETTER, W_WORSE, W_TIE, W_BETTER_PA, W_WORSE_PA, W_TIE_PA = range(8)
-T_IGNORED, T_BAD_GROUP, T_BAD_UNIT = 0, 1, 2
+T_BAD_UNIT = 2                # the third trailer word, behind the two of group_table
 NJ = 17
 FIXED = float(1 << 24)        # the sums are in units of 2^-24 m
 SUM_LIMIT = 1 << 62           # include/jrr.h: (largest segment) x (largest unit word) stays below
-ALL = eval_report.ALL
 UNIT_KINDS = ('sequence', 'frame')
 METRICS = (('mpjpe', BEFORE, AFTER), ('pampjpe', BEFORE_PA, AFTER_PA))
 _OWN_FLAGS = ('eval_ci', 'eval_ci_unit', 'eval_ci_reps', 'eval_ci_level')
@@ -113,8 +112,7 @@ class PairedBootstrap:
         group): the group of every dataset index, as the evaluation report assigns it"""
         self.names = [str(g) for g in group_names]
         G = len(self.names)
-        if not 1 <= G <= eval_report.MAX_GROUPS:
-            raise ValueError(f'{G} groups: 1 .. {eval_report.MAX_GROUPS}')
+        group_table.check_groups(G)
         self.unit_of_row = np.asarray(unit_of_row).astype(np.int32).reshape(-1)
         self.group_of_row = np.zeros_like(self.unit_of_row) if group_of_row is None else np.asarray(group_of_row).astype(np.int32).reshape(-1)
         if self.group_of_row.shape != self.unit_of_row.shape:
@@ -154,19 +152,7 @@ class PairedBootstrap:
         from . import engine as _engine
         grouped = reduce and dist.is_available() and dist.is_initialized()
         rank, world = (dist.get_rank(), dist.get_world_size()) if grouped else (0, 1)
-        via_host = grouped and self.flat.is_cuda and dist.get_backend() == 'gloo'
-
-        def all_reduce(t):
-            if via_host:
-                h = t.cpu()
-                dist.all_reduce(h, op=dist.ReduceOp.SUM)
-                t.copy_(h)
-            else:
-                dist.all_reduce(t, op=dist.ReduceOp.SUM)
-
-        if grouped:
-            all_reduce(self.flat)                                                      # the first integer collective
-        host = self.flat.cpu().numpy()                                                 # ... and its read-back
+        host = group_table.all_reduce(self.flat, reduce, in_place=True).cpu().numpy()                 # the first integer collective and its read-back
         G = len(self.names)
         units = host[:self.n_units * UNIT_ROW].reshape(self.n_units, UNIT_ROW)
         wins = host[self.n_units * UNIT_ROW:]
@@ -180,9 +166,7 @@ class PairedBootstrap:
             full = torch.zeros((len(segments), reps, UNIT_ROW), dtype=torch.int64, device=self.device)
             if hi > lo:
                 full[:, lo:hi] = _engine.bootstrap_sums(table, segments, seed, lo, hi - lo, max_word=int(np.abs(units[kept]).max()))
-            if grouped:
-                all_reduce(full)                                                       # the second integer collective
-            sums = full.cpu().numpy()
+            sums = group_table.all_reduce(full, reduce).cpu().numpy()                  # the second integer collective
         return derive(units[kept], group_of_unit, segments, sums, wins, self.names, level, seed=int(seed), unit_kind=unit_kind)
 
 
@@ -272,10 +256,6 @@ def derive(units: np.ndarray, group_of_unit: np.ndarray, segments: np.ndarray, s
 
 
 # ---- the files -----------------------------------------------------------------------------------------------------------------
-def _fmt(x, spec='.2f') -> str:
-    return '-' if x is None else format(x, spec)
-
-
 def _cell(r: Optional[dict], spec='.2f') -> str:
     return '-' if r is None else f'{_fmt(r["mean_mm"], spec)} [{_fmt(r["lo_mm"], spec)}, {_fmt(r["hi_mm"], spec)}]'
 
@@ -305,23 +285,12 @@ def markdown(doc: dict) -> str:
 
 def write(directory: str, result: dict, group_names: Sequence[str], group_kind: str, source: str) -> Optional[dict]:
     """DIR/ci.json and DIR/ci.md from what finish() returned; rank 0 alone writes (the others return None)"""
-    if eval_report._rank() != 0:
-        return None
     doc = {'layout_version': LAYOUT_VERSION, 'source': source, 'group_kind': group_kind, 'groups': list(group_names), 'data': result, 'unit': 'mm'}
-    os.makedirs(directory, exist_ok=True)
-    with open(os.path.join(directory, 'ci.json'), 'w') as f:
-        json.dump(doc, f, indent=1, sort_keys=True, default=str)
-    with open(os.path.join(directory, 'ci.md'), 'w', encoding='utf-8') as f:
-        f.write(markdown(doc))
-    return doc
+    return group_table.write(directory, 'ci', doc, markdown)
 
 
 def load(directory: str) -> dict:
-    with open(os.path.join(directory, 'ci.json')) as f:
-        doc = json.load(f)
-    if doc.get('layout_version') != LAYOUT_VERSION:
-        raise ValueError(f'{directory}: table layout version {doc.get("layout_version")!r}, this build reads version {LAYOUT_VERSION}')
-    return doc
+    return group_table.load(directory, 'ci', LAYOUT_VERSION)
 
 
 def summary_line(doc: dict) -> str:

@@ -18,6 +18,7 @@
 // Every floating-point operation is rounded once, in the order written (no product is fused into a sum), so a host restatement
 // follows it.
 #include "jrr_common.h"
+#include "acctab.h"
 #include "../../include/jrr.h"
 
 namespace jrr {
@@ -27,7 +28,8 @@ constexpr int AC_NS = AC_TILE + 2;                 // slots a tile can see: a ha
 constexpr int AC_ROWF = NH * 3;                    // 51 floats per table row
 constexpr int AC_THREADS = AC_TILE * NH;           // 544: one thread per (position, joint)
 constexpr float AC_FIXED = 16777216.f;             // 2^24
-enum { AC_COUNTED = 0, AC_BAD = 1, AC_NO_TRIPLE = 2, AC_IGNORED = 3, AC_BAD_GROUP = 4 };
+constexpr int AC_NO_TRIPLE = 2;                    // the kind of its own beside acctab.h's: in range, lands in the row's NO_TRIPLE word
+static_assert(AC_NO_TRIPLE > ACC_BAD && AC_NO_TRIPLE < ACC_IGNORED, "a kind of the row");
 
 static_assert(JRR_ACCEL_ACC_SUM_ERR == 3 && JRR_ACCEL_ACC_SUM_PRED == JRR_ACCEL_ACC_SUM_ERR + NH &&
               JRR_ACCEL_ACC_SUM_GT == JRR_ACCEL_ACC_SUM_PRED + NH && JRR_ACCEL_ACC_HIST == JRR_ACCEL_ACC_SUM_GT + NH &&
@@ -37,9 +39,6 @@ static_assert(AC_THREADS <= 1024 && AC_TILE <= AC_THREADS, "tile shape");
 
 #pragma clang fp contract(off)
 
-__device__ __forceinline__ void ac_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
 __device__ __forceinline__ float ac_len(float v0, float v1, float v2) { return sqrtf((v0 * v0 + v1 * v1) + v2 * v2); }
 
 // grid: ceil(count / 32) workgroups of 544 threads; workgroup b owns positions p0 = begin + 32 b .. min(p0 + 32, begin + count)
@@ -125,18 +124,16 @@ __global__ __launch_bounds__(AC_THREADS) void k_accel_error(const float* __restr
   // what each position is to the table
   if (tid < npos) {
     const int gid = group ? group[p0 + tid] : 0;
-    int kind;
-    if (gid < 0) kind = AC_IGNORED;
-    else if (gid >= n_groups) kind = AC_BAD_GROUP;
-    else {
+    int kind = acc_group_kind(gid, n_groups);
+    if (kind == ACC_COUNTED) {
       const int cc = 1 + tid;
       const bool tr = s_row[cc] >= 0 && s_row[cc - 1] >= 0 && s_row[cc + 1] >= 0 && s_run[cc - 1] == s_run[cc] && s_run[cc + 1] == s_run[cc];
       if (!tr) kind = AC_NO_TRIPLE;
       else {
         bool good = true;
         for (int i = 0; i < NH; ++i)               // false for NaN
-          good = good && (s_out[0][tid * NH + i] < 1.0e3f) && (s_out[1][tid * NH + i] < 1.0e3f) && (s_out[2][tid * NH + i] < 1.0e3f);
-        kind = good ? AC_COUNTED : AC_BAD;
+          good = good && (s_out[0][tid * NH + i] < ERR_CAP) && (s_out[1][tid * NH + i] < ERR_CAP) && (s_out[2][tid * NH + i] < ERR_CAP);
+        kind = good ? ACC_COUNTED : ACC_BAD;
       }
     }
     s_kind[tid] = kind;
@@ -151,38 +148,36 @@ __global__ __launch_bounds__(AC_THREADS) void k_accel_error(const float* __restr
   }
   __syncthreads();
 
-  long long* trailer = acc + (size_t)n_groups * JRR_ACCEL_ACC_ROW;
   if (tid < npos) {                                // one word per position
     const int kind = s_kind[tid], gid = s_gid[tid];
-    if (kind == AC_IGNORED) ac_add(trailer + JRR_EVAL_ACC_TRAILER_IGNORED, 1);
-    else if (kind == AC_BAD_GROUP) ac_add(trailer + JRR_EVAL_ACC_TRAILER_BAD_GROUP, 1);
+    if (kind >= ACC_IGNORED) acc_add(acc_trailer_word(acc, JRR_ACCEL_ACC_ROW, n_groups, kind), 1);
     else {
-      const int w = kind == AC_COUNTED ? JRR_ACCEL_ACC_COUNT : (kind == AC_BAD ? JRR_ACCEL_ACC_BAD : JRR_ACCEL_ACC_NO_TRIPLE);
-      if (gid == s_group) ac_add(s_acc + w, 1);
-      else ac_add(acc + (size_t)gid * JRR_ACCEL_ACC_ROW + w, 1);
+      const int w = kind == ACC_COUNTED ? JRR_ACCEL_ACC_COUNT : (kind == ACC_BAD ? JRR_ACCEL_ACC_BAD : JRR_ACCEL_ACC_NO_TRIPLE);
+      if (gid == s_group) acc_add(s_acc + w, 1);
+      else acc_add(acc_row(acc, JRR_ACCEL_ACC_ROW, gid) + w, 1);
     }
   }
-  if (pp < npos && s_kind[pp] == AC_COUNTED) {     // three sums and one bin per (position, joint)
+  if (pp < npos && s_kind[pp] == ACC_COUNTED) {     // three sums and one bin per (position, joint)
     const int gid = s_gid[pp];
     const long long qe = __float2ll_rn(e * AC_FIXED), qs = __float2ll_rn(s * AC_FIXED), qg = __float2ll_rn(g * AC_FIXED);
     const int bin = min((int)floorf(e * 1000.f), JRR_ACCEL_ACC_BINS - 1);    // 0 <= e < the cap here: 0 <= bin
     if (gid == s_group) {                          // the two branches differ in the address space alone
-      ac_add(s_acc + JRR_ACCEL_ACC_SUM_ERR + j, qe);
-      ac_add(s_acc + JRR_ACCEL_ACC_SUM_PRED + j, qs);
-      ac_add(s_acc + JRR_ACCEL_ACC_SUM_GT + j, qg);
-      ac_add(s_acc + JRR_ACCEL_ACC_HIST + bin, 1);
+      acc_add(s_acc + JRR_ACCEL_ACC_SUM_ERR + j, qe);
+      acc_add(s_acc + JRR_ACCEL_ACC_SUM_PRED + j, qs);
+      acc_add(s_acc + JRR_ACCEL_ACC_SUM_GT + j, qg);
+      acc_add(s_acc + JRR_ACCEL_ACC_HIST + bin, 1);
     } else {
-      long long* row = acc + (size_t)gid * JRR_ACCEL_ACC_ROW;
-      ac_add(row + JRR_ACCEL_ACC_SUM_ERR + j, qe);
-      ac_add(row + JRR_ACCEL_ACC_SUM_PRED + j, qs);
-      ac_add(row + JRR_ACCEL_ACC_SUM_GT + j, qg);
-      ac_add(row + JRR_ACCEL_ACC_HIST + bin, 1);
+      long long* row = acc_row(acc, JRR_ACCEL_ACC_ROW, gid);
+      acc_add(row + JRR_ACCEL_ACC_SUM_ERR + j, qe);
+      acc_add(row + JRR_ACCEL_ACC_SUM_PRED + j, qs);
+      acc_add(row + JRR_ACCEL_ACC_SUM_GT + j, qg);
+      acc_add(row + JRR_ACCEL_ACC_HIST + bin, 1);
     }
   }
   __syncthreads();
   if (s_group >= 0 && tid < JRR_ACCEL_ACC_ROW) {
     const long long v = s_acc[tid];
-    if (v != 0) ac_add(acc + (size_t)s_group * JRR_ACCEL_ACC_ROW + tid, v);
+    if (v != 0) acc_add(acc_row(acc, JRR_ACCEL_ACC_ROW, s_group) + tid, v);
   }
 }
 
@@ -199,16 +194,13 @@ extern "C" int jrr_accel_error(const float* pred, const float* gt_mm, int64_t n_
   else if (begin < 0 || count < 0 || begin > m || count > m - begin) why = "the position range must lie inside [0, m)";
   else if (!err_j && !acc_pred_j && !acc_gt_j && !acc) why = "no output: err_j, acc_pred_j, acc_gt_j and acc are all NULL";
   else if ((((uintptr_t)pred | (uintptr_t)gt_mm | (uintptr_t)order | (uintptr_t)run | (uintptr_t)group | (uintptr_t)status | (uintptr_t)err_j |
-             (uintptr_t)acc_pred_j | (uintptr_t)acc_gt_j) & 3) != 0 || ((uintptr_t)acc & 7) != 0)
+             (uintptr_t)acc_pred_j | (uintptr_t)acc_gt_j) & 3) != 0 || !acc_aligned(acc))
     why = "the float and int32 arrays must be 4-byte aligned, acc 8-byte aligned";
   if (why) {
     jrr_set_error("jrr_accel_error: %s", why);
     return JRR_ERR_ARG;
   }
-  if (acc && (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS)) {
-    jrr_set_error("jrr_accel_error: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
-    return JRR_ERR_ARG;
-  }
+  if (acc && acc_groups_refused("jrr_accel_error", n_groups)) return JRR_ERR_ARG;
   if (count == 0) return JRR_OK;
   hipLaunchKernelGGL(k_accel_error, dim3((unsigned)((count + AC_TILE - 1) / AC_TILE)), dim3(AC_THREADS), 0, (hipStream_t)stream, pred, gt_mm,
                      (long long)n_rows, order, run, group, m, begin, count, n_groups, err_j, acc_pred_j, acc_gt_j,

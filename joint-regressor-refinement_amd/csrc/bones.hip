@@ -21,7 +21,7 @@
 #include "jrr_common.h"
 #include "../../include/jrr.h"
 #include "procfit.h"
-#include "fixedpt.h"
+#include "acctab.h"
 #include <utility>
 
 namespace jrr {
@@ -155,13 +155,7 @@ __global__ __launch_bounds__(BN_POSES) void k_bone_error(const float* __restrict
   }
 }
 
-__device__ __forceinline__ void bn_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
-
-enum { BN_COUNTED = 0, BN_BAD = 1, BN_IGNORED = 2, BN_BAD_GROUP = 3 };
 enum { BN_FIXED = 0, BN_ABS_DIFF = 1, BN_SQUARE = 2, BN_Q = 3, BN_KIND = 4 };      // what a word sums
-static_assert(JRR_EVAL_ACC_TRAILER_IGNORED == 0 && JRR_EVAL_ACC_TRAILER_BAD_GROUP == 1, "trailer words");
 
 // grid: ceil(B / 64) workgroups of 256 threads; workgroup t owns poses 64 t .. 64 t + 63.  Thread w < 192 owns WORD w of the row, thread
 // 192 / 193 the two trailer words: it walks the tile's poses in order and sums its word's contributions in a register for as long as the
@@ -180,13 +174,11 @@ __global__ __launch_bounds__(BN_ACC_THREADS) void k_bone_accumulate(const float*
   __syncthreads();
   if (tid < np) {                                  // what each pose is to the table
     const int gid = group ? group[b0 + tid] : 0;
-    int kind;
-    if (gid < 0) kind = BN_IGNORED;
-    else if (gid >= n_groups) kind = BN_BAD_GROUP;
-    else {
+    int kind = acc_group_kind(gid, n_groups);
+    if (kind == ACC_COUNTED) {
       bool good = true;
       for (int i = 0; i < BN_VALS; ++i) good = good && (s_v[tid * BN_STRIDE + i] < ERR_CAP);      // false for NaN
-      kind = good ? BN_COUNTED : BN_BAD;
+      kind = good ? ACC_COUNTED : ACC_BAD;
     }
     s_kind[tid] = kind;
     s_gid[tid] = gid;
@@ -195,10 +187,10 @@ __global__ __launch_bounds__(BN_ACC_THREADS) void k_bone_accumulate(const float*
   const int w = tid;
   if (w >= JRR_BONE_ACC_ROW + JRR_BONE_ACC_TRAILER) return;
   if (w >= JRR_BONE_ACC_ROW) {                     // the trailer: poses ignored on purpose, poses with a group outside the table
-    const int want = w == JRR_BONE_ACC_ROW + JRR_EVAL_ACC_TRAILER_IGNORED ? BN_IGNORED : BN_BAD_GROUP;
+    const int want = ACC_IGNORED + (w - JRR_BONE_ACC_ROW);
     int n = 0;
     for (int p = 0; p < np; ++p) n += s_kind[p] == want;
-    if (n) bn_add(acc + (size_t)n_groups * JRR_BONE_ACC_ROW + (w - JRR_BONE_ACC_ROW), n);
+    if (n) acc_add(acc_trailer_word(acc, JRR_BONE_ACC_ROW, n_groups, want), n);
     return;
   }
   // what word w sums: one value, |difference of two|, q * q or q of one
@@ -222,16 +214,16 @@ __global__ __launch_bounds__(BN_ACC_THREADS) void k_bone_accumulate(const float*
   int cur = 0;                                     // the group `sum` belongs to (sum == 0: none yet)
   for (int p = 0; p < np; ++p) {                   // uniform over the workgroup: every thread sees the same kinds and groups
     const int kind = s_kind[p];
-    if (kind > BN_BAD) continue;
+    if (kind >= ACC_IGNORED) continue;
     const int g = s_gid[p];                        // 0 <= g < n_groups
     if (g != cur) {
-      if (sum != 0) bn_add(acc + (size_t)cur * JRR_BONE_ACC_ROW + w, sum);
+      if (sum != 0) acc_add(acc_row(acc, JRR_BONE_ACC_ROW, cur) + w, sum);
       sum = 0;
       cur = g;
     }
     const float* v = s_v + p * BN_STRIDE;
-    if (cls == BN_KIND) sum += (kind == (w == JRR_BONE_ACC_COUNT ? BN_COUNTED : BN_BAD)) ? 1 : 0;
-    else if (kind == BN_COUNTED) {
+    if (cls == BN_KIND) sum += (kind == (w == JRR_BONE_ACC_COUNT ? ACC_COUNTED : ACC_BAD)) ? 1 : 0;
+    else if (kind == ACC_COUNTED) {
       if (cls == BN_FIXED) sum += err_fixed24(v[a]);
       else if (cls == BN_ABS_DIFF) sum += err_fixed24(fabsf(v[a] - v[c]));
       else {
@@ -240,7 +232,7 @@ __global__ __launch_bounds__(BN_ACC_THREADS) void k_bone_accumulate(const float*
       }
     }
   }
-  if (sum != 0) bn_add(acc + (size_t)cur * JRR_BONE_ACC_ROW + w, sum);
+  if (sum != 0) acc_add(acc_row(acc, JRR_BONE_ACC_ROW, cur) + w, sum);
 }
 
 }  // namespace jrr
@@ -268,16 +260,13 @@ extern "C" int jrr_bone_accumulate(const float* vals, const int32_t* group, int 
   const char* why = nullptr;
   if (!vals || !acc) why = "bad argument (vals and acc are required)";
   else if (batch < 0) why = "batch must not be negative";
-  else if ((((uintptr_t)vals | (uintptr_t)group) & 3) != 0 || ((uintptr_t)acc & 7) != 0)
+  else if ((((uintptr_t)vals | (uintptr_t)group) & 3) != 0 || !acc_aligned(acc))
     why = "vals and group must be 4-byte aligned, acc 8-byte aligned";
   if (why) {
     jrr_set_error("jrr_bone_accumulate: %s", why);
     return JRR_ERR_ARG;
   }
-  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS) {
-    jrr_set_error("jrr_bone_accumulate: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
-    return JRR_ERR_ARG;
-  }
+  if (acc_groups_refused("jrr_bone_accumulate", n_groups)) return JRR_ERR_ARG;
   if (batch == 0) return JRR_OK;
   hipLaunchKernelGGL(k_bone_accumulate, dim3((unsigned)((batch + BN_POSES - 1) / BN_POSES)), dim3(BN_ACC_THREADS), 0,
                      (hipStream_t)stream, vals, group, n_groups, reinterpret_cast<long long*>(acc), batch);

@@ -16,15 +16,14 @@
 //                    served there; the rest of the time is Philox: 40 32-bit multiplies (quarter rate) per four draws.
 #include "jrr_common.h"
 #include "fixedpt.h"
+#include "acctab.h"
 #include "../../include/jrr.h"
 
 namespace jrr {
 
-static_assert(JRR_BOOT_UNIT_ROW == 5 && JRR_BOOT_UNIT_COUNT == 4 && JRR_BOOT_WINS_ROW == 8 && JRR_BOOT_WINS_TRAILER == 3, "row layouts");
-
-__device__ __forceinline__ void boot_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
+static_assert(JRR_BOOT_UNIT_ROW == 5 && JRR_BOOT_UNIT_COUNT == 4 && JRR_BOOT_WINS_ROW == 8 && JRR_BOOT_WINS_TRAILER == 3 &&
+              JRR_BOOT_WINS_TRAILER_IGNORED == JRR_EVAL_ACC_TRAILER_IGNORED && JRR_BOOT_WINS_TRAILER_BAD_GROUP == JRR_EVAL_ACC_TRAILER_BAD_GROUP,
+              "row layouts; the trailer of acctab.h and a third word");
 
 constexpr int PU_THREADS = 64;
 
@@ -34,13 +33,11 @@ __global__ __launch_bounds__(PU_THREADS) void k_paired_units(const float* __rest
                                                              int n_units, long long* __restrict__ units, long long* __restrict__ wins, int B) {
   const int b = blockIdx.x * PU_THREADS + threadIdx.x;
   if (b >= B) return;
-  long long* trailer = wins + (size_t)n_groups * JRR_BOOT_WINS_ROW;
   const int g = group[b];
-  if (g < 0) { boot_add(trailer + JRR_BOOT_WINS_TRAILER_IGNORED, 1); return; }
-  if (g >= n_groups) { boot_add(trailer + JRR_BOOT_WINS_TRAILER_BAD_GROUP, 1); return; }
+  if (long long* t = acc_refused(wins, JRR_BOOT_WINS_ROW, n_groups, g)) { acc_add(t, 1); return; }
   const int u = unit[b];
-  if (u < 0 || u >= n_units) { boot_add(trailer + JRR_BOOT_WINS_TRAILER_BAD_UNIT, 1); return; }
-  long long* wrow = wins + (size_t)g * JRR_BOOT_WINS_ROW;
+  if (u < 0 || u >= n_units) { acc_add(acc_trailer(wins, JRR_BOOT_WINS_ROW, n_groups) + JRR_BOOT_WINS_TRAILER_BAD_UNIT, 1); return; }
+  long long* wrow = acc_row(wins, JRR_BOOT_WINS_ROW, g);
   const float* src[4] = {before + (size_t)b * NH, before_pa + (size_t)b * NH, after + (size_t)b * NH, after_pa + (size_t)b * NH};
   long long S[4];
   bool good = true;
@@ -54,16 +51,16 @@ __global__ __launch_bounds__(PU_THREADS) void k_paired_units(const float* __rest
     }
     S[c] = s;
   }
-  if (!good) { boot_add(wrow + JRR_BOOT_WINS_BAD, 1); return; }
-  long long* urow = units + (size_t)u * JRR_BOOT_UNIT_ROW;
-  boot_add(urow + JRR_BOOT_UNIT_BEFORE, S[0]);
-  boot_add(urow + JRR_BOOT_UNIT_BEFORE_PA, S[1]);
-  boot_add(urow + JRR_BOOT_UNIT_AFTER, S[2]);
-  boot_add(urow + JRR_BOOT_UNIT_AFTER_PA, S[3]);
-  boot_add(urow + JRR_BOOT_UNIT_COUNT, 1);
-  boot_add(wrow + JRR_BOOT_WINS_COUNT, 1);
-  boot_add(wrow + (S[2] < S[0] ? JRR_BOOT_WINS_BETTER : (S[2] > S[0] ? JRR_BOOT_WINS_WORSE : JRR_BOOT_WINS_TIE)), 1);
-  boot_add(wrow + (S[3] < S[1] ? JRR_BOOT_WINS_BETTER_PA : (S[3] > S[1] ? JRR_BOOT_WINS_WORSE_PA : JRR_BOOT_WINS_TIE_PA)), 1);
+  if (!good) { acc_add(wrow + JRR_BOOT_WINS_BAD, 1); return; }
+  long long* urow = acc_row(units, JRR_BOOT_UNIT_ROW, u);
+  acc_add(urow + JRR_BOOT_UNIT_BEFORE, S[0]);
+  acc_add(urow + JRR_BOOT_UNIT_BEFORE_PA, S[1]);
+  acc_add(urow + JRR_BOOT_UNIT_AFTER, S[2]);
+  acc_add(urow + JRR_BOOT_UNIT_AFTER_PA, S[3]);
+  acc_add(urow + JRR_BOOT_UNIT_COUNT, 1);
+  acc_add(wrow + JRR_BOOT_WINS_COUNT, 1);
+  acc_add(wrow + (S[2] < S[0] ? JRR_BOOT_WINS_BETTER : (S[2] > S[0] ? JRR_BOOT_WINS_WORSE : JRR_BOOT_WINS_TIE)), 1);
+  acc_add(wrow + (S[3] < S[1] ? JRR_BOOT_WINS_BETTER_PA : (S[3] > S[1] ? JRR_BOOT_WINS_WORSE_PA : JRR_BOOT_WINS_TIE_PA)), 1);
 }
 
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC11): c <- ten rounds of c under key k
@@ -131,11 +128,11 @@ using namespace jrr;
 extern "C" int jrr_paired_units(const float* before, const float* before_pa, const float* after, const float* after_pa, const int32_t* group,
                                 const int32_t* unit, int batch, int n_groups, int n_units, int64_t* units, int64_t* wins, void* stream) {
   if (!before || !before_pa || !after || !after_pa || !group || !unit || !units || !wins || batch < 0 ||
-      (((uintptr_t)units | (uintptr_t)wins) & 7) != 0) {
+      !acc_aligned(units, wins)) {
     jrr_set_error("jrr_paired_units: bad argument");
     return JRR_ERR_ARG;
   }
-  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS || n_units < 1) {
+  if (!acc_groups_ok(n_groups) || n_units < 1) {
     jrr_set_error("jrr_paired_units: n_groups %d: 1 .. %d, n_units %d: at least 1", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS, n_units);
     return JRR_ERR_ARG;
   }

@@ -13,6 +13,7 @@
 //                      per group (include/jrr.h, JRR_DEPTH_ACC_*).  Integer atomics only, as k_shift_accumulate: the table does not
 //                      depend on the order, the split into calls or the sharding over ranks.
 #include "jrr_common.h"
+#include "acctab.h"
 #include "../../include/jrr.h"
 
 namespace jrr {
@@ -161,10 +162,6 @@ __global__ __launch_bounds__(DP_THREADS) void k_point_mesh_depth(DepthArgs q) {
 
 #pragma clang fp contract(off)
 
-__device__ __forceinline__ void dp_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
-
 // one wave per pose, lane k = point column k; every update is an int64 atomic
 __global__ __launch_bounds__(DP_ACC_THREADS) void k_depth_accumulate(const float* __restrict__ dist, const float* __restrict__ wind,
                                                                      const int* __restrict__ group, int n_points, int n_groups,
@@ -172,27 +169,25 @@ __global__ __launch_bounds__(DP_ACC_THREADS) void k_depth_accumulate(const float
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * (DP_ACC_THREADS / 64) + (threadIdx.x >> 6);
   if (b >= B) return;
-  long long* trailer = acc + (size_t)n_groups * JRR_DEPTH_ACC_ROW;
   const int g = group ? group[b] : 0;
-  if (g < 0) { if (lane == 0) dp_add(trailer + JRR_EVAL_ACC_TRAILER_IGNORED, 1); return; }
-  if (g >= n_groups) { if (lane == 0) dp_add(trailer + JRR_EVAL_ACC_TRAILER_BAD_GROUP, 1); return; }
-  long long* row = acc + (size_t)g * JRR_DEPTH_ACC_ROW;
+  if (long long* t = acc_refused(acc, JRR_DEPTH_ACC_ROW, n_groups, g)) { if (lane == 0) acc_add(t, 1); return; }
+  long long* row = acc_row(acc, JRR_DEPTH_ACC_ROW, g);
   const bool mine = lane < n_points;
   const float d = mine ? dist[(size_t)b * n_points + lane] : 0.f;
   const float wn = mine ? wind[(size_t)b * n_points + lane] : 0.f;
-  const bool bad = !(dp_finite(d) && dp_finite(wn) && d < 1.0e3f);
-  if (__any(bad)) { if (lane == 0) dp_add(row + JRR_DEPTH_ACC_BAD, 1); return; }   // a pose is counted whole or not at all
-  if (lane == 0) dp_add(row + JRR_DEPTH_ACC_COUNT, 1);
+  const bool bad = !(dp_finite(d) && dp_finite(wn) && d < ERR_CAP);
+  if (__any(bad)) { if (lane == 0) acc_add(row + JRR_DEPTH_ACC_BAD, 1); return; }   // a pose is counted whole or not at all
+  if (lane == 0) acc_add(row + JRR_DEPTH_ACC_COUNT, 1);
   if (!mine) return;
   const float aw = fabsf(wn);
   const bool inside = aw > 0.5f;
   const float depth = inside ? d : -d;
-  if (!inside) dp_add(row + JRR_DEPTH_ACC_OUTSIDE + lane, 1);
-  if (fabsf(aw - rintf(aw)) > 0.1f) dp_add(row + JRR_DEPTH_ACC_UNSURE + lane, 1);
-  dp_add(row + JRR_DEPTH_ACC_SUM + lane, __float2ll_rn(depth * DP_FIXED));
+  if (!inside) acc_add(row + JRR_DEPTH_ACC_OUTSIDE + lane, 1);
+  if (fabsf(aw - rintf(aw)) > 0.1f) acc_add(row + JRR_DEPTH_ACC_UNSURE + lane, 1);
+  acc_add(row + JRR_DEPTH_ACC_SUM + lane, __float2ll_rn(depth * DP_FIXED));
   const float t = depth + 0.064f;
   const int bin = max(min((int)floorf(t * 250.0f), JRR_DEPTH_ACC_BINS - 1), 0);
-  dp_add(row + JRR_DEPTH_ACC_HIST + lane * JRR_DEPTH_ACC_BINS + bin, 1);
+  acc_add(row + JRR_DEPTH_ACC_HIST + lane * JRR_DEPTH_ACC_BINS + bin, 1);
 }
 
 }  // namespace jrr
@@ -230,11 +225,11 @@ extern "C" int jrr_point_mesh_depth(const float* verts, int batch, int n_verts, 
 
 extern "C" int jrr_depth_accumulate(const float* dist, const float* wind, const int32_t* group, int batch, int n_points, int n_groups,
                                     int64_t* acc, void* stream) {
-  if (!dist || !wind || !acc || batch < 0 || ((uintptr_t)acc & 7) != 0) {
+  if (!dist || !wind || !acc || batch < 0 || !acc_aligned(acc)) {
     jrr_set_error("jrr_depth_accumulate: bad argument");
     return JRR_ERR_ARG;
   }
-  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS || n_points < 1 || n_points > JRR_DEPTH_MAX_POINTS) {
+  if (!acc_groups_ok(n_groups) || n_points < 1 || n_points > JRR_DEPTH_MAX_POINTS) {
     jrr_set_error("jrr_depth_accumulate: %d groups of %d points: 1 .. %d groups, 1 .. %d points", n_groups, n_points, (int)JRR_EVAL_ACC_MAX_GROUPS,
                   (int)JRR_DEPTH_MAX_POINTS);
     return JRR_ERR_ARG;

@@ -27,6 +27,7 @@
 #include "jrr_common.h"
 #include "evalk.h"
 #include "fixedpt.h"
+#include "acctab.h"
 #include "../../include/jrr.h"
 
 namespace jrr {
@@ -192,24 +193,18 @@ static int launch_regress_joints(const float* verts, const void* ws, int n_reg, 
 static_assert(JRR_EVAL_ACC_ROW == JRR_EVAL_ACC_HIST_PA + JRR_EVAL_ACC_BINS && JRR_EVAL_ACC_SUM_PA == JRR_EVAL_ACC_SUM + NH &&
               JRR_EVAL_ACC_HIST == JRR_EVAL_ACC_SUM_PA + NH && JRR_EVAL_ACC_HIST_PA == JRR_EVAL_ACC_HIST + JRR_EVAL_ACC_BINS, "row layout");
 
-__device__ __forceinline__ void acc_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
-
 // one pose per thread; every update is an int64 atomic
 __global__ __launch_bounds__(256) void k_eval_accumulate(const float* __restrict__ err_j, const float* __restrict__ err_pa_j,
                                                          const int* __restrict__ group, int n_groups, long long* __restrict__ acc, int B) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  long long* trailer = acc + (size_t)n_groups * JRR_EVAL_ACC_ROW;
   const int g = group[b];
-  if (g < 0) { acc_add(trailer + JRR_EVAL_ACC_TRAILER_IGNORED, 1); return; }
-  if (g >= n_groups) { acc_add(trailer + JRR_EVAL_ACC_TRAILER_BAD_GROUP, 1); return; }
-  long long* row = acc + (size_t)g * JRR_EVAL_ACC_ROW;
+  if (long long* t = acc_refused(acc, JRR_EVAL_ACC_ROW, n_groups, g)) { acc_add(t, 1); return; }
+  long long* row = acc_row(acc, JRR_EVAL_ACC_ROW, g);
   const float* e0 = err_j + (size_t)b * NH;
   const float* e1 = err_pa_j + (size_t)b * NH;
   bool good = true;
-  for (int i = 0; i < NH; ++i) good = good && (e0[i] < 1.0e3f) && (e1[i] < 1.0e3f);       // false for NaN
+  for (int i = 0; i < NH; ++i) good = good && (e0[i] < ERR_CAP) && (e1[i] < ERR_CAP);       // false for NaN
   if (!good) { acc_add(row + JRR_EVAL_ACC_BAD, 1); return; }
   acc_add(row + JRR_EVAL_ACC_COUNT, 1);
   for (int i = 0; i < NH; ++i) {
@@ -278,14 +273,11 @@ extern "C" int jrr_regress_joints(const float* verts, int batch, const void* wor
 }
 extern "C" int jrr_eval_accumulate(const float* err_j, const float* err_pa_j, const int32_t* group, int batch, int n_groups, int64_t* acc,
                                    void* stream) {
-  if (!err_j || !err_pa_j || !group || !acc || batch < 0 || ((uintptr_t)acc & 7) != 0) {
+  if (!err_j || !err_pa_j || !group || !acc || batch < 0 || !acc_aligned(acc)) {
     jrr_set_error("jrr_eval_accumulate: bad argument");
     return JRR_ERR_ARG;
   }
-  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS) {
-    jrr_set_error("jrr_eval_accumulate: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
-    return JRR_ERR_ARG;
-  }
+  if (acc_groups_refused("jrr_eval_accumulate", n_groups)) return JRR_ERR_ARG;
   if (batch == 0) return JRR_OK;
   hipLaunchKernelGGL(k_eval_accumulate, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, err_j, err_pa_j, group, n_groups,
                      reinterpret_cast<long long*>(acc), batch);

@@ -17,6 +17,7 @@
 //                           JRR_PEN_ACC_*) and the per-vertex counts.  Integer atomics only: the tables do not depend on the order, the
 //                           split into calls or the sharding over ranks.
 #include "jrr_common.h"
+#include "acctab.h"
 #include "../../include/jrr.h"
 
 namespace jrr {
@@ -130,10 +131,6 @@ __global__ __launch_bounds__(PN_THREADS) void k_mesh_winding(WindingArgs q) {
 
 #pragma clang fp contract(off)
 
-__device__ __forceinline__ void pn_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
-
 // bit 0: penetrating, bit 1: thin, bit 2: unsure, bit 3: not finite
 __device__ __forceinline__ int pn_classify(float w) {
   const float aw = fabsf(w), k = rintf(aw);
@@ -173,30 +170,28 @@ __global__ __launch_bounds__(PN_ACC_THREADS) void k_penetration_accumulate(PenAc
     if (q.n_thin) q.n_thin[b] = n_thin;
     if (q.n_unsure) q.n_unsure[b] = n_unsure;
   }
-  long long* trailer = q.acc + (size_t)q.n_groups * JRR_PEN_ACC_ROW;
   const int g = q.group ? q.group[b] : 0;
-  if (g < 0) { if (tid == 0) pn_add(trailer + JRR_EVAL_ACC_TRAILER_IGNORED, 1); return; }
-  if (g >= q.n_groups) { if (tid == 0) pn_add(trailer + JRR_EVAL_ACC_TRAILER_BAD_GROUP, 1); return; }
-  long long* row = q.acc + (size_t)g * JRR_PEN_ACC_ROW;
-  if (bad) { if (tid == 0) pn_add(row + JRR_PEN_ACC_BAD, 1); return; }      // a pose is counted whole or not at all
+  if (long long* t = acc_refused(q.acc, JRR_PEN_ACC_ROW, q.n_groups, g)) { if (tid == 0) acc_add(t, 1); return; }
+  long long* row = acc_row(q.acc, JRR_PEN_ACC_ROW, g);
+  if (bad) { if (tid == 0) acc_add(row + JRR_PEN_ACC_BAD, 1); return; }      // a pose is counted whole or not at all
   if (tid == 0) {
-    pn_add(row + JRR_PEN_ACC_COUNT, 1);
-    if (n_pen >= 1) pn_add(row + JRR_PEN_ACC_POSES_PEN, 1);
-    if (n_pen >= 8) pn_add(row + JRR_PEN_ACC_POSES_PEN8, 1);
-    if (n_pen) pn_add(row + JRR_PEN_ACC_SUM_PEN, n_pen);
-    if (n_thin) pn_add(row + JRR_PEN_ACC_SUM_THIN, n_thin);
-    if (n_unsure) pn_add(row + JRR_PEN_ACC_SUM_UNSURE, n_unsure);
-    pn_add(row + JRR_PEN_ACC_HIST + min(JRR_PEN_ACC_BINS - 1, 32 - __clz(n_pen)), 1);      // the number of bits of n_pen; __clz(0) = 32
+    acc_add(row + JRR_PEN_ACC_COUNT, 1);
+    if (n_pen >= 1) acc_add(row + JRR_PEN_ACC_POSES_PEN, 1);
+    if (n_pen >= 8) acc_add(row + JRR_PEN_ACC_POSES_PEN8, 1);
+    if (n_pen) acc_add(row + JRR_PEN_ACC_SUM_PEN, n_pen);
+    if (n_thin) acc_add(row + JRR_PEN_ACC_SUM_THIN, n_thin);
+    if (n_unsure) acc_add(row + JRR_PEN_ACC_SUM_UNSURE, n_unsure);
+    acc_add(row + JRR_PEN_ACC_HIST + min(JRR_PEN_ACC_BINS - 1, 32 - __clz(n_pen)), 1);      // the number of bits of n_pen; __clz(0) = 32
   }
   if (n_pen == 0) return;
   for (int v = tid; v < q.n_verts; v += PN_ACC_THREADS) {
     if (!(pn_classify(w[v]) & 1)) continue;
-    if (q.per_vertex) pn_add(q.per_vertex + v, 1);
+    if (q.per_vertex) acc_add(q.per_vertex + v, 1);
     const int pl = q.part ? q.part[v] : 0;
     atomicAdd(&s_part[(unsigned)pl < (unsigned)JRR_PEN_ACC_PARTS ? pl : JRR_PEN_ACC_PARTS - 1], 1);
   }
   __syncthreads();
-  if (tid < JRR_PEN_ACC_PARTS && s_part[tid]) pn_add(row + JRR_PEN_ACC_PART + tid, s_part[tid]);
+  if (tid < JRR_PEN_ACC_PARTS && s_part[tid]) acc_add(row + JRR_PEN_ACC_PART + tid, s_part[tid]);
 }
 
 }  // namespace jrr
@@ -230,12 +225,12 @@ extern "C" int jrr_mesh_winding(const float* verts, int batch, int n_verts, cons
 
 extern "C" int jrr_penetration_accumulate(const float* wind, const int32_t* part, const int32_t* group, int batch, int n_verts, int n_groups,
                                           int64_t* acc, int64_t* per_vertex, int32_t* n_pen, int32_t* n_thin, int32_t* n_unsure, void* stream) {
-  if (!wind || !acc || batch < 0 || (((uintptr_t)acc | (uintptr_t)per_vertex) & 7) != 0 ||
+  if (!wind || !acc || batch < 0 || !acc_aligned(acc, per_vertex) ||
       (((uintptr_t)wind | (uintptr_t)part | (uintptr_t)group | (uintptr_t)n_pen | (uintptr_t)n_thin | (uintptr_t)n_unsure) & 3) != 0) {
     jrr_set_error("jrr_penetration_accumulate: bad argument (wind and acc must not be NULL, batch >= 0, the tables 8-byte aligned, the others 4)");
     return JRR_ERR_ARG;
   }
-  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS || n_verts < 1 || n_verts > JRR_WINDING_MAX_POINTS) {
+  if (!acc_groups_ok(n_groups) || n_verts < 1 || n_verts > JRR_WINDING_MAX_POINTS) {
     jrr_set_error("jrr_penetration_accumulate: %d groups of %d vertices: 1 .. %d groups, 1 .. %d vertices", n_groups, n_verts,
                   (int)JRR_EVAL_ACC_MAX_GROUPS, (int)JRR_WINDING_MAX_POINTS);
     return JRR_ERR_ARG;

@@ -22,6 +22,7 @@
 // follows it.
 #pragma clang fp contract(off)
 #include "jrr_common.h"
+#include "acctab.h"
 #include "../../include/jrr.h"
 #include "procfit.h"
 
@@ -40,10 +41,6 @@ static_assert(JRR_PVE_ACC_COUNT == 0 && JRR_PVE_ACC_BAD == 1 && JRR_PVE_ACC_SUM 
               JRR_PVE_ACC_PART_PA == JRR_PVE_ACC_PART + JRR_PVE_MAX_PARTS && JRR_PVE_ACC_ROW == JRR_PVE_ACC_PART_PA + JRR_PVE_MAX_PARTS &&
               JRR_PVE_ACC_BINS == JRR_EVAL_ACC_BINS && JRR_PVE_ACC_TRAILER == JRR_EVAL_ACC_TRAILER, "row layout");
 static_assert(PV_SMALL >= 6890 && JRR_PVE_MAX_VERTS == 65536, "sizes");
-
-__device__ __forceinline__ void pv_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
 
 // sum over the workgroup of each of v[0 .. N): on return every thread holds the same N sums.  s_red: PV_W * N words.
 template <class T, int N>
@@ -81,8 +78,8 @@ __device__ __forceinline__ float pv_aligned(const float x[3], const float y[3], 
   }
   return sqrtf(d2);
 }
-// the fixed-point value of a distance; 0 for one that fails v < 1.0e3f (its pose is then not counted)
-__device__ __forceinline__ long long pv_fixed(float v) { return v < 1.0e3f ? __float2ll_rn(v * PV_FIXED) : 0ll; }
+// the fixed-point value of a distance; 0 for one that fails v < ERR_CAP (its pose is then not counted)
+__device__ __forceinline__ long long pv_fixed(float v) { return v < ERR_CAP ? __float2ll_rn(v * PV_FIXED) : 0ll; }
 
 template <bool SMALL>
 __global__ __launch_bounds__(PV_T) void k_vertex_error(const float* __restrict__ pred, const float* __restrict__ gt,
@@ -167,31 +164,31 @@ __global__ __launch_bounds__(PV_T) void k_vertex_error(const float* __restrict__
 
     // whether the pose can reach the per-vertex table is known now; whether its means are NaN only after walk C
     const int gid = group ? group[b] : 0;
-    const bool in_range = gid >= 0 && gid < n_groups;
+    const bool in_range = acc_group_kind(gid, n_groups) == ACC_COUNTED;
     const bool want_v = acc_v && (in_range || (!acc && !group));
     auto add_v = [&](int i, long long qd, long long qe) __attribute__((always_inline)) {
       if constexpr (SMALL) {
         s_v[i] += qd;                                      // vertex i belongs to this thread alone
         s_v[PV_SMALL + i] += qe;
       } else {
-        if (qd != 0) pv_add(acc_v + i, qd);
-        if (qe != 0) pv_add(acc_v + (size_t)n + i, qe);
+        if (qd != 0) acc_add(acc_v + i, qd);
+        if (qe != 0) acc_add(acc_v + (size_t)n + i, qe);
       }
     };
 
     // walk A: the plain error, the sums of x and y
     double sm[6] = {0., 0., 0., 0., 0., 0.};
-    long long si[2] = {0, 0};                              // the fixed-point sum; vertices that fail d < 1.0e3f
+    long long si[2] = {0, 0};                              // the fixed-point sum; vertices that fail d < ERR_CAP
     each(First{}, [&](int i, const float* x, const float* y) __attribute__((always_inline)) {
       const float d = pv_plain(x, y);
       if (err_v) err_v[(size_t)b * n + i] = d;
       const long long q = pv_fixed(d);
       si[0] += q;
-      si[1] += d < 1.0e3f ? 0 : 1;
+      si[1] += d < ERR_CAP ? 0 : 1;
       if (want_v) add_v(i, q, 0);
       if (part) {
         const int p = part[i];
-        if (p >= 0 && p < n_parts) pv_add(&s_part[0][wave][p], q);
+        if (p >= 0 && p < n_parts) acc_add(&s_part[0][wave][p], q);
       }
 #pragma unroll
       for (int c = 0; c < 3; ++c) { sm[c] += (double)x[c]; sm[3 + c] += (double)y[c]; }
@@ -235,11 +232,11 @@ __global__ __launch_bounds__(PV_T) void k_vertex_error(const float* __restrict__
       if (err_pa_v) err_pa_v[(size_t)b * n + i] = e;
       const long long q = pv_fixed(e);
       si[0] += q;
-      si[1] += e < 1.0e3f ? 0 : 1;
+      si[1] += e < ERR_CAP ? 0 : 1;
       if (want_v) add_v(i, 0, q);
       if (part) {
         const int p = part[i];
-        if (p >= 0 && p < n_parts) pv_add(&s_part[1][wave][p], q);
+        if (p >= 0 && p < n_parts) acc_add(&s_part[1][wave][p], q);
       }
     });
     pv_block_sum(si, s_redi, tid);                         // its barriers also order the ds atomics of s_part before the reads below
@@ -252,18 +249,16 @@ __global__ __launch_bounds__(PV_T) void k_vertex_error(const float* __restrict__
     // the tables (uniform branches: every thread holds the same values)
     const bool counted = (in_range || (!acc && !group)) && v_pve == v_pve && v_pa == v_pa;
     if (acc) {
-      long long* trailer = acc + (size_t)n_groups * JRR_PVE_ACC_ROW;
-      long long* row = acc + (size_t)(in_range ? gid : 0) * JRR_PVE_ACC_ROW;
+      long long* row = acc_row(acc, JRR_PVE_ACC_ROW, in_range ? gid : 0);
       if (tid == 0) {
-        if (gid < 0) pv_add(trailer + JRR_EVAL_ACC_TRAILER_IGNORED, 1);
-        else if (gid >= n_groups) pv_add(trailer + JRR_EVAL_ACC_TRAILER_BAD_GROUP, 1);
-        else if (!counted) pv_add(row + JRR_PVE_ACC_BAD, 1);
+        if (long long* t = acc_refused(acc, JRR_PVE_ACC_ROW, n_groups, gid)) acc_add(t, 1);
+        else if (!counted) acc_add(row + JRR_PVE_ACC_BAD, 1);
         else {
-          pv_add(row + JRR_PVE_ACC_COUNT, 1);
-          pv_add(row + JRR_PVE_ACC_SUM, __float2ll_rn(v_pve * PV_FIXED));
-          pv_add(row + JRR_PVE_ACC_SUM_PA, __float2ll_rn(v_pa * PV_FIXED));
-          pv_add(row + JRR_PVE_ACC_HIST + min((int)floorf(v_pve * 1000.f), JRR_PVE_ACC_BINS - 1), 1);
-          pv_add(row + JRR_PVE_ACC_HIST_PA + min((int)floorf(v_pa * 1000.f), JRR_PVE_ACC_BINS - 1), 1);
+          acc_add(row + JRR_PVE_ACC_COUNT, 1);
+          acc_add(row + JRR_PVE_ACC_SUM, __float2ll_rn(v_pve * PV_FIXED));
+          acc_add(row + JRR_PVE_ACC_SUM_PA, __float2ll_rn(v_pa * PV_FIXED));
+          acc_add(row + JRR_PVE_ACC_HIST + min((int)floorf(v_pve * 1000.f), JRR_PVE_ACC_BINS - 1), 1);
+          acc_add(row + JRR_PVE_ACC_HIST_PA + min((int)floorf(v_pa * 1000.f), JRR_PVE_ACC_BINS - 1), 1);
         }
       }
       if (part && counted && in_range && tid >= 64 && tid < 64 + 2 * PV_PARTS) {      // one thread per (plain | aligned, part), off wave 0
@@ -272,7 +267,7 @@ __global__ __launch_bounds__(PV_T) void k_vertex_error(const float* __restrict__
           long long s = 0;
           for (int w = 0; w < PV_W; ++w) s += s_part[which][w][p];
           const float m = (float)((double)s / ((double)s_np[p] * 16777216.0));
-          pv_add(row + (which ? JRR_PVE_ACC_PART_PA : JRR_PVE_ACC_PART) + p, __float2ll_rn(m * PV_FIXED));
+          acc_add(row + (which ? JRR_PVE_ACC_PART_PA : JRR_PVE_ACC_PART) + p, __float2ll_rn(m * PV_FIXED));
         }
       }
     }
@@ -289,8 +284,8 @@ __global__ __launch_bounds__(PV_T) void k_vertex_error(const float* __restrict__
   if (SMALL && acc_v)
     for (int i = tid; i < n; i += PV_T) {                  // the thread's own words: no barrier needed
       const long long qd = s_v[i], qe = s_v[PV_SMALL + i];
-      if (qd != 0) pv_add(acc_v + i, qd);
-      if (qe != 0) pv_add(acc_v + (size_t)n + i, qe);
+      if (qd != 0) acc_add(acc_v + i, qd);
+      if (qe != 0) acc_add(acc_v + (size_t)n + i, qe);
     }
 }
 
@@ -307,16 +302,13 @@ extern "C" int jrr_vertex_error(const float* pred, const float* gt, const float*
   else if (batch < 0 || n_verts < 1 || n_verts > JRR_PVE_MAX_VERTS) why = "batch must be >= 0, n_verts in 1 .. 65536";
   else if (part && (n_parts < 1 || n_parts > JRR_PVE_MAX_PARTS)) why = "n_parts must lie in 1 .. 32 when part is given";
   else if ((((uintptr_t)pred | (uintptr_t)gt | (uintptr_t)root_pred | (uintptr_t)root_gt | (uintptr_t)group | (uintptr_t)part | (uintptr_t)pve |
-             (uintptr_t)pa_pve | (uintptr_t)err_v | (uintptr_t)err_pa_v) & 3) != 0 || (((uintptr_t)acc | (uintptr_t)acc_v) & 7) != 0)
+             (uintptr_t)pa_pve | (uintptr_t)err_v | (uintptr_t)err_pa_v) & 3) != 0 || !acc_aligned(acc, acc_v))
     why = "the float and int32 arrays must be 4-byte aligned, acc and acc_v 8-byte aligned";
   if (why) {
     jrr_set_error("jrr_vertex_error: %s", why);
     return JRR_ERR_ARG;
   }
-  if ((acc || (acc_v && group)) && (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS)) {
-    jrr_set_error("jrr_vertex_error: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
-    return JRR_ERR_ARG;
-  }
+  if ((acc || (acc_v && group)) && acc_groups_refused("jrr_vertex_error", n_groups)) return JRR_ERR_ARG;
   if (batch == 0) return JRR_OK;
   long long* a = reinterpret_cast<long long*>(acc);
   long long* av = reinterpret_cast<long long*>(acc_v);

@@ -13,6 +13,7 @@
 // Every floating-point operation is stated in include/jrr.h and rounded once, in the order written (no product is fused into a sum), so
 // a host restatement follows it.
 #include "jrr_common.h"
+#include "acctab.h"
 #include "../../include/jrr.h"
 
 namespace jrr {
@@ -35,9 +36,6 @@ __device__ __forceinline__ void rr_cross(const float* a, const float* b, float* 
   o[1] = a[2] * b[0] - a[0] * b[2];
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
-__device__ __forceinline__ void rr_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
 
 // one pose per thread; every update is an int64 atomic
 __global__ __launch_bounds__(RR_THREADS) void k_shift_accumulate(const float* __restrict__ ja, const float* __restrict__ jb,
@@ -45,11 +43,9 @@ __global__ __launch_bounds__(RR_THREADS) void k_shift_accumulate(const float* __
                                                                  int B) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  long long* trailer = acc + (size_t)n_groups * JRR_SHIFT_ACC_ROW;
   const int g = group ? group[b] : 0;
-  if (g < 0) { rr_add(trailer + JRR_EVAL_ACC_TRAILER_IGNORED, 1); return; }
-  if (g >= n_groups) { rr_add(trailer + JRR_EVAL_ACC_TRAILER_BAD_GROUP, 1); return; }
-  long long* row = acc + (size_t)g * JRR_SHIFT_ACC_ROW;
+  if (long long* t = acc_refused(acc, JRR_SHIFT_ACC_ROW, n_groups, g)) { acc_add(t, 1); return; }
+  long long* row = acc_row(acc, JRR_SHIFT_ACC_ROW, g);
   const float* pa = ja + (size_t)b * NH * 3;
   const float* pb = jb + (size_t)b * NH * 3;
 
@@ -77,8 +73,8 @@ __global__ __launch_bounds__(RR_THREADS) void k_shift_accumulate(const float* __
       good = good && fabsf(rr_dot(d, xh)) < 4.0f && fabsf(rr_dot(d, yh)) < 4.0f && fabsf(rr_dot(d, zh)) < 4.0f;
     }
   }
-  if (!good) { rr_add(row + JRR_SHIFT_ACC_BAD, 1); return; }
-  rr_add(row + JRR_SHIFT_ACC_COUNT, 1);
+  if (!good) { acc_add(row + JRR_SHIFT_ACC_BAD, 1); return; }
+  acc_add(row + JRR_SHIFT_ACC_COUNT, 1);
   const float d0[3] = {pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2]};
   for (int j = 0; j < NH; ++j) {
     const float d[3] = {pb[j * 3] - pa[j * 3], pb[j * 3 + 1] - pa[j * 3 + 1], pb[j * 3 + 2] - pa[j * 3 + 2]};
@@ -87,17 +83,17 @@ __global__ __launch_bounds__(RR_THREADS) void k_shift_accumulate(const float* __
     int m = 0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-      rr_add(row + JRR_SHIFT_ACC_SUM + j * 3 + i, q[i]);
+      acc_add(row + JRR_SHIFT_ACC_SUM + j * 3 + i, q[i]);
 #pragma unroll
-      for (int k = i; k < 3; ++k, ++m) rr_add(row + JRR_SHIFT_ACC_MOM + j * 6 + m, (q[i] * q[k]) >> 16);
+      for (int k = i; k < 3; ++k, ++m) acc_add(row + JRR_SHIFT_ACC_MOM + j * 6 + m, (q[i] * q[k]) >> 16);
     }
     const float len = sqrtf(rr_dot(d, d));
     const float r[3] = {d[0] - d0[0], d[1] - d0[1], d[2] - d0[2]};
     const float rel = sqrtf(rr_dot(r, r));
-    rr_add(row + JRR_SHIFT_ACC_ABS + j, __float2ll_rn(len * RR_FIXED));
-    rr_add(row + JRR_SHIFT_ACC_ABS_REL + j, __float2ll_rn(rel * RR_FIXED));
+    acc_add(row + JRR_SHIFT_ACC_ABS + j, __float2ll_rn(len * RR_FIXED));
+    acc_add(row + JRR_SHIFT_ACC_ABS_REL + j, __float2ll_rn(rel * RR_FIXED));
     const int bin = max(min((int)floorf(len * 500.0f), JRR_SHIFT_ACC_BINS - 1), 0);
-    rr_add(row + JRR_SHIFT_ACC_HIST + j * JRR_SHIFT_ACC_BINS + bin, 1);
+    acc_add(row + JRR_SHIFT_ACC_HIST + j * JRR_SHIFT_ACC_BINS + bin, 1);
   }
 }
 
@@ -156,14 +152,11 @@ using namespace jrr;
 
 extern "C" int jrr_regressor_shift_accumulate(const float* joints_a, const float* joints_b, const int32_t* group, int batch, int n_groups,
                                               int64_t* acc, void* stream) {
-  if (!joints_a || !joints_b || !acc || batch < 0 || ((uintptr_t)acc & 7) != 0) {
+  if (!joints_a || !joints_b || !acc || batch < 0 || !acc_aligned(acc)) {
     jrr_set_error("jrr_regressor_shift_accumulate: bad argument");
     return JRR_ERR_ARG;
   }
-  if (n_groups < 1 || n_groups > JRR_EVAL_ACC_MAX_GROUPS) {
-    jrr_set_error("jrr_regressor_shift_accumulate: n_groups %d: 1 .. %d", n_groups, (int)JRR_EVAL_ACC_MAX_GROUPS);
-    return JRR_ERR_ARG;
-  }
+  if (acc_groups_refused("jrr_regressor_shift_accumulate", n_groups)) return JRR_ERR_ARG;
   if (batch == 0) return JRR_OK;
   hipLaunchKernelGGL(k_shift_accumulate, dim3((unsigned)((batch + RR_THREADS - 1) / RR_THREADS)), dim3(RR_THREADS), 0, (hipStream_t)stream, joints_a,
                      joints_b, group, n_groups, reinterpret_cast<long long*>(acc), batch);

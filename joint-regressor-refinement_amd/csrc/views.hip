@@ -21,6 +21,7 @@
 #include "jrr_common.h"
 #include "rot6.h"
 #include "quat.h"
+#include "acctab.h"
 #include "../../include/jrr.h"
 
 // rot6d_fwd, included above, keeps the default contraction it has in the loop's kernels; everything below is rounded once per operation,
@@ -89,10 +90,6 @@ __device__ __forceinline__ Quat load_quat(const float4* s_q, int i) {
   return q;
 }
 
-__device__ __forceinline__ void vf_add(long long* p, long long v) {
-  atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
-}
-
 // grid: ceil(count / 64) workgroups of 64 threads, one position per thread
 __global__ __launch_bounds__(VF_RR_THREADS) void k_view_relrot(const float* __restrict__ table, long long n_rows, const int* __restrict__ order,
                                                                const int* __restrict__ group, const int* __restrict__ pair,
@@ -125,14 +122,14 @@ __global__ __launch_bounds__(VF_RR_THREADS) void k_view_relrot(const float* __re
   const float ev[4] = {e.w, e.x, e.y, e.z};
   if (!(fabsf(e.w) <= 2.f && fabsf(e.x) <= 2.f && fabsf(e.y) <= 2.f && fabsf(e.z) <= 2.f)) return;
   long long* out = acc + (size_t)c * JRR_FUSE_ACC_ROW;
-  vf_add(out, 1);
+  acc_add(out, 1);
   int w = 1;
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
     for (int b = a; b < 4; ++b) {
       const float prod = ev[a] * ev[b];
-      vf_add(out + w, llrintf(prod * VF_FIX));
+      acc_add(out + w, llrintf(prod * VF_FIX));
       ++w;
     }
 }

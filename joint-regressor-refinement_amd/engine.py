@@ -906,16 +906,27 @@ def price_vertices(verts: torch.Tensor, gt_centred_mm: torch.Tensor, vtx, counts
 EVAL_ACC_ROW, EVAL_ACC_TRAILER = 338, 2         # include/jrr.h: JRR_EVAL_ACC_ROW, JRR_EVAL_ACC_TRAILER
 
 
+def _check_acc(acc: torch.Tensor, n_groups: int, row: int, trailer: int, dev) -> None:
+    """a grouped int64 accumulator (csrc/acctab.h): contiguous, on `dev`, n_groups * row + trailer words"""
+    assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.device == dev
+    assert acc.numel() == int(n_groups) * row + trailer
+
+
+def _check_ids(ids: torch.Tensor, n: int, dev) -> None:
+    """the group (or unit) ids of n poses: (n,) int32, contiguous, on `dev`"""
+    assert ids.shape == (n,) and ids.dtype == torch.int32 and ids.is_contiguous() and ids.device == dev
+
+
 def eval_accumulate(err_j: torch.Tensor, err_pa_j: torch.Tensor, group: torch.Tensor, n_groups: int, acc: torch.Tensor) -> None:
     """jrr_eval_accumulate: ADD the poses' per-joint errors (B,17) to rows `group` (B, int32) of the int64 table `acc`
     (n_groups * 338 + 2 words, include/jrr.h JRR_EVAL_ACC_*)"""
     lib = _lib.load()
     B = err_j.shape[0]
     err_j, err_pa_j, group = err_j.contiguous(), err_pa_j.contiguous(), group.contiguous()
-    assert err_j.shape == (B, 17) and err_pa_j.shape == (B, 17) and group.shape == (B,)
-    assert err_j.dtype == torch.float32 and err_pa_j.dtype == torch.float32 and group.dtype == torch.int32 and acc.dtype == torch.int64
-    assert acc.is_contiguous() and acc.numel() == n_groups * EVAL_ACC_ROW + EVAL_ACC_TRAILER
-    assert all(t.device == err_j.device for t in (err_pa_j, group, acc))
+    assert err_j.shape == (B, 17) and err_pa_j.shape == (B, 17) and err_j.dtype == torch.float32 and err_pa_j.dtype == torch.float32
+    assert err_pa_j.device == err_j.device
+    _check_ids(group, B, err_j.device)
+    _check_acc(acc, n_groups, EVAL_ACC_ROW, EVAL_ACC_TRAILER, err_j.device)
     check(lib.jrr_eval_accumulate(ptr(err_j), ptr(err_pa_j), ptr(group), B, int(n_groups), ptr(acc), stream_ptr(err_j.device)),
           'eval_accumulate')
 
@@ -941,10 +952,9 @@ def accel_error(pred: torch.Tensor, gt_mm: torch.Tensor, order: torch.Tensor, ru
     assert order.is_contiguous() and run.is_contiguous() and status.is_contiguous() and status.dtype == torch.int32
     assert all(t.device == dev for t in (gt_mm, order, run, status))
     if group is not None:
-        assert group.shape == (M,) and group.dtype == torch.int32 and group.is_contiguous() and group.device == dev
+        _check_ids(group, M, dev)
     if acc is not None:
-        assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.device == dev
-        assert acc.numel() == int(n_groups) * ACCEL_ACC_ROW + ACCEL_ACC_TRAILER
+        _check_acc(acc, n_groups, ACCEL_ACC_ROW, ACCEL_ACC_TRAILER, dev)
     begin = int(begin)
     count = M - begin if count is None else int(count)
     if rows:
@@ -978,12 +988,11 @@ def vertex_error(pred: torch.Tensor, gt: torch.Tensor, root_pred: Optional[torch
     for r in (root_pred, root_gt):
         assert r is None or (r.shape == (B, 3) and r.dtype == torch.float32 and r.is_contiguous() and r.device == dev)
     if group is not None:
-        assert group.shape == (B,) and group.dtype == torch.int32 and group.is_contiguous() and group.device == dev
+        _check_ids(group, B, dev)
     if part is not None:
         assert part.shape == (n,) and part.dtype == torch.int32 and part.is_contiguous() and part.device == dev
     if acc is not None:
-        assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.device == dev
-        assert acc.numel() == int(n_groups) * PVE_ACC_ROW + PVE_ACC_TRAILER
+        _check_acc(acc, n_groups, PVE_ACC_ROW, PVE_ACC_TRAILER, dev)
     if acc_v is not None:
         assert acc_v.dtype == torch.int64 and acc_v.is_contiguous() and acc_v.device == dev and acc_v.shape == (2, n)
     pve, pa = (torch.empty(B, device=dev), torch.empty(B, device=dev)) if means else (None, None)
@@ -1010,9 +1019,10 @@ def paired_units(before: torch.Tensor, before_pa: torch.Tensor, after: torch.Ten
     group, unit = group.contiguous(), unit.contiguous()
     dev = errs[0].device
     assert all(t.shape == (B, 17) and t.dtype == torch.float32 and t.device == dev for t in errs)
-    assert all(t.shape == (B,) and t.dtype == torch.int32 and t.device == dev for t in (group, unit))
+    _check_ids(group, B, dev)
+    _check_ids(unit, B, dev)
     assert units.dtype == torch.int64 and units.is_contiguous() and units.dim() == 2 and units.shape[1] == BOOT_UNIT_ROW and units.device == dev
-    assert wins.dtype == torch.int64 and wins.is_contiguous() and wins.numel() == int(n_groups) * BOOT_WINS_ROW + BOOT_WINS_TRAILER and wins.device == dev
+    _check_acc(wins, n_groups, BOOT_WINS_ROW, BOOT_WINS_TRAILER, dev)
     if B == 0:                                      # an empty tensor has no address to pass
         return
     check(lib.jrr_paired_units(ptr(errs[0]), ptr(errs[1]), ptr(errs[2]), ptr(errs[3]), ptr(group), ptr(unit), B, int(n_groups), int(units.shape[0]),
@@ -1060,12 +1070,12 @@ def regressor_shift_accumulate(joints_a: torch.Tensor, joints_b: torch.Tensor, g
     B = joints_a.shape[0]
     joints_a, joints_b = joints_a.contiguous(), joints_b.contiguous()
     assert joints_a.shape == (B, 17, 3) and joints_b.shape == (B, 17, 3)
-    assert joints_a.dtype == torch.float32 and joints_b.dtype == torch.float32 and acc.dtype == torch.int64
-    assert acc.is_contiguous() and acc.numel() == n_groups * SHIFT_ACC_ROW + SHIFT_ACC_TRAILER
-    assert joints_a.is_cuda and joints_b.device == joints_a.device and acc.device == joints_a.device
+    assert joints_a.dtype == torch.float32 and joints_b.dtype == torch.float32
+    assert joints_a.is_cuda and joints_b.device == joints_a.device
+    _check_acc(acc, n_groups, SHIFT_ACC_ROW, SHIFT_ACC_TRAILER, joints_a.device)
     if group is not None:
         group = group.contiguous()
-        assert group.shape == (B,) and group.dtype == torch.int32 and group.device == joints_a.device
+        _check_ids(group, B, joints_a.device)
     check(lib.jrr_regressor_shift_accumulate(ptr(joints_a), ptr(joints_b), ptr(group), B, int(n_groups), ptr(acc),
                                              stream_ptr(joints_a.device)), 'regressor_shift_accumulate')
 
@@ -1139,11 +1149,11 @@ def depth_accumulate(dist: torch.Tensor, wind: torch.Tensor, group: Optional[tor
     B = int(dist.shape[0])
     dist, wind = dist.contiguous(), wind.contiguous()
     assert dist.dim() == 2 and wind.shape == dist.shape and dist.dtype == torch.float32 and wind.dtype == torch.float32
-    assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.numel() == int(n_groups) * DEPTH_ACC_ROW + DEPTH_ACC_TRAILER
-    assert dist.is_cuda and wind.device == dist.device and acc.device == dist.device
+    assert dist.is_cuda and wind.device == dist.device
+    _check_acc(acc, n_groups, DEPTH_ACC_ROW, DEPTH_ACC_TRAILER, dist.device)
     if group is not None:
         group = group.contiguous()
-        assert group.shape == (B,) and group.dtype == torch.int32 and group.device == dist.device
+        _check_ids(group, B, dist.device)
     if B == 0:
         return
     check(lib.jrr_depth_accumulate(ptr(dist), ptr(wind), ptr(group), B, int(dist.shape[1]), int(n_groups), ptr(acc), stream_ptr(dist.device)),
@@ -1188,9 +1198,10 @@ def penetration_accumulate(wind: torch.Tensor, part: Optional[torch.Tensor], gro
     lib = _lib.load()
     assert wind.dim() == 2 and wind.dtype == torch.float32 and wind.is_cuda and wind.is_contiguous()
     B, n, dev = int(wind.shape[0]), int(wind.shape[1]), wind.device
-    assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.device == dev and acc.numel() == int(n_groups) * PEN_ACC_ROW + PEN_ACC_TRAILER
+    _check_acc(acc, n_groups, PEN_ACC_ROW, PEN_ACC_TRAILER, dev)
     assert part is None or (part.shape == (n,) and part.dtype == torch.int32 and part.is_contiguous() and part.device == dev)
-    assert group is None or (group.shape == (B,) and group.dtype == torch.int32 and group.is_contiguous() and group.device == dev)
+    if group is not None:
+        _check_ids(group, B, dev)
     assert per_vertex is None or (per_vertex.shape == (n,) and per_vertex.dtype == torch.int64 and per_vertex.is_contiguous() and per_vertex.device == dev)
     for c in (n_pen, n_thin, n_unsure):
         assert c is None or (c.shape == (B,) and c.dtype == torch.int32 and c.is_contiguous() and c.device == dev)
@@ -1228,11 +1239,10 @@ def bone_accumulate(vals: torch.Tensor, group: Optional[torch.Tensor], n_groups:
     B = int(vals.shape[0])
     vals = vals.contiguous()
     assert vals.shape == (B, BONE_VALS) and vals.dtype == torch.float32 and vals.is_cuda
-    assert acc.dtype == torch.int64 and acc.is_contiguous() and acc.numel() == int(n_groups) * BONE_ACC_ROW + BONE_ACC_TRAILER
-    assert acc.device == vals.device
+    _check_acc(acc, n_groups, BONE_ACC_ROW, BONE_ACC_TRAILER, vals.device)
     if group is not None:
         group = group.contiguous()
-        assert group.shape == (B,) and group.dtype == torch.int32 and group.device == vals.device
+        _check_ids(group, B, vals.device)
     if B == 0:
         return
     check(lib.jrr_bone_accumulate(ptr(vals), ptr(group), B, int(n_groups), ptr(acc), stream_ptr(vals.device)), 'bone_accumulate')

@@ -20,7 +20,6 @@ vertices.  No SMPL model file, no engine.  `--eval_pve` adds the per-vertex erro
 from __future__ import annotations
 
 import hashlib
-import json
 import os
 import re
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -29,19 +28,19 @@ import numpy as np
 import torch
 
 from . import dist as jdist
+from . import group_table
+from .group_table import ALL, MAX_GROUPS, arrow as _arrow, fmt as _fmt, rank as _rank
 
 LAYOUT_VERSION = 1            # include/jrr.h: JRR_EVAL_ACC_LAYOUT_VERSION and the offsets below
-ROW, TRAILER = 338, 2
+ROW, TRAILER = 338, group_table.TRAILER
 COUNT, BAD, SUM, SUM_PA, HIST, HIST_PA, BINS = 0, 1, 2, 19, 36, 187, 151
 NJ = 17
 FIXED = float(1 << 24)        # the sums are in units of 2^-24 m
-MAX_GROUPS = 1024
 PCK_THRESHOLDS_MM = (50, 100, 150)
 AUC_THRESHOLDS_MM = tuple(range(0, 151, 5))     # 31 thresholds
 JOINT_NAMES = ('Pelvis', 'R_Hip', 'R_Knee', 'R_Ankle', 'L_Hip', 'L_Knee', 'L_Ankle', 'Torso', 'Neck', 'Nose', 'Head',
                'L_Shoulder', 'L_Elbow', 'L_Wrist', 'R_Shoulder', 'R_Elbow', 'R_Wrist')
 GROUP_KINDS = ('action', 'subject', 'none')
-ALL = 'all'
 
 
 # ---- groups ----------------------------------------------------------------------------------------------------------------
@@ -83,8 +82,7 @@ def assign_groups(paths: Optional[Sequence[str]], kind: str, n: Optional[int] = 
 class EvalReport:
     def __init__(self, group_names: Sequence[str], device):
         self.names = [str(g) for g in group_names]
-        if not 1 <= len(self.names) <= MAX_GROUPS:
-            raise ValueError(f'{len(self.names)} groups: 1 .. {MAX_GROUPS}')
+        group_table.check_groups(len(self.names))
         self.device = torch.device(device)
         self.acc = torch.zeros(len(self.names) * ROW + TRAILER, dtype=torch.int64, device=self.device)
 
@@ -103,13 +101,7 @@ class EvalReport:
 
     def finish(self, reduce: bool = True) -> dict:
         """the ONE all-reduce (reduce=False: this process evaluated everything alone), the one read-back, the derivation"""
-        import torch.distributed as dist
-        table = self.acc
-        if reduce and dist.is_available() and dist.is_initialized():
-            if table.is_cuda and dist.get_backend() == 'gloo':
-                table = table.cpu()
-            dist.all_reduce(table, op=dist.ReduceOp.SUM)
-        return derive(table.cpu().numpy(), self.names)
+        return derive(group_table.all_reduce(self.acc, reduce).cpu().numpy(), self.names)
 
 
 def _stats(row: np.ndarray) -> dict:
@@ -134,15 +126,7 @@ def derive(table: np.ndarray, names: Sequence[str]) -> dict:
     """the numbers of one regressor's report from the int64 table (n_groups * 338 + 2 words): per group and for `all`
     n, n_bad, MPJPE / PA-MPJPE in mm = sum / 2^24 / (17 n) * 1000 in float64, the 17 per-joint means, PCK@t = (values in bins below t)
     / (17 n), AUC = mean of PCK over t = 0, 5, ..., 150.  Raises when a pose carried a group id >= n_groups."""
-    table = np.asarray(table)
-    G = len(names)
-    if table.dtype != np.int64 or table.shape != (G * ROW + TRAILER,):
-        raise ValueError(f'evaluation table: {G * ROW + TRAILER} int64 expected for {G} groups, got {table.dtype} {table.shape}')
-    ignored, bad_group = int(table[G * ROW]), int(table[G * ROW + 1])
-    if bad_group:
-        raise RuntimeError(f'evaluation table: {bad_group} poses carried a group id outside [0, {G}); they were not scored')
-    rows = table[:G * ROW].reshape(G, ROW)
-    return {'groups': {name: _stats(rows[i]) for i, name in enumerate(names)}, ALL: _stats(rows.sum(0)), 'ignored': ignored}
+    return group_table.derive(table, names, ROW, _stats, 'evaluation table')
 
 
 # ---- the files -------------------------------------------------------------------------------------------------------------
@@ -153,14 +137,6 @@ def sha16(path: Optional[str], fallback: Optional[np.ndarray] = None) -> Optiona
     if fallback is not None:
         return hashlib.sha256(np.ascontiguousarray(fallback).tobytes()).hexdigest()[:16]
     return None
-
-
-def _fmt(x, spec='.2f') -> str:
-    return '-' if x is None else format(x, spec)
-
-
-def _arrow(b, a, spec='.2f') -> str:
-    return f'{_fmt(b, spec)} → {_fmt(a, spec)}'
 
 
 def markdown(doc: dict) -> str:
@@ -199,34 +175,16 @@ def write(directory: str, results: Dict[str, dict], group_names: Sequence[str], 
           initial: Tuple[Optional[str], Optional[str]], retrained: Tuple[Optional[str], Optional[str]]) -> Optional[dict]:
     """DIR/eval.json and DIR/eval.md; rank 0 alone writes (the others return None).  `results`: name ('before', 'after') -> what
     finish() returned; initial / retrained: (path, sha256[:16])."""
-    if _rank() != 0:
-        return None
     doc = {'layout_version': LAYOUT_VERSION, 'source': source, 'group_kind': group_kind, 'groups': list(group_names),
            'joints': list(JOINT_NAMES), 'pck_thresholds_mm': list(PCK_THRESHOLDS_MM), 'auc_thresholds_mm': list(AUC_THRESHOLDS_MM),
            'regressors': results, 'flags': flags,
            'j_regressor_initial': {'path': initial[0], 'sha256_16': initial[1]},
            'j_regressor_retrained': {'path': retrained[0], 'sha256_16': retrained[1]}}
-    os.makedirs(directory, exist_ok=True)
-    with open(os.path.join(directory, 'eval.json'), 'w') as f:
-        json.dump(doc, f, indent=1, sort_keys=True, default=str)
-    with open(os.path.join(directory, 'eval.md'), 'w', encoding='utf-8') as f:
-        f.write(markdown(doc))
-    return doc
+    return group_table.write(directory, 'eval', doc, markdown)
 
 
 def load(directory: str) -> dict:
-    with open(os.path.join(directory, 'eval.json')) as f:
-        doc = json.load(f)
-    if doc.get('layout_version') != LAYOUT_VERSION:
-        raise ValueError(f'{directory}: table layout version {doc.get("layout_version")!r}, this build reads version {LAYOUT_VERSION}')
-    return doc
-
-
-def _rank() -> int:
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank()
-    return jdist.env_rank_world()[0]
+    return group_table.load(directory, 'eval', LAYOUT_VERSION)
 
 
 # ---- --eval_vertices -------------------------------------------------------------------------------------------------------

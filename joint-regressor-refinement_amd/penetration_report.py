@@ -15,7 +15,6 @@ ranks (exact: integers of disjoint shards), makes the only read-back and derives
 """
 from __future__ import annotations
 
-import json
 import math
 import os
 from typing import Optional, Sequence
@@ -23,14 +22,14 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import eval_report, vertex_report
+from . import group_table, vertex_report
+from .group_table import ALL, fmt as _fmt
 
 LAYOUT_VERSION = 1            # include/jrr.h: JRR_PEN_ACC_LAYOUT_VERSION and the offsets below
-ROW, TRAILER, BINS, MAX_PARTS = 55, 2, 16, 32
+ROW, TRAILER, BINS, MAX_PARTS = 55, group_table.TRAILER, 16, 32
 COUNT, BAD, POSES_PEN, POSES_PEN8, SUM_PEN, SUM_THIN, SUM_UNSURE, HIST, PART = 0, 1, 2, 3, 4, 5, 6, 7, 23
 NV = 6890
 WORST = 20
-ALL = eval_report.ALL
 _OWN_FLAGS = ('eval_penetration', 'eval_penetration_offset_mm')
 HIST_LABELS = ['0', '1'] + [f'{1 << (b - 1)}-{(1 << b) - 1}' for b in range(2, BINS - 1)] + [f'>={1 << (BINS - 2)}']
 
@@ -78,8 +77,7 @@ class PenetrationReport:
     def __init__(self, group_names: Sequence[str], device, faces: np.ndarray, n_total: int, offset_mm: float, sign: int,
                  part: Optional[np.ndarray] = None, n_parts: int = 0, n_verts: int = NV):
         self.names = [str(g) for g in group_names]
-        if not 1 <= len(self.names) <= eval_report.MAX_GROUPS:
-            raise ValueError(f'{len(self.names)} groups: 1 .. {eval_report.MAX_GROUPS}')
+        group_table.check_groups(len(self.names))
         if sign not in (1, -1):
             raise ValueError(f'orientation {sign!r}: +1 or -1')
         self.device, self.n_verts, self.n_total = torch.device(device), int(n_verts), int(n_total)
@@ -116,14 +114,7 @@ class PenetrationReport:
 
     def finish(self, reduce: bool = True) -> dict:
         """the sums over the ranks (reduce=False: this process evaluated everything alone), the one read-back, the derivation"""
-        import torch.distributed as dist
-        table, counts = self.both, self.counts
-        if reduce and dist.is_available() and dist.is_initialized():
-            if table.is_cuda and dist.get_backend() == 'gloo':
-                table, counts = table.cpu(), counts.cpu()
-            dist.all_reduce(table, op=dist.ReduceOp.SUM)
-            dist.all_reduce(counts, op=dist.ReduceOp.SUM)
-        host, counts = table.cpu().numpy(), counts.cpu().numpy()
+        host, counts = (group_table.all_reduce(t, reduce).cpu().numpy() for t in (self.both, self.counts))
         if int(self.status.item()) & 1:
             raise RuntimeError('--eval_penetration: a face of the body model names a vertex outside the mesh')
         cut = len(self.names) * ROW + TRAILER
@@ -150,24 +141,17 @@ def derive(table: np.ndarray, per_vertex: np.ndarray, names: Sequence[str], part
     poses and the share of poses with any and with at least 8 penetrating vertices, the mean and the histogram of n_pen, the share of
     thin and of unsure vertices (of n * n_verts), the penetrating vertices per part (part: the labels the table was filled with).
     Raises when a pose carried a group id >= n_groups."""
-    table, per_vertex = np.asarray(table), np.asarray(per_vertex)
-    G = len(names)
-    if table.dtype != np.int64 or table.shape != (G * ROW + TRAILER,):
-        raise ValueError(f'penetration table: {G * ROW + TRAILER} int64 expected for {G} groups, got {table.dtype} {table.shape}')
+    rows, ignored = group_table.split(table, len(names), ROW, 'penetration table')
+    per_vertex = np.asarray(per_vertex)
     if per_vertex.dtype != np.int64 or per_vertex.ndim != 1:
         raise ValueError(f'per-vertex table: (n_verts,) int64 expected, got {per_vertex.dtype} {per_vertex.shape}')
-    ignored, bad_group = int(table[G * ROW]), int(table[G * ROW + 1])
-    if bad_group:
-        raise RuntimeError(f'penetration table: {bad_group} poses carried a group id outside [0, {G}); they were not scored')
     parts = None
     if part is not None:
         p = np.asarray(part)
         sizes = np.bincount(p[(p >= 0) & (p < n_parts)], minlength=n_parts)
         parts = list(zip(vertex_report.part_names(n_parts), (int(s) for s in sizes)))
-    rows = table[:G * ROW].reshape(G, ROW)
-    total = rows.sum(0)
     nv = int(per_vertex.shape[0])
-    return {'groups': {name: _stats(rows[i], parts, nv) for i, name in enumerate(names)}, ALL: _stats(total, parts, nv), 'ignored': ignored,
+    return {**group_table.assemble(rows, ignored, names, lambda row: _stats(row, parts, nv)),
             'parts': None if parts is None else {name: size for name, size in parts}, 'per_vertex': per_vertex.copy()}
 
 
@@ -182,10 +166,6 @@ def worst_poses(counts: np.ndarray, k: int = WORST) -> list:
 # ---- the files -----------------------------------------------------------------------------------------------------------------
 def _pct(x) -> str:
     return '-' if x is None else format(100.0 * x, '.2f')
-
-
-def _fmt(x, spec='.2f') -> str:
-    return '-' if x is None else format(x, spec)
 
 
 def markdown(doc: dict) -> str:
@@ -222,7 +202,7 @@ def markdown(doc: dict) -> str:
 def write(directory: str, result: dict, group_names: Sequence[str], group_kind: str, source: str, offset_mm: float, sign: int) -> Optional[dict]:
     """DIR/penetration.json, DIR/penetration.md, DIR/penetration_per_vertex.npy and DIR/penetration.npz from what finish() returned;
     rank 0 alone writes (the others return None)"""
-    if eval_report._rank() != 0:
+    if group_table.rank() != 0:
         return None
     data = dict(result)
     per_vertex = np.asarray(data.pop('per_vertex'), dtype=np.int64)
@@ -236,19 +216,11 @@ def write(directory: str, result: dict, group_names: Sequence[str], group_kind: 
     os.makedirs(directory, exist_ok=True)
     np.save(os.path.join(directory, 'penetration_per_vertex.npy'), per_vertex)
     np.savez(os.path.join(directory, 'penetration.npz'), n_pen=counts[0], n_thin=counts[1], n_unsure=counts[2])
-    with open(os.path.join(directory, 'penetration.json'), 'w') as f:
-        json.dump(doc, f, indent=1, sort_keys=True, default=str)
-    with open(os.path.join(directory, 'penetration.md'), 'w', encoding='utf-8') as f:
-        f.write(markdown(doc))
-    return doc
+    return group_table.write(directory, 'penetration', doc, markdown)
 
 
 def load(directory: str) -> dict:
-    with open(os.path.join(directory, 'penetration.json')) as f:
-        doc = json.load(f)
-    if doc.get('layout_version') != LAYOUT_VERSION:
-        raise ValueError(f'{directory}: table layout version {doc.get("layout_version")!r}, this build reads version {LAYOUT_VERSION}')
-    return doc
+    return group_table.load(directory, 'penetration', LAYOUT_VERSION)
 
 
 def summary_line(doc: dict) -> str:

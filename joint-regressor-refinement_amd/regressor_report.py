@@ -27,7 +27,6 @@ their bytes.
 """
 from __future__ import annotations
 
-import json
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -35,11 +34,12 @@ import numpy as np
 import torch
 
 from . import bones_report, ci_report, penetration_report
-from . import dist as jdist
-from .eval_report import ALL, JOINT_NAMES, MAX_GROUPS, sha16
+from . import group_table
+from .eval_report import JOINT_NAMES, sha16
+from .group_table import ALL, fmt as _f, rank as _rank
 
 LAYOUT_VERSION = 1            # include/jrr.h: JRR_SHIFT_ACC_LAYOUT_VERSION and the offsets below
-ROW, TRAILER = 1277, 2
+ROW, TRAILER = 1277, group_table.TRAILER
 COUNT, BAD, SUM, MOM, ABS, ABS_REL, HIST, BINS = 0, 1, 2, 53, 155, 172, 189, 64
 NJ = 17
 FIXED = float(1 << 24)        # lengths are in units of 2^-24 m, the moments in units of 2^-32 m^2
@@ -55,8 +55,7 @@ TOP = 5
 class ShiftReport:
     def __init__(self, group_names: Sequence[str], device):
         self.names = [str(g) for g in group_names]
-        if not 1 <= len(self.names) <= MAX_GROUPS:
-            raise ValueError(f'{len(self.names)} groups: 1 .. {MAX_GROUPS}')
+        group_table.check_groups(len(self.names))
         self.device = torch.device(device)
         self.acc = torch.zeros(len(self.names) * ROW + TRAILER, dtype=torch.int64, device=self.device)
 
@@ -71,13 +70,7 @@ class ShiftReport:
 
     def finish(self, reduce: bool = True) -> dict:
         """the ONE all-reduce (reduce=False: this process saw everything alone), the one read-back, the derivation"""
-        import torch.distributed as dist
-        table = self.acc
-        if reduce and dist.is_available() and dist.is_initialized():
-            if table.is_cuda and dist.get_backend() == 'gloo':
-                table = table.cpu()
-            dist.all_reduce(table, op=dist.ReduceOp.SUM)
-        return derive(table.cpu().numpy(), self.names)
+        return derive(group_table.all_reduce(self.acc, reduce).cpu().numpy(), self.names)
 
 
 def _quantile_mm(hist: np.ndarray, n: int, p: float) -> float:
@@ -115,15 +108,7 @@ def derive(table: np.ndarray, names: Sequence[str]) -> dict:
     second moments (a moment word drops up to 2^-32 m^2 per pose: a spread below ~0.015 mm may read as zero, one of a millimetre reads
     up to 1e-4 mm low), the mean |d|, the mean pelvis-relative |d|, the median and the 95th percentile of |d| from the 2-mm histogram (bin
     upper edges), n and n_bad.  Raises when a pose carried a group id >= n_groups."""
-    table = np.asarray(table)
-    G = len(names)
-    if table.dtype != np.int64 or table.shape != (G * ROW + TRAILER,):
-        raise ValueError(f'regressor-shift table: {G * ROW + TRAILER} int64 expected for {G} groups, got {table.dtype} {table.shape}')
-    ignored, bad_group = int(table[G * ROW]), int(table[G * ROW + 1])
-    if bad_group:
-        raise RuntimeError(f'regressor-shift table: {bad_group} poses carried a group id outside [0, {G}); they were not counted')
-    rows = table[:G * ROW].reshape(G, ROW)
-    return {'groups': {name: _stats(rows[i]) for i, name in enumerate(names)}, ALL: _stats(rows.sum(0)), 'ignored': ignored}
+    return group_table.derive(table, names, ROW, _stats, 'regressor-shift table', verb='counted')
 
 
 # ---- the depth below the skin ------------------------------------------------------------------------------------------------
@@ -139,8 +124,7 @@ class DepthReport:
 
     def __init__(self, group_names: Sequence[str], device, faces):
         self.names = [str(g) for g in group_names]
-        if not 1 <= len(self.names) <= MAX_GROUPS:
-            raise ValueError(f'{len(self.names)} groups: 1 .. {MAX_GROUPS}')
+        group_table.check_groups(len(self.names))
         faces = np.asarray(faces)
         if faces.ndim != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
             raise ValueError(f'depth section: faces (n_faces,3) expected, got {faces.shape}')
@@ -161,13 +145,7 @@ class DepthReport:
 
     def finish(self, reduce: bool = True) -> dict:
         """the ONE all-reduce (the status word rides behind the table), the one read-back, the derivation"""
-        import torch.distributed as dist
-        table = torch.cat([self.acc, self.status.to(torch.int64)])
-        if reduce and dist.is_available() and dist.is_initialized():
-            if table.is_cuda and dist.get_backend() == 'gloo':
-                table = table.cpu()
-            dist.all_reduce(table, op=dist.ReduceOp.SUM)
-        table = table.cpu().numpy()
+        table = group_table.all_reduce(torch.cat([self.acc, self.status.to(torch.int64)]), reduce).cpu().numpy()
         if int(table[-1]) != 0:
             raise RuntimeError('depth section: a face of the body model names a vertex outside the meshes; it was skipped (status bit 0)')
         return derive_depth(table[:-1], self.names)
@@ -203,18 +181,9 @@ def derive_depth(table: np.ndarray, names: Sequence[str], n_sets: int = 3) -> di
     17 s .. 17 s + 16) and joint: the mean signed depth in mm (positive: under the skin) = sum / 2^24 / n * 1000, the share of poses in
     which the joint is outside, the share in which the winding number is no integer within 0.1, the median and the 5th percentile of the
     depth from the 4-mm histogram (bin upper edges), n and n_bad.  Raises when a pose carried a group id >= n_groups."""
-    table = np.asarray(table)
-    G = len(names)
-    if table.dtype != np.int64 or table.shape != (G * D_ROW + TRAILER,):
-        raise ValueError(f'depth table: {G * D_ROW + TRAILER} int64 expected for {G} groups, got {table.dtype} {table.shape}')
     if not 1 <= n_sets <= D_COLS // NJ:
         raise ValueError(f'depth table: {n_sets} sets of {NJ} columns: 1 .. {D_COLS // NJ}')
-    ignored, bad_group = int(table[G * D_ROW]), int(table[G * D_ROW + 1])
-    if bad_group:
-        raise RuntimeError(f'depth table: {bad_group} poses carried a group id outside [0, {G}); they were not counted')
-    rows = table[:G * D_ROW].reshape(G, D_ROW)
-    return {'groups': {name: _depth_stats(rows[i], n_sets) for i, name in enumerate(names)}, ALL: _depth_stats(rows.sum(0), n_sets),
-            'ignored': ignored}
+    return group_table.derive(table, names, D_ROW, lambda row: _depth_stats(row, n_sets), 'depth table', verb='counted')
 
 
 def template_depth(model_np: Dict[str, np.ndarray], J_a, J_b, mask, device) -> dict:
@@ -286,26 +255,15 @@ def depth_markdown(doc: dict) -> str:
 
 def write_depth(directory: str, data: dict, template: dict, group_names: Sequence[str], source: str, body_model: Optional[str]) -> Optional[dict]:
     """DIR/depth.json and DIR/depth.md; rank 0 alone writes (the others return None)"""
-    if _rank() != 0:
-        return None
-    doc = {'layout_version': DEPTH_LAYOUT_VERSION, 'source': source, 'groups': list(group_names), 'joint_names': list(JOINT_NAMES),
+    doc = lambda: {'layout_version': DEPTH_LAYOUT_VERSION, 'source': source, 'groups': list(group_names), 'joint_names': list(JOINT_NAMES),
            'sets': list(DEPTH_SETS), 'bin_mm': D_BIN_MM, 'bin_low_mm': D_LOW_MM, 'orientation': template['orientation'],
            'sign': 'depth > 0: under the skin; inside <=> |winding number| > 0.5', 'data': data, 'template': template,
            'newly_outside': newly_outside(data), 'body_model': body_model}
-    os.makedirs(directory, exist_ok=True)
-    with open(os.path.join(directory, 'depth.json'), 'w') as f:
-        json.dump(doc, f, indent=1, sort_keys=True, default=str)
-    with open(os.path.join(directory, 'depth.md'), 'w', encoding='utf-8') as f:
-        f.write(depth_markdown(doc))
-    return doc
+    return group_table.write(directory, 'depth', doc, depth_markdown)
 
 
 def load_depth(directory: str) -> dict:
-    with open(os.path.join(directory, 'depth.json')) as f:
-        doc = json.load(f)
-    if doc.get('layout_version') != DEPTH_LAYOUT_VERSION:
-        raise ValueError(f'{directory}: depth table layout version {doc.get("layout_version")!r}, this build reads version {DEPTH_LAYOUT_VERSION}')
-    return doc
+    return group_table.load(directory, 'depth', DEPTH_LAYOUT_VERSION, 'depth table')
 
 
 # ---- the two regressors, without data ----------------------------------------------------------------------------------------
@@ -472,10 +430,6 @@ class PoseKeeper:
 
 
 # ---- the files ---------------------------------------------------------------------------------------------------------------
-def _f(x, spec='.2f') -> str:
-    return '-' if x is None else format(x, spec)
-
-
 def _xyz(v) -> str:
     return '-' if v is None else ' '.join(format(c, '+.2f') for c in v)
 
@@ -514,35 +468,17 @@ def write(directory: str, data: dict, joints: List[dict], group_names: Sequence[
           body_model: Optional[str] = None) -> Optional[dict]:
     """DIR/regressor.json and DIR/regressor.md; rank 0 alone writes (the others return None).  data: what finish() returned; joints:
     compare_regressors(); initial / retrained: (path, sha256[:16]); pictures: what was written, or why not"""
-    if _rank() != 0:
-        return None
-    doc = {'layout_version': LAYOUT_VERSION, 'source': source, 'groups': list(group_names), 'joint_names': list(JOINT_NAMES),
+    doc = lambda: {'layout_version': LAYOUT_VERSION, 'source': source, 'groups': list(group_names), 'joint_names': list(JOINT_NAMES),
            'frame': 'x = L_Hip - R_Hip, y = up (Neck - Pelvis made orthogonal to x), z = x cross y: forward; from the joints of A',
            'bin_mm': BIN_MM, 'joints': joints, 'data': data, 'flags': flags, 'pictures': pictures, 'body_model': body_model,
            'colours': {'a': list(GREEN), 'b': list(BLUE), 'ground_truth': list(RED), 'joint_a': list(PALE_GREEN), 'joint_b': list(PALE_BLUE)},
            'j_regressor_initial': {'path': initial[0], 'sha256_16': initial[1]},
            'j_regressor_retrained': {'path': retrained[0], 'sha256_16': retrained[1]}}
-    os.makedirs(directory, exist_ok=True)
-    with open(os.path.join(directory, 'regressor.json'), 'w') as f:
-        json.dump(doc, f, indent=1, sort_keys=True, default=str)
-    with open(os.path.join(directory, 'regressor.md'), 'w', encoding='utf-8') as f:
-        f.write(markdown(doc))
-    return doc
+    return group_table.write(directory, 'regressor', doc, markdown)
 
 
 def load(directory: str) -> dict:
-    with open(os.path.join(directory, 'regressor.json')) as f:
-        doc = json.load(f)
-    if doc.get('layout_version') != LAYOUT_VERSION:
-        raise ValueError(f'{directory}: table layout version {doc.get("layout_version")!r}, this build reads version {LAYOUT_VERSION}')
-    return doc
-
-
-def _rank() -> int:
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank()
-    return jdist.env_rank_world()[0]
+    return group_table.load(directory, 'regressor', LAYOUT_VERSION)
 
 
 _OWN_FLAGS = ('regressor_report_depth',)

@@ -14,21 +14,20 @@ vertices carry part labels (`--eval_pve_parts`: the argmax of the body model's s
 """
 from __future__ import annotations
 
-import json
 import os
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import accel_report, eval_report
+from . import accel_report, group_table
+from .group_table import ALL, fmt as _fmt
 
 LAYOUT_VERSION = 1            # include/jrr.h: JRR_PVE_ACC_LAYOUT_VERSION and the offsets below
-ROW, TRAILER, MAX_PARTS = 370, 2, 32
+ROW, TRAILER, MAX_PARTS = 370, group_table.TRAILER, 32
 COUNT, BAD, SUM, SUM_PA, HIST, HIST_PA, PART, PART_PA, BINS = 0, 1, 2, 3, 4, 155, 306, 338, 151
 NV = 6890
 FIXED = float(1 << 24)        # the sums are in units of 2^-24 m
-ALL = eval_report.ALL
 GT_NAME = 'gt_vertices.npy'
 PART_NAMES = ('Pelvis', 'L_Hip', 'R_Hip', 'Spine1', 'L_Knee', 'R_Knee', 'Spine2', 'L_Ankle', 'R_Ankle', 'Spine3', 'L_Foot', 'R_Foot', 'Neck',
               'L_Collar', 'R_Collar', 'Head', 'L_Shoulder', 'R_Shoulder', 'L_Elbow', 'R_Elbow', 'L_Wrist', 'R_Wrist', 'L_Hand', 'R_Hand')
@@ -78,8 +77,7 @@ def part_names(n_parts: int) -> list:
 class VertexReport:
     def __init__(self, group_names: Sequence[str], device, n_verts: int = NV, part: Optional[np.ndarray] = None, n_parts: int = 0):
         self.names = [str(g) for g in group_names]
-        if not 1 <= len(self.names) <= eval_report.MAX_GROUPS:
-            raise ValueError(f'{len(self.names)} groups: 1 .. {eval_report.MAX_GROUPS}')
+        group_table.check_groups(len(self.names))
         self.device, self.n_verts = torch.device(device), int(n_verts)
         self.n_parts = int(n_parts) if part is not None else 0
         if part is not None:
@@ -103,13 +101,7 @@ class VertexReport:
 
     def finish(self, reduce: bool = True) -> dict:
         """the ONE all-reduce (reduce=False: this process evaluated everything alone), the one read-back, the derivation"""
-        import torch.distributed as dist
-        table = self.both
-        if reduce and dist.is_available() and dist.is_initialized():
-            if table.is_cuda and dist.get_backend() == 'gloo':
-                table = table.cpu()
-            dist.all_reduce(table, op=dist.ReduceOp.SUM)
-        host = table.cpu().numpy()
+        host = group_table.all_reduce(self.both, reduce).cpu().numpy()
         cut = len(self.names) * ROW + TRAILER
         return derive(host[:cut], host[cut:].reshape(2, self.n_verts), self.names, self.part_np, self.n_parts)
 
@@ -136,32 +128,21 @@ def derive(table: np.ndarray, table_v: np.ndarray, names: Sequence[str], part: O
     PA-PVE in mm = sum / 2^24 / n * 1000 in float64, the median and 90th percentile of the per-pose values from the histogram, the
     per-part means (part: the labels the table was filled with); `per_vertex_mm` (2,n_verts) float32 = table_v / 2^24 / n(all) * 1000
     (NaN without a counted pose).  Raises when a pose carried a group id >= n_groups."""
-    table, table_v = np.asarray(table), np.asarray(table_v)
-    G = len(names)
-    if table.dtype != np.int64 or table.shape != (G * ROW + TRAILER,):
-        raise ValueError(f'vertex error table: {G * ROW + TRAILER} int64 expected for {G} groups, got {table.dtype} {table.shape}')
+    rows, ignored = group_table.split(table, len(names), ROW, 'vertex error table')
+    table_v = np.asarray(table_v)
     if table_v.dtype != np.int64 or table_v.ndim != 2 or table_v.shape[0] != 2:
         raise ValueError(f'per-vertex table: (2,n_verts) int64 expected, got {table_v.dtype} {table_v.shape}')
-    ignored, bad_group = int(table[G * ROW]), int(table[G * ROW + 1])
-    if bad_group:
-        raise RuntimeError(f'vertex error table: {bad_group} poses carried a group id outside [0, {G}); they were not scored')
     parts = None
     if part is not None:
         sizes = np.bincount(np.asarray(part)[(np.asarray(part) >= 0) & (np.asarray(part) < n_parts)], minlength=n_parts)
         parts = list(zip(part_names(n_parts), (int(s) for s in sizes)))
-    rows = table[:G * ROW].reshape(G, ROW)
-    total = rows.sum(0)
-    n_all = int(total[COUNT])
+    n_all = int(rows[:, COUNT].sum())
     per_vertex = (table_v.astype(np.float64) / FIXED / n_all * 1000.0).astype(np.float32) if n_all else np.full(table_v.shape, np.nan, dtype=np.float32)
-    return {'groups': {name: _stats(rows[i], parts) for i, name in enumerate(names)}, ALL: _stats(total, parts), 'ignored': ignored,
+    return {**group_table.assemble(rows, ignored, names, lambda row: _stats(row, parts)),
             'parts': None if parts is None else {name: size for name, size in parts}, 'per_vertex_mm': per_vertex}
 
 
 # ---- the files -----------------------------------------------------------------------------------------------------------------
-def _fmt(x, spec='.2f') -> str:
-    return '-' if x is None else format(x, spec)
-
-
 def markdown(doc: dict) -> str:
     lines = [f'# Per-vertex error ({doc["source"]}, groups by {doc["group_kind"]})', '',
              f'Errors in mm over the {doc["n_verts"]} vertices, both meshes centred at joint 0 of `{doc["j_regressor_initial"]["path"]}` '
@@ -191,7 +172,7 @@ def markdown(doc: dict) -> str:
 def write(directory: str, result: dict, group_names: Sequence[str], group_kind: str, source: str, initial) -> Optional[dict]:
     """DIR/pve.json, DIR/pve.md and DIR/pve_per_vertex.npy from what finish() returned; rank 0 alone writes (the others return None).
     initial: (path, sha256[:16]) of the regressor whose joint 0 centred the meshes."""
-    if eval_report._rank() != 0:
+    if group_table.rank() != 0:
         return None
     data = dict(result)
     per_vertex = np.asarray(data.pop('per_vertex_mm'), dtype=np.float32)
@@ -202,19 +183,11 @@ def write(directory: str, result: dict, group_names: Sequence[str], group_kind: 
                           'argmax': [int(v) for v in per_vertex.argmax(1)] if finite else [None, None]}}
     os.makedirs(directory, exist_ok=True)
     np.save(os.path.join(directory, 'pve_per_vertex.npy'), per_vertex)
-    with open(os.path.join(directory, 'pve.json'), 'w') as f:
-        json.dump(doc, f, indent=1, sort_keys=True, default=str)
-    with open(os.path.join(directory, 'pve.md'), 'w', encoding='utf-8') as f:
-        f.write(markdown(doc))
-    return doc
+    return group_table.write(directory, 'pve', doc, markdown)
 
 
 def load(directory: str) -> dict:
-    with open(os.path.join(directory, 'pve.json')) as f:
-        doc = json.load(f)
-    if doc.get('layout_version') != LAYOUT_VERSION:
-        raise ValueError(f'{directory}: table layout version {doc.get("layout_version")!r}, this build reads version {LAYOUT_VERSION}')
-    return doc
+    return group_table.load(directory, 'pve', LAYOUT_VERSION)
 
 
 def summary_line(doc: dict) -> str:
