@@ -729,6 +729,40 @@ int jrr_regress_joints(const float* verts_dev, int batch, const void* workspace_
 int jrr_eval_accumulate(const float* err_j_dev, const float* err_pa_j_dev, const int32_t* group_dev, int batch, int n_groups,
                         int64_t* acc_dev, void* stream);
 
+/* The evaluation report under a published protocol (`--eval_protocol`; no reference counterpart in running code: H36M_TO_J14 of
+ * scripts/constants.py and the commented METRO block name the 14 joints): which joints are scored, where both skeletons are centred,
+ * in which unit the target comes.  One launch.  M = the joints whose bit is set in joint_mask, ascending, n = |M|.  Per pose, fp32:
+ *   target   Q_i = target_i / 1000.f under JRR_EVAL_TARGET_MM (exactly as jrr_evaluate_joints), target_i itself under JRR_EVAL_TARGET_M
+ *   root     JRR_EVAL_ROOT_JOINT0: rP = P_0, rQ = Q_0; JRR_EVAL_ROOT_HIPS: rP_c = (P_1c + P_4c) * 0.5f, rQ likewise.  The root joints are
+ *            used whether or not they are in M.
+ *   plain    for i in M: P_i -= rP, Q_i -= rQ, err_j[i] = |P_i - Q_i|
+ *   aligned  the Procrustes fit of jrr_evaluate_joints over M ALONE: means divided by (float)n, K and var1 summed over M in ascending
+ *            order, the same one-sided Jacobi (six sweeps), static sort and rank-2 / rank-1 / rank-0 rules;
+ *            err_pa_j[i] = |s R P_i + t - Q_i| for i in M.  A single joint (var1 = 0) gives NaN there, as the reference does.
+ *   others   a joint outside M gets +0.0f in both outputs.  A joint that is neither in M nor a root joint is not read: a NaN there
+ *            changes no output bit.
+ * err_j_dev / err_pa_j_dev (batch,17) metres, each nullable, 16-byte aligned.  With zeros in the excluded columns a sum over the 17
+ * columns is a sum over the protocol's joints: jrr_paired_units takes these arrays UNCHANGED (its four sums are then sums over M, and a
+ * zero passes its e < 1.0e3f test).  They are NOT input for jrr_eval_accumulate: its histograms would count the zeros of the excluded
+ * joints in bin 0 and its COUNT-based divisor is 17.  Use acc_dev here instead:
+ * acc_dev (nullable) is the table of jrr_eval_accumulate (JRR_EVAL_ACC_*, n_groups rows + the 2-word trailer), added to in the same
+ * launch with that function's expressions: group_dev (batch) int32 or NULL (every pose in group 0); group < 0 counts in trailer word 0
+ * only, group >= n_groups in trailer word 1 only; a pose with a value OF A JOINT IN M failing e < 1.0e3f adds BAD += 1 only; otherwise
+ * COUNT += 1 and, for i in M only, SUM[i], SUM_PA[i] and one bin each of HIST and HIST_PA.  The words of excluded joints stay 0, so the
+ * means are sum / (n COUNT) and PCK = (bins below t) / (n COUNT).  Integer atomics only: the table is a function of the multiset of
+ * (pose, group) pairs.  At JRR_EVAL_MASK_ALL, JRR_EVAL_ROOT_JOINT0, JRR_EVAL_TARGET_MM the table equals what jrr_eval_accumulate makes of
+ * the two arrays written here.  One pose per thread, no value crosses lanes: a pose's result does not depend on batch or on its place.
+ * JRR_ERR_ARG with a message, before any launch: a NULL pred or target; all three outputs NULL; joint_mask == 0 or a bit at or above
+ * 17; an unknown root or unit; batch < 0; n_groups outside 1 .. JRR_EVAL_ACC_MAX_GROUPS with acc_dev given; a misaligned array.
+ * batch == 0 returns JRR_OK without a launch.                                                                                       */
+enum { JRR_EVAL_ROOT_JOINT0 = 0, JRR_EVAL_ROOT_HIPS = 1 };      /* hips: midpoint of joints 1 and 4 */
+enum { JRR_EVAL_TARGET_MM = 0, JRR_EVAL_TARGET_M = 1 };
+enum { JRR_EVAL_MASK_ALL = 0x1FFFF, JRR_EVAL_MASK_LSP14 = 0x1FD7E };      /* LSP14: the 17 minus Pelvis (0), Torso (7) and Nose (9) */
+int jrr_evaluate_protocol(const float* pred_dev /* (batch,17,3) m */, const float* target_dev /* (batch,17,3) */, int target_unit,
+                          uint32_t joint_mask, int root, const int32_t* group_dev /* (batch) or NULL: group 0 */, int batch, int n_groups,
+                          float* err_j_dev, float* err_pa_j_dev /* (batch,17) m, each nullable */, int64_t* acc_dev /* nullable */,
+                          void* stream);
+
 /* The acceleration error along each video sequence (`--eval_accel`; the HMMR / VIBE convention, no reference counterpart in code:
  * this text is the specification).  pred_dev (n_rows,17,3) fp32 metres and gt_mm_dev (n_rows,17,3) fp32 millimetres are tables whose
  * row is the dataset index; both are only read.  order_dev (m) int32 lists table rows in time order and run_dev (m) int32 gives each

@@ -78,6 +78,7 @@ SIGNATURES = {
     'jrr_regress_joints_prepare': (c_int, [_P, c_int, _P, _P, c_size_t, _P]),
     'jrr_regress_joints': (c_int, [_P, c_int, _P, c_int, _P, _P]),
     'jrr_eval_accumulate': (c_int, [_P, _P, _P, c_int, c_int, _P, _P]),
+    'jrr_evaluate_protocol': (c_int, [_P, _P, c_int, ctypes.c_uint32, c_int, _P, c_int, c_int, _P, _P, _P, _P]),
     'jrr_accel_error': (c_int, [_P, _P, ctypes.c_int64, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     'jrr_vertex_error': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P]),
     'jrr_paired_units': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),

@@ -134,6 +134,17 @@ def build_parser() -> argparse.ArgumentParser:
                              'scripts/test.py:141-301 does with the vertices of other models; no SMPL model file is read.  The regressors '
                              'are multiplied by find_j_reg_mask of the initial one as at scripts/test.py:108 (the convention of '
                              'test_pose_refiner_model; :206-212 applies no mask -- the reference\'s mask is all ones, so the two agree)')
+    parser.add_argument('--eval_protocol', type=str, default='h36m17', choices=['h36m17', 'lsp14', 'lsp14_hips'],
+                        help='the protocol of eval.json / eval.md and ci.json / ci.md (eval_protocol.py): h36m17 -- all 17 joints centred on '
+                             'joint 0, the reference\'s evaluate; lsp14 -- the 14 LSP joints (the 17 minus Pelvis, Torso and Nose) centred on '
+                             'joint 0, Procrustes alignment on the 14 alone: SPIN, METRO; lsp14_hips -- the same 14 centred on the midpoint of '
+                             'the hips (joints 1 and 4): VIBE and its descendants.  The four printed means of scripts/test.py:125-138 stay '
+                             'the 17-joint evaluate; --eval_accel, --eval_bones and --regressor_report run on the 17 joints as before')
+    parser.add_argument('--eval_gt_joints', type=str, default='file', choices=['file', 'regressed'],
+                        help='where the ground-truth joints come from: file -- gt_j3d.npy / the dataset; regressed -- with --eval_vertices DIR: '
+                             'each regressor applied to DIR/gt_vertices.npy in metres (3DPW-style data: the initial regressor\'s predictions '
+                             'are scored against the initial regressor\'s ground-truth joints, the retrained one\'s against its own); '
+                             'gt_j3d.npy is then neither needed nor read; not with --eval_accel, --eval_bones or --regressor_report')
     parser.add_argument('--eval_accel', action='store_true',
                         help='with --eval_report DIR (the evaluation, --eval_vertices): also write DIR/accel.json and DIR/accel.md, the '
                              'acceleration error of both regressors\' joints along each video sequence -- per run of consecutive frames of '

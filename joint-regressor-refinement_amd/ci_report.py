@@ -7,7 +7,8 @@ on the same resample, and reports percentile intervals of before, after and afte
 replicates as the standard error, and the share of replicates in which the retrained regressor was not better.
 
 `PairedBootstrap` owns one int64 device buffer: the unit table (n_units,5) and the wins table (n_groups * 8 + 3 words) of
-include/jrr.h (JRR_BOOT_*).  `add()` is jrr_evaluate_joints twice and jrr_paired_units once, and reads nothing back.  `finish()`: ONE
+include/jrr.h (JRR_BOOT_*).  `add()` is jrr_evaluate_joints twice (under a non-default `--eval_protocol`: jrr_evaluate_protocol twice,
+whose excluded columns hold zeros) and jrr_paired_units once, and reads nothing back.  `finish()`: ONE
 int64 sum all-reduce of the buffer under data parallelism (exact: the shards are disjoint), the read-back, the checks, the units with
 a counted pose ordered by (group, unit id), the segments (0: all units; 1 + g: the units of group g -- a group's interval resamples
 that group's own units), the overflow rule in Python integers, the replicates sharded over the ranks with dist.shard_bounds, ONE
@@ -28,6 +29,7 @@ import numpy as np
 import torch
 
 from . import dist as jdist
+from . import eval_protocol
 from . import group_table
 from .group_table import ALL, T_BAD_GROUP, T_IGNORED, fmt as _fmt
 
@@ -107,10 +109,13 @@ def unit_ids(kind: str, n_rows: int, paths: Optional[Sequence[str]] = None) -> T
 
 # ---- the tables ----------------------------------------------------------------------------------------------------------------
 class PairedBootstrap:
-    def __init__(self, group_names: Sequence[str], unit_of_row: np.ndarray, n_units: int, device, group_of_row: Optional[np.ndarray] = None):
+    def __init__(self, group_names: Sequence[str], unit_of_row: np.ndarray, n_units: int, device, group_of_row: Optional[np.ndarray] = None,
+                 protocol: Optional[eval_protocol.Protocol] = None):
         """unit_of_row (n_rows,) int32: the unit of every dataset index (unit_ids); group_of_row (n_rows,) int32 or None (the single
-        group): the group of every dataset index, as the evaluation report assigns it"""
+        group): the group of every dataset index, as the evaluation report assigns it; protocol None or `h36m17`: the reference's
+        evaluate (all 17 joints, centred on joint 0)"""
         self.names = [str(g) for g in group_names]
+        self.protocol = eval_protocol.H36M17 if protocol is None else protocol
         G = len(self.names)
         group_table.check_groups(G)
         self.unit_of_row = np.asarray(unit_of_row).astype(np.int32).reshape(-1)
@@ -125,9 +130,13 @@ class PairedBootstrap:
         self.units = self.flat[:self.n_units * UNIT_ROW].view(self.n_units, UNIT_ROW)
         self.wins = self.flat[self.n_units * UNIT_ROW:]
 
-    def add(self, joints_before: torch.Tensor, joints_after: torch.Tensor, gt_mm: torch.Tensor, group_ids: Optional[torch.Tensor], index) -> None:
-        """joints (B,17,3) m of both regressors on the same poses, gt (B,17,3) mm, group_ids (B,) int32 on the device (None: group 0;
-        < 0 = do not score), index (B,): the poses' dataset indices, a host array or CPU tensor.  Three launches, nothing read back."""
+    def add(self, joints_before: torch.Tensor, joints_after: torch.Tensor, gt_mm, group_ids: Optional[torch.Tensor], index,
+            target_unit: int = eval_protocol.TARGET_MM) -> None:
+        """joints (B,17,3) m of both regressors on the same poses; gt (B,17,3) mm (target_unit TARGET_M: metres), one tensor for both
+        regressors or a pair (before, after) -- ground-truth joints regressed from meshes differ between the two --; group_ids (B,) int32
+        on the device (None: group 0; < 0 = do not score), index (B,): the poses' dataset indices, a host array or CPU tensor.  Three
+        launches (the default protocol with a millimetre target: jrr_evaluate_joints twice; any other: jrr_evaluate_protocol twice,
+        without a table; then jrr_paired_units, which sums the 17 columns -- the excluded ones hold zeros), nothing read back."""
         from . import engine as _engine
         idx = np.asarray(index.cpu() if torch.is_tensor(index) else index).astype(np.int64).reshape(-1)
         B = int(joints_before.shape[0])
@@ -141,9 +150,13 @@ class PairedBootstrap:
         if group_ids.device != dev or group_ids.dtype != torch.int32:
             raise ValueError(f'PairedBootstrap.add: group_ids must be an int32 tensor on {dev}, got {group_ids.dtype} on {group_ids.device}')
         unit = torch.from_numpy(self.unit_of_row[idx]).to(dev, non_blocking=True)
-        gt = gt_mm.detach().float()
-        eb, eb_pa = _engine.evaluate_joints(joints_before.detach().float(), gt)
-        ea, ea_pa = _engine.evaluate_joints(joints_after.detach().float(), gt)
+        gt_b, gt_a = (t.detach().float() for t in (gt_mm if isinstance(gt_mm, (tuple, list)) else (gt_mm, gt_mm)))
+        if self.protocol.is_default and target_unit == eval_protocol.TARGET_MM:
+            eb, eb_pa = _engine.evaluate_joints(joints_before.detach().float(), gt_b)
+            ea, ea_pa = _engine.evaluate_joints(joints_after.detach().float(), gt_a)
+        else:
+            eb, eb_pa = _engine.evaluate_protocol(joints_before.detach().float(), gt_b, self.protocol.joint_mask, self.protocol.root, target_unit)
+            ea, ea_pa = _engine.evaluate_protocol(joints_after.detach().float(), gt_a, self.protocol.joint_mask, self.protocol.root, target_unit)
         _engine.paired_units(eb, eb_pa, ea, ea_pa, group_ids, unit, len(self.names), self.units, self.wins)
 
     def finish(self, reps: int, seed: int, level: float, unit_kind: str, reduce: bool = True) -> dict:
@@ -167,7 +180,8 @@ class PairedBootstrap:
             if hi > lo:
                 full[:, lo:hi] = _engine.bootstrap_sums(table, segments, seed, lo, hi - lo, max_word=int(np.abs(units[kept]).max()))
             sums = group_table.all_reduce(full, reduce).cpu().numpy()                  # the second integer collective
-        return derive(units[kept], group_of_unit, segments, sums, wins, self.names, level, seed=int(seed), unit_kind=unit_kind)
+        return derive(units[kept], group_of_unit, segments, sums, wins, self.names, level, seed=int(seed), unit_kind=unit_kind,
+                      n_joints=self.protocol.n_joints)
 
 
 def plan(units: np.ndarray, wins: np.ndarray, n_groups: int, unit_of_row: np.ndarray, group_of_row: np.ndarray):
@@ -208,8 +222,8 @@ def check_overflow(units: np.ndarray, segments: np.ndarray) -> None:
 
 
 # ---- the derivation ------------------------------------------------------------------------------------------------------------
-def _mean_mm(total, count):
-    return total / FIXED / (NJ * count) * 1000.0
+def _mean_mm(total, count, n_joints: int = NJ):
+    return total / FIXED / (n_joints * count) * 1000.0
 
 
 def _interval(point: float, reps: np.ndarray, level: float) -> dict:
@@ -217,8 +231,9 @@ def _interval(point: float, reps: np.ndarray, level: float) -> dict:
     return {'mean_mm': float(point), 'lo_mm': float(lo), 'hi_mm': float(hi), 'se_mm': float(np.std(reps))}
 
 
-def _stats(point: np.ndarray, reps: np.ndarray, n_units: int, wrow: np.ndarray, level: float) -> dict:
-    """point (5,) int64: the unresampled sums of the segment; reps (R,5) int64: its replicates; wrow (8,) int64"""
+def _stats(point: np.ndarray, reps: np.ndarray, n_units: int, wrow: np.ndarray, level: float, n_joints: int = NJ) -> dict:
+    """point (5,) int64: the unresampled sums of the segment; reps (R,5) int64: its replicates; wrow (8,) int64; n_joints: the joints
+    the sums run over (the protocol's)"""
     n = int(point[UNIT_COUNT])
     out = {'n_units': int(n_units), 'n_poses': n, 'n_bad': int(wrow[W_BAD]), 'raw_sums': [int(x) for x in point],
            'wins': {'mpjpe': {'better': int(wrow[W_BETTER]), 'worse': int(wrow[W_WORSE]), 'tie': int(wrow[W_TIE])},
@@ -228,8 +243,8 @@ def _stats(point: np.ndarray, reps: np.ndarray, n_units: int, wrow: np.ndarray, 
         return out
     counts = reps[:, UNIT_COUNT].astype(np.float64)
     for key, cb, ca in METRICS:
-        pb, pa = _mean_mm(np.float64(point[cb]), np.float64(n)), _mean_mm(np.float64(point[ca]), np.float64(n))
-        rb, ra = _mean_mm(reps[:, cb].astype(np.float64), counts), _mean_mm(reps[:, ca].astype(np.float64), counts)
+        pb, pa = _mean_mm(np.float64(point[cb]), np.float64(n), n_joints), _mean_mm(np.float64(point[ca]), np.float64(n), n_joints)
+        rb, ra = _mean_mm(reps[:, cb].astype(np.float64), counts, n_joints), _mean_mm(reps[:, ca].astype(np.float64), counts, n_joints)
         diff = _interval(pa - pb, ra - rb, level)
         diff['p_not_better'] = float(np.mean(ra - rb >= 0.0))
         out[key] = {'before': _interval(pb, rb, level), 'after': _interval(pa, ra, level), 'difference': diff}
@@ -237,9 +252,9 @@ def _stats(point: np.ndarray, reps: np.ndarray, n_units: int, wrow: np.ndarray, 
 
 
 def derive(units: np.ndarray, group_of_unit: np.ndarray, segments: np.ndarray, sums: np.ndarray, wins: np.ndarray, names: Sequence[str],
-           level: float, seed: int = 0, unit_kind: str = 'frame') -> dict:
+           level: float, seed: int = 0, unit_kind: str = 'frame', n_joints: int = NJ) -> dict:
     """the numbers from the integers: units (K,5) ordered as the segments say, sums (1 + G, R, 5) the replicates, wins (G * 8 + 3).
-    Per segment and column mean_mm = sum / 2^24 / (17 count) * 1000 in float64 -- the point estimate from the unresampled sums, a
+    Per segment and column mean_mm = sum / 2^24 / (n_joints count) * 1000 in float64 (n_joints: 17, or the protocol's number) -- the point estimate from the unresampled sums, a
     replicate's from its own sums and its own count --; numpy.percentile at (1 -+ level) / 2 of before, after and after - before; their
     standard deviation over the replicates as the standard error; p_not_better = the share of replicates with after - before >= 0."""
     units, sums, wins, segments = np.asarray(units), np.asarray(sums), np.asarray(wins), np.asarray(segments)
@@ -250,8 +265,8 @@ def derive(units: np.ndarray, group_of_unit: np.ndarray, segments: np.ndarray, s
         raise ValueError(f'wins table: {G * WINS_ROW + WINS_TRAILER} words expected for {G} groups, got {wins.shape}')
     wrows = wins[:G * WINS_ROW].reshape(G, WINS_ROW)
     point = lambda s: units[int(segments[s, 0]):int(segments[s, 0]) + int(segments[s, 1])].sum(0) if segments[s, 1] else np.zeros(UNIT_ROW, dtype=np.int64)
-    return {'groups': {name: _stats(point(1 + i), sums[1 + i], int(segments[1 + i, 1]), wrows[i], level) for i, name in enumerate(names)},
-            ALL: _stats(point(0), sums[0], int(segments[0, 1]), wrows.sum(0), level), 'ignored': int(wins[G * WINS_ROW + T_IGNORED]),
+    return {'groups': {name: _stats(point(1 + i), sums[1 + i], int(segments[1 + i, 1]), wrows[i], level, n_joints) for i, name in enumerate(names)},
+            ALL: _stats(point(0), sums[0], int(segments[0, 1]), wrows.sum(0), level, n_joints), 'ignored': int(wins[G * WINS_ROW + T_IGNORED]),
             'reps': int(sums.shape[1]), 'seed': int(seed), 'level': float(level), 'unit': unit_kind}
 
 
@@ -263,7 +278,9 @@ def _cell(r: Optional[dict], spec='.2f') -> str:
 def markdown(doc: dict) -> str:
     d = doc['data']
     pct = f'{100 * d["level"]:g} %'
-    lines = [f'# Paired bootstrap of before → after ({doc["source"]}, groups by {doc["group_kind"]})', '',
+    title = f', protocol {doc["protocol"]["name"]}' if doc.get('protocol') else ''
+    lines = [f'# Paired bootstrap of before → after ({doc["source"]}, groups by {doc["group_kind"]}{title})', ''] + \
+            ([eval_protocol.headline(doc['protocol']), ''] if doc.get('protocol') else []) + [
              f'{d["reps"]} resamples of the {d["unit"]}s with replacement, both regressors on the same resample; seed {d["seed"]}.  '
              f'Errors in mm with the {pct} percentile interval; p = the share of resamples in which the retrained regressor was not better '
              f'(difference >= 0); better / worse / tie count the poses themselves.  A group resamples its own {d["unit"]}s.  The intervals '
@@ -283,9 +300,12 @@ def markdown(doc: dict) -> str:
     return '\n'.join(lines) + '\n'
 
 
-def write(directory: str, result: dict, group_names: Sequence[str], group_kind: str, source: str) -> Optional[dict]:
-    """DIR/ci.json and DIR/ci.md from what finish() returned; rank 0 alone writes (the others return None)"""
+def write(directory: str, result: dict, group_names: Sequence[str], group_kind: str, source: str, protocol: Optional[dict] = None) -> Optional[dict]:
+    """DIR/ci.json and DIR/ci.md from what finish() returned; rank 0 alone writes (the others return None).  protocol:
+    eval_protocol.document(...), None under the default"""
     doc = {'layout_version': LAYOUT_VERSION, 'source': source, 'group_kind': group_kind, 'groups': list(group_names), 'data': result, 'unit': 'mm'}
+    if protocol:
+        doc['protocol'] = protocol
     return group_table.write(directory, 'ci', doc, markdown)
 
 

@@ -931,7 +931,37 @@ def eval_accumulate(err_j: torch.Tensor, err_pa_j: torch.Tensor, group: torch.Te
           'eval_accumulate')
 
 
-ACCEL_ACC_ROW, ACCEL_ACC_TRAILER, ACCEL_TILE = 205, 2, 32      # include/jrr.h: JRR_ACCEL_ACC_ROW, JRR_ACCEL_ACC_TRAILER, JRR_ACCEL_TILE
+EVAL_ROOT_JOINT0, EVAL_ROOT_HIPS = 0, 1         # include/jrr.h: JRR_EVAL_ROOT_*
+EVAL_TARGET_MM, EVAL_TARGET_M = 0, 1            # JRR_EVAL_TARGET_*
+EVAL_MASK_ALL, EVAL_MASK_LSP14 = 0x1FFFF, 0x1FD7E      # JRR_EVAL_MASK_*
+
+
+def evaluate_protocol(pred_j3d: torch.Tensor, target_j3d: torch.Tensor, joint_mask: int, root: int, target_unit: int = EVAL_TARGET_MM,
+                      group: Optional[torch.Tensor] = None, n_groups: int = 1, acc: Optional[torch.Tensor] = None, rows: bool = True):
+    """jrr_evaluate_protocol: the per-joint distances of the joints of `joint_mask` after centring on `root`, err_j, err_pa_j (B,17) in
+    metres with +0.0 in the excluded columns (rows=False: None, None), and -- acc given -- their addition to the int64 table `acc`
+    (n_groups * 338 + 2 words, include/jrr.h JRR_EVAL_ACC_*) by `group` (B, int32; None: group 0), in ONE launch.  pred (B,17,3) m,
+    target (B,17,3) in `target_unit`."""
+    lib = _lib.load()
+    B = pred_j3d.shape[0]
+    dev = pred_j3d.device
+    pred_j3d, target_j3d = pred_j3d.contiguous(), target_j3d.contiguous()
+    assert pred_j3d.shape == (B, 17, 3) and target_j3d.shape == (B, 17, 3) and target_j3d.device == dev
+    assert pred_j3d.dtype == torch.float32 and target_j3d.dtype == torch.float32
+    if group is not None:
+        group = group.contiguous()
+        _check_ids(group, B, dev)
+    if acc is not None:
+        _check_acc(acc, n_groups, EVAL_ACC_ROW, EVAL_ACC_TRAILER, dev)
+    err_j, err_pa_j = (torch.empty(B, 17, device=dev), torch.empty(B, 17, device=dev)) if rows else (None, None)
+    if B == 0:                                      # an empty tensor has no address to pass
+        return err_j, err_pa_j
+    check(lib.jrr_evaluate_protocol(ptr(pred_j3d), ptr(target_j3d), int(target_unit), int(joint_mask), int(root), ptr(group), B, int(n_groups),
+                                    ptr(err_j), ptr(err_pa_j), ptr(acc), stream_ptr(dev)), 'evaluate_protocol')
+    return err_j, err_pa_j
+
+
+ACCEL_ACC_ROW, ACCEL_ACC_TRAILER, ACCEL_TILE = 205, 2, 32     # include/jrr.h: JRR_ACCEL_ACC_ROW, JRR_ACCEL_ACC_TRAILER, JRR_ACCEL_TILE
 
 
 def accel_error(pred: torch.Tensor, gt_mm: torch.Tensor, order: torch.Tensor, run: torch.Tensor, status: torch.Tensor,

@@ -16,6 +16,11 @@ on a CPU tensor table with a gloo group as well.
 optionally `paths.txt` or `group.npy` + `group_names.txt` -- through jrr_regress_joints with both regressors on one read of the
 vertices.  No SMPL model file, no engine.  `--eval_pve` adds the per-vertex error of the same meshes against `gt_vertices.npy`
 (vertex_report.py): one more launch per chunk, one more all-reduce at the end, and the files above keep their contents.
+
+`--eval_protocol` / `--eval_gt_joints` (eval_protocol.py) choose which joints are scored, where the skeletons are centred and where
+the ground-truth joints come from, as published tables do (14 LSP joints, hip root, joints regressed from the ground-truth meshes).
+Under the defaults nothing above changes; otherwise `add()` is ONE launch, jrr_evaluate_protocol, and every 17 in a divisor is the
+protocol's number of joints.
 """
 from __future__ import annotations
 
@@ -28,6 +33,7 @@ import numpy as np
 import torch
 
 from . import dist as jdist
+from . import eval_protocol
 from . import group_table
 from .group_table import ALL, MAX_GROUPS, arrow as _arrow, fmt as _fmt, rank as _rank
 
@@ -80,15 +86,19 @@ def assign_groups(paths: Optional[Sequence[str]], kind: str, n: Optional[int] = 
 
 # ---- the table -------------------------------------------------------------------------------------------------------------
 class EvalReport:
-    def __init__(self, group_names: Sequence[str], device):
+    def __init__(self, group_names: Sequence[str], device, protocol: Optional[eval_protocol.Protocol] = None):
+        """protocol None or `h36m17`: the reference's evaluate (all 17 joints, centred on joint 0)"""
         self.names = [str(g) for g in group_names]
+        self.protocol = eval_protocol.H36M17 if protocol is None else protocol
         group_table.check_groups(len(self.names))
         self.device = torch.device(device)
         self.acc = torch.zeros(len(self.names) * ROW + TRAILER, dtype=torch.int64, device=self.device)
 
-    def add(self, pred_joints: torch.Tensor, gt_j3d_mm: torch.Tensor, group_ids: Optional[torch.Tensor] = None) -> None:
-        """pred (B,17,3) m, gt (B,17,3) mm, group_ids (B,) int32 on the same device (None: group 0); < 0 = do not score.  Two
-        launches, nothing read back."""
+    def add(self, pred_joints: torch.Tensor, gt_j3d_mm: torch.Tensor, group_ids: Optional[torch.Tensor] = None,
+            target_unit: int = eval_protocol.TARGET_MM) -> None:
+        """pred (B,17,3) m, gt (B,17,3) mm (target_unit TARGET_M: metres), group_ids (B,) int32 on the same device (None: group 0);
+        < 0 = do not score.  The default protocol with a millimetre target: two launches (jrr_evaluate_joints, jrr_eval_accumulate);
+        any other: ONE launch (jrr_evaluate_protocol) that accumulates.  Nothing read back."""
         from . import engine as _engine
         B = pred_joints.shape[0]
         if group_ids is None:
@@ -96,16 +106,22 @@ class EvalReport:
         if group_ids.device != pred_joints.device or group_ids.dtype != torch.int32:
             raise ValueError(f'EvalReport.add: group_ids must be an int32 tensor on {pred_joints.device}, got {group_ids.dtype} on '
                              f'{group_ids.device}')
-        err_j, err_pa_j = _engine.evaluate_joints(pred_joints.detach().float(), gt_j3d_mm.detach().float())
-        _engine.eval_accumulate(err_j, err_pa_j, group_ids, len(self.names), self.acc)
+        if self.protocol.is_default and target_unit == eval_protocol.TARGET_MM:
+            err_j, err_pa_j = _engine.evaluate_joints(pred_joints.detach().float(), gt_j3d_mm.detach().float())
+            _engine.eval_accumulate(err_j, err_pa_j, group_ids, len(self.names), self.acc)
+            return
+        _engine.evaluate_protocol(pred_joints.detach().float(), gt_j3d_mm.detach().float(), self.protocol.joint_mask, self.protocol.root, target_unit,
+                                  group_ids, len(self.names), self.acc, rows=False)
 
     def finish(self, reduce: bool = True) -> dict:
         """the ONE all-reduce (reduce=False: this process evaluated everything alone), the one read-back, the derivation"""
-        return derive(group_table.all_reduce(self.acc, reduce).cpu().numpy(), self.names)
+        return derive(group_table.all_reduce(self.acc, reduce).cpu().numpy(), self.names, self.protocol)
 
 
-def _stats(row: np.ndarray) -> dict:
+def _stats(row: np.ndarray, joints: Optional[Sequence[int]] = None) -> dict:
+    """joints: the protocol's joints (None: all 17).  The divisor is their number; an excluded joint has no mean (None)"""
     n, n_bad = int(row[COUNT]), int(row[BAD])
+    nj = NJ if joints is None else len(joints)
     out = {'n': n, 'n_bad': n_bad, 'raw': [int(x) for x in row]}
     for key, s0, h0 in (('mpjpe', SUM, HIST), ('pampjpe', SUM_PA, HIST_PA)):
         sums = row[s0:s0 + NJ].astype(np.float64)
@@ -113,20 +129,23 @@ def _stats(row: np.ndarray) -> dict:
         if n == 0:
             out.update({f'{key}_mm': None, f'{key}_per_joint_mm': None, f'pck_{key}': None, f'auc_{key}': None})
             continue
-        out[f'{key}_mm'] = float(sums.sum() / FIXED / (NJ * n) * 1000.0)
-        out[f'{key}_per_joint_mm'] = [float(s / FIXED / n * 1000.0) for s in sums]
+        out[f'{key}_mm'] = float(sums.sum() / FIXED / (nj * n) * 1000.0)
+        out[f'{key}_per_joint_mm'] = [float(s / FIXED / n * 1000.0) if joints is None or i in joints else None for i, s in enumerate(sums)]
         below = np.concatenate([[0.0], np.cumsum(hist)])                      # below[t] = values < t mm, t = 0 .. 151
-        pck = lambda t: float(below[t] / (NJ * n))
+        pck = lambda t: float(below[t] / (nj * n))
         out[f'pck_{key}'] = {str(t): pck(t) for t in PCK_THRESHOLDS_MM}
         out[f'auc_{key}'] = float(np.mean([pck(t) for t in AUC_THRESHOLDS_MM]))
     return out
 
 
-def derive(table: np.ndarray, names: Sequence[str]) -> dict:
+def derive(table: np.ndarray, names: Sequence[str], protocol: Optional[eval_protocol.Protocol] = None) -> dict:
     """the numbers of one regressor's report from the int64 table (n_groups * 338 + 2 words): per group and for `all`
     n, n_bad, MPJPE / PA-MPJPE in mm = sum / 2^24 / (17 n) * 1000 in float64, the 17 per-joint means, PCK@t = (values in bins below t)
-    / (17 n), AUC = mean of PCK over t = 0, 5, ..., 150.  Raises when a pose carried a group id >= n_groups."""
-    return group_table.derive(table, names, ROW, _stats, 'evaluation table')
+    / (17 n), AUC = mean of PCK over t = 0, 5, ..., 150.  Under a protocol of fewer joints every 17 above is the protocol's number of
+    joints and the per-joint mean of an excluded joint is None.  Raises when a pose carried a group id >= n_groups."""
+    if protocol is None or protocol.joint_mask == eval_protocol.MASK_ALL:
+        return group_table.derive(table, names, ROW, _stats, 'evaluation table')
+    return group_table.derive(table, names, ROW, lambda row: _stats(row, protocol.joints), 'evaluation table')
 
 
 # ---- the files -------------------------------------------------------------------------------------------------------------
@@ -144,10 +163,14 @@ def markdown(doc: dict) -> str:
     first = 'before' if 'before' in reg else sorted(reg)[0]
     last = 'after' if 'after' in reg else sorted(reg)[-1]
     b, a = reg[first], reg[last]
-    lines = [f'# Evaluation report ({doc["source"]}, groups by {doc["group_kind"]})', '',
+    title = f', protocol {doc["protocol"]["name"]}' if doc.get('protocol') else ''
+    lines = [f'# Evaluation report ({doc["source"]}, groups by {doc["group_kind"]}{title})', '',
              f'`{first}`: {doc["j_regressor_initial"]["path"]} ({doc["j_regressor_initial"]["sha256_16"]})  ',
-             f'`{last}`: {doc["j_regressor_retrained"]["path"]} ({doc["j_regressor_retrained"]["sha256_16"]})', '',
-             f'Errors in mm, {first} → {last}.  PCK@150 and AUC (PCK over 0, 5, ..., 150 mm) of the unaligned error.', '',
+             f'`{last}`: {doc["j_regressor_retrained"]["path"]} ({doc["j_regressor_retrained"]["sha256_16"]})', ''] + \
+            ([eval_protocol.headline(doc['protocol']), '',
+              'The acceleration, bone and regressor reports (`--eval_accel`, `--eval_bones`, `--regressor_report`) do not know the protocol: '
+              'they run as before, on all 17 joints centred on joint 0.', ''] if doc.get('protocol') else []) + \
+            [f'Errors in mm, {first} → {last}.  PCK@150 and AUC (PCK over 0, 5, ..., 150 mm) of the unaligned error.', '',
              '| group | n | bad | MPJPE | PA-MPJPE | PCK@150 | AUC |', '|---|---|---|---|---|---|---|']
     for name in list(doc['groups']) + [ALL]:
         rb = b[ALL] if name == ALL else b['groups'][name]
@@ -172,14 +195,16 @@ def markdown(doc: dict) -> str:
 
 
 def write(directory: str, results: Dict[str, dict], group_names: Sequence[str], group_kind: str, source: str, flags: dict,
-          initial: Tuple[Optional[str], Optional[str]], retrained: Tuple[Optional[str], Optional[str]]) -> Optional[dict]:
+          initial: Tuple[Optional[str], Optional[str]], retrained: Tuple[Optional[str], Optional[str]], protocol: Optional[dict] = None) -> Optional[dict]:
     """DIR/eval.json and DIR/eval.md; rank 0 alone writes (the others return None).  `results`: name ('before', 'after') -> what
-    finish() returned; initial / retrained: (path, sha256[:16])."""
+    finish() returned; initial / retrained: (path, sha256[:16]); protocol: eval_protocol.document(...), None under the default."""
     doc = {'layout_version': LAYOUT_VERSION, 'source': source, 'group_kind': group_kind, 'groups': list(group_names),
            'joints': list(JOINT_NAMES), 'pck_thresholds_mm': list(PCK_THRESHOLDS_MM), 'auc_thresholds_mm': list(AUC_THRESHOLDS_MM),
            'regressors': results, 'flags': flags,
            'j_regressor_initial': {'path': initial[0], 'sha256_16': initial[1]},
            'j_regressor_retrained': {'path': retrained[0], 'sha256_16': retrained[1]}}
+    if protocol:
+        doc['protocol'] = protocol
     return group_table.write(directory, 'eval', doc, markdown)
 
 
@@ -188,14 +213,15 @@ def load(directory: str) -> dict:
 
 
 # ---- --eval_vertices -------------------------------------------------------------------------------------------------------
-def open_vertices_dir(directory: str, kind: str = 'action'):
+def open_vertices_dir(directory: str, kind: str = 'action', gt_joints: str = 'file'):
     """(vertices memmap (N,6890,3) float32, gt_j3d memmap (N,17,3) float32, group names, int32 ids (N,)) of an --eval_vertices
-    directory.  Refuses -- with the file's name -- a wrong shape or dtype, a vertex count other than 6890 and NaN ground truth."""
+    directory.  Refuses -- with the file's name -- a wrong shape or dtype, a vertex count other than 6890 and NaN ground truth.
+    gt_joints 'regressed' (`--eval_gt_joints regressed`): gt_j3d.npy is neither required nor read, None stands in its place."""
     vp, gp = os.path.join(directory, 'vertices.npy'), os.path.join(directory, 'gt_j3d.npy')
-    for p in (vp, gp):
+    for p in (vp, gp) if gt_joints != 'regressed' else (vp,):
         if not os.path.isfile(p):
             raise FileNotFoundError(f'--eval_vertices: {p} is missing')
-    verts, gt = np.load(vp, mmap_mode='r'), np.load(gp, mmap_mode='r')
+    verts, gt = np.load(vp, mmap_mode='r'), (np.load(gp, mmap_mode='r') if gt_joints != 'regressed' else None)
     if verts.ndim != 3 or verts.shape[2] != 3:
         raise ValueError(f'{vp}: (N,6890,3) expected, got {verts.shape}')
     if verts.shape[1] != 6890:
@@ -203,11 +229,11 @@ def open_vertices_dir(directory: str, kind: str = 'action'):
     if verts.dtype != np.float32:
         raise ValueError(f'{vp}: float32 expected, got {verts.dtype}')
     N = verts.shape[0]
-    if gt.shape != (N, NJ, 3):
+    if gt is not None and gt.shape != (N, NJ, 3):
         raise ValueError(f'{gp}: ({N},17,3) expected for {N} meshes, got {gt.shape}')
-    if gt.dtype not in (np.float32, np.float64):
+    if gt is not None and gt.dtype not in (np.float32, np.float64):
         raise ValueError(f'{gp}: float32 or float64 expected, got {gt.dtype}')
-    if np.isnan(gt).any():
+    if gt is not None and np.isnan(gt).any():
         raise ValueError(f'{gp}: NaN in the ground truth of sample {int(np.argwhere(np.isnan(gt).reshape(N, -1).any(1))[0, 0])}')
     pp, gnp, gip = (os.path.join(directory, f) for f in ('paths.txt', 'group_names.txt', 'group.npy'))
     if kind != 'none' and os.path.isfile(pp):
@@ -258,8 +284,11 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     vertex_report.check_flags(args._get())
     ci_report.check_flags(args._get())
     penetration_report.check_flags(args._get())
-    verts, gt, names, ids = open_vertices_dir(args.eval_vertices, args.eval_groups)          # before any launch
-    gt_verts = vertex_report.open_gt_vertices(args.eval_vertices, verts.shape[0]) if args.eval_pve else None
+    eval_protocol.check_flags(args._get())
+    protocol, gt_joints = eval_protocol.of(args._get()), eval_protocol.gt_source(args._get())
+    regressed = gt_joints == 'regressed'
+    verts, gt, names, ids = open_vertices_dir(args.eval_vertices, args.eval_groups, gt_joints)          # before any launch
+    gt_verts = vertex_report.open_gt_vertices(args.eval_vertices, verts.shape[0]) if args.eval_pve or regressed else None
     part_np = None
     if args.eval_pve and args.eval_pve_parts:      # the body model as --regressor_report resolves it; every rank labels the vertices alike
         model_parts = regressor_report.resolve_body_model(args.smpl_dir, args.synthetic)
@@ -276,6 +305,9 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     rank, local_rank, world = jdist.env_rank_world()
     device = torch.device(args.device if (world == 1 or args.single_device) else f'cuda:{local_rank}')
     torch.cuda.set_device(device)
+    if regressed and rank == 0:
+        log(f'--eval_gt_joints regressed: the ground-truth joints are each regressor applied to {os.path.join(args.eval_vertices, vertex_report.GT_NAME)}; '
+            f'gt_j3d.npy is not read')
     path = args.eval_j_regressor or args.save_j_regressor or 'models/retrained_J_Regressor.pt'
     J_after = checkpoint.load_j_regressor(path).float()
     J_np = smpl_model.default_h36m_regressor(args.j_regressor_init,
@@ -283,7 +315,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     J_before = torch.from_numpy(J_np).float()
     Js = torch.stack([J_before, J_after.cpu()]).to(device)
     table = _engine.JointRegressorTable(Js, utils.find_j_reg_mask(Js[0]))     # the mask of scripts/test.py:51-53,108
-    reports = {'before': EvalReport(names, device), 'after': EvalReport(names, device)} if args.eval_report else None
+    reports = {'before': EvalReport(names, device, protocol), 'after': EvalReport(names, device, protocol)} if args.eval_report else None
     mask_np = utils.find_j_reg_mask(J_before).numpy()
     shift = regressor_report.Run(args._get(), names, device, J_np, J_after.cpu().numpy(), mask_np, 'vertices') if args.regressor_report else None
     N = verts.shape[0]
@@ -292,8 +324,8 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     if args.eval_bones:        # subjects from paths.txt when present; without it the rigidity section says so
         subject_names, subject_ids = bones_report.subjects_of(read_optional_paths(args.eval_vertices, verts.shape[0]))
         bones = bones_report.BoneReport(names, subject_names, device)
-    ci = ci_report.PairedBootstrap(names, *ci_report.unit_ids(args.eval_ci_unit, N, ci_paths), device, ids) if args.eval_ci else None
-    pve = vertex_report.VertexReport(names, device, 6890, part_np, 0 if part_np is None else model_parts['lbs_weights'].shape[1]) if gt_verts is not None else None
+    ci = ci_report.PairedBootstrap(names, *ci_report.unit_ids(args.eval_ci_unit, N, ci_paths), device, ids, protocol=protocol) if args.eval_ci else None
+    pve = vertex_report.VertexReport(names, device, 6890, part_np, 0 if part_np is None else model_parts['lbs_weights'].shape[1]) if args.eval_pve else None
     root_table = _engine.JointRegressorTable(Js[:1], utils.find_j_reg_mask(Js[0])) if pve is not None else None      # joint 0 of the INITIAL regressor centres both meshes
     pen = penetration_report.PenetrationReport(names, device, pen_model['faces'], N, args.eval_penetration_offset_mm, pen_sign,
                                                vertex_report.part_labels(pen_model['lbs_weights']), pen_model['lbs_weights'].shape[1]) if pen_model is not None else None
@@ -301,7 +333,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
     bs = max(1, int(args.batch_size))
     stage = [(torch.empty((bs, 6890, 3), dtype=torch.float32).pin_memory(), torch.empty((bs, NJ, 3), dtype=torch.float32).pin_memory(),
               torch.empty((bs,), dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(2)]
-    stage_gt = [torch.empty((bs, 6890, 3), dtype=torch.float32).pin_memory() for _ in range(2)] if pve is not None else None      # --eval_pve: the third pinned buffer
+    stage_gt = [torch.empty((bs, 6890, 3), dtype=torch.float32).pin_memory() for _ in range(2)] if gt_verts is not None else None      # --eval_pve, --eval_gt_joints regressed: the third pinned buffer
     used = [False, False]
     with torch.no_grad():
         for k, a in enumerate(range(lo, hi, bs)):
@@ -311,19 +343,25 @@ def evaluate_vertices(log=print) -> Optional[dict]:
             if used[k % 2]:
                 ev.synchronize()                                              # the upload that last read this buffer is done
             pv.numpy()[:n] = verts[a:b]
-            pg.numpy()[:n] = gt[a:b]
+            if gt is not None:
+                pg.numpy()[:n] = gt[a:b]
             pi.numpy()[:n] = ids[a:b]
             dv, dg, di = (t[:n].to(device, non_blocking=True) for t in (pv, pg, pi))
-            if pve is not None:
+            if gt_verts is not None:
                 stage_gt[k % 2].numpy()[:n] = gt_verts[a:b]
                 dq = stage_gt[k % 2][:n].to(device, non_blocking=True)
             ev.record()
             used[k % 2] = True
             joints = table.regress(dv)
-            gtc = utils.move_pelvis(dg)                                       # scripts/test.py:87
+            if regressed:      # each regressor's own joints of the ground-truth mesh, in metres: the retrained regressor moves both sides
+                gtj = table.regress(dq)
+                gts, unit = (gtj[0], gtj[1]), eval_protocol.TARGET_M
+            else:
+                gtc = utils.move_pelvis(dg)                                   # scripts/test.py:87
+                gts, unit = (gtc, gtc), eval_protocol.TARGET_MM
             if reports is not None:
-                reports['before'].add(joints[0], gtc, di)
-                reports['after'].add(joints[1], gtc, di)
+                reports['before'].add(joints[0], gts[0], di, unit)
+                reports['after'].add(joints[1], gts[1], di, unit)
             if track is not None:
                 track.add(np.arange(a, b), (joints[0], joints[1]), gtc)
             if bones is not None:
@@ -331,7 +369,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
                 bones.add('before', joints[0], gtc, di, ds)
                 bones.add('after', joints[1], gtc, di, ds)
             if ci is not None:
-                ci.add(joints[0], joints[1], gtc, di, np.arange(a, b))
+                ci.add(joints[0], joints[1], gts, di, np.arange(a, b), unit)
             if shift is not None:
                 shift.add(dv, joints[0], joints[1], gtc, di, ids[a:b] >= 0)
             if pve is not None:
@@ -345,15 +383,16 @@ def evaluate_vertices(log=print) -> Optional[dict]:
         if reports is None:
             return shift_doc
     results = {k: r.finish() for k, r in reports.items()}
-    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(args._get())))))), initial,
-                retrained)
+    entry = eval_protocol.document(protocol, gt_joints, JOINT_NAMES)
+    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', eval_protocol.flags_doc(penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(args._get()))))))), initial,
+                retrained, entry)
     accel_doc = None
     if track is not None:      # every mesh is present and every rank knows it: the float all-reduce, the launches, the integer all-reduce
         accel_doc = accel_report.write(args.eval_report, track.finish(accel_paths, ids, names, ('before', 'after'), present=np.ones(N, dtype=bool)),
                                        args.eval_groups, 'vertices')
     bones_doc = bones_report.write(args.eval_report, bones.finish(), args.eval_groups, 'vertices', results) if bones is not None else None
     ci_doc = ci_report.write(args.eval_report, ci.finish(args.eval_ci_reps, args.seed, args.eval_ci_level, args.eval_ci_unit), names, args.eval_groups,
-                             'vertices') if ci is not None else None
+                             'vertices', entry) if ci is not None else None
     pve_doc = vertex_report.write(args.eval_report, pve.finish(), names, args.eval_groups, 'vertices', initial) if pve is not None else None
     pen_doc = penetration_report.write(args.eval_report, pen.finish(), names, args.eval_groups, 'vertices', args.eval_penetration_offset_mm, pen_sign) if pen is not None else None
     if rank == 0:

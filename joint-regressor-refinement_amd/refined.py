@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import ci_report
+from . import eval_protocol
 from . import dist as jdist
 from .args import args
 
@@ -120,7 +121,7 @@ class RefinedExport:
     def finish(self):
         if self.table is None:
             raise RuntimeError('--save_refined: no batch was refined, there is nothing to save')
-        flags_doc = {k: v for k, v in ci_report.flags_doc(args._get()).items() if isinstance(v, (bool, int, float, str, type(None))) and k not in ('eval_accel', 'regressor_report_depth', 'eval_bones', 'eval_penetration', 'eval_penetration_offset_mm')}
+        flags_doc = {k: v for k, v in eval_protocol.flags_doc(ci_report.flags_doc(args._get())).items() if isinstance(v, (bool, int, float, str, type(None))) and k not in ('eval_accel', 'regressor_report_depth', 'eval_bones', 'eval_penetration', 'eval_penetration_offset_mm')}
         self.table.finish(self.directory, {'flags': flags_doc, 'body_model': self.body_model, 'j_regressor_sha256_16': self.j_hash,
                                            'inner_iters': int(args.inner_iters), 'data': 'dataset' if args.data_root else 'synthetic'})
 

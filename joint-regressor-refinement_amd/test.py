@@ -18,7 +18,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import accel_report, batches, bones_report, checkpoint, ci_report, engine as _engine, eval_report, penetration_report, regressor_report, smpl_model, utils
+from . import accel_report, batches, bones_report, checkpoint, ci_report, engine as _engine, eval_protocol, eval_report, penetration_report, regressor_report, smpl_model, utils
 from .args import args
 from .smpl import SMPL
 
@@ -95,6 +95,8 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     ci_units = _ci_units() if args.eval_ci else None                                                     # likewise
     bones_report.check_flags(args._get())                                                                # likewise
     penetration_report.check_flags(args._get())                                                          # likewise: --eval_penetration belongs to --eval_vertices
+    eval_protocol.check_flags(args._get())                                                               # likewise: --eval_gt_joints regressed belongs to --eval_vertices
+    protocol = eval_protocol.of(args._get())                                                             # of eval.json / ci.json; the printed means stay the 17-joint evaluate
     device = torch.device(args.device)
     torch.cuda.set_device(device)
     smpl = SMPL(args.smpl_dir, batch_size=1, allow_synthetic=args.synthetic or args.smpl_dir == 'SPIN/data/smpl').to(device)   # :40-43
@@ -114,7 +116,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
         shift = regressor_report.Run(args._get(), names, device, J_np, J_regressor.cpu().numpy(), j_reg_mask.cpu().numpy(), 'parameters', **depth_model)
     if args.eval_report:       # per group / per joint / PCK next to the four printed means: two more launches per evaluate, no read-back
         names, group_ids = _groups()
-        reports = {'before': eval_report.EvalReport(names, device), 'after': eval_report.EvalReport(names, device)}
+        reports = {'before': eval_report.EvalReport(names, device, protocol), 'after': eval_report.EvalReport(names, device, protocol)}
     track = accel_report.JointTrack(len(accel_paths), 2, device) if accel_paths is not None else None
     bones, subject_ids = None, None
     if args.eval_bones:        # the skeleton beside the points: one launch per regressor and one per table, no read-back
@@ -161,7 +163,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
             if args.eval_ci:   # three more launches: both regressors' per-joint errors, then the units; nothing read back
                 if ci is None:
                     unit_of_row, n_units = ci_units or ci_report.unit_ids('frame', int(batch.get('n_samples', args.synthetic_batches * B)))
-                    ci = ci_report.PairedBootstrap(names, unit_of_row, n_units, device, group_ids)
+                    ci = ci_report.PairedBootstrap(names, unit_of_row, n_units, device, group_ids, protocol=protocol)
                 ci.add(joints_before, joints, gt, gid, batch['index'] if 'index' in batch else torch.arange(ci_seen, ci_seen + B))
                 ci_seen += B
             if shift is not None:
@@ -175,8 +177,8 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     if reports is not None:    # this function runs in ONE process (main.py: rank 0) on whole batches: nothing to reduce
         results = {k: r.finish(reduce=False) for k, r in reports.items()}
         rep['eval_report'] = eval_report.write(args.eval_report, results, names, args.eval_groups if group_ids is not None else 'none', 'parameters',
-                                               penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(accel_report.flags_doc(args._get()))))), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
-                                               (path, eval_report.sha16(path)))
+                                               eval_protocol.flags_doc(penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(accel_report.flags_doc(args._get())))))), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
+                                               (path, eval_report.sha16(path)), eval_protocol.document(protocol, 'file', eval_report.JOINT_NAMES))
     if track is not None:      # one launch per regressor over the whole split's time order, one read-back
         rep['accel_report'] = accel_report.write(args.eval_report, track.finish(accel_paths, group_ids, names, ('before', 'after'), reduce=False),
                                                  args.eval_groups, 'parameters')
@@ -185,7 +187,8 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
                                                  'parameters', results)
     if ci is not None:         # the read-back of the unit table, one launch for all replicates, the read-back of their sums
         rep['ci_report'] = ci_report.write(args.eval_report, ci.finish(args.eval_ci_reps, args.seed, args.eval_ci_level, args.eval_ci_unit, reduce=False),
-                                           names, args.eval_groups if group_ids is not None else 'none', 'parameters')
+                                           names, args.eval_groups if group_ids is not None else 'none', 'parameters',
+                                           eval_protocol.document(protocol, 'file', eval_report.JOINT_NAMES))
     if shift is not None:
         rep['regressor_report'] = shift.finish((args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
                                                (path, eval_report.sha16(path)), smpl.model_np, smpl.device_model, reduce=False)

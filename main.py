@@ -12,7 +12,8 @@ networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evalu
 (regressor_solve.py) it solves that fit exactly from the table's second moments instead of taking Adam epochs.
 `--eval_accel` (accel_report.py) adds the acceleration error along each video sequence to the evaluations and to those two commands.
 `--eval_bones` (bones_report.py) adds bone length and direction errors to the evaluations.
-`--eval_ci` (ci_report.py) adds paired bootstrap intervals of before, after and their difference to the evaluations."""
+`--eval_ci` (ci_report.py) adds paired bootstrap intervals of before, after and their difference to the evaluations.
+`--eval_protocol` / `--eval_gt_joints` (eval_protocol.py) score the evaluations as published tables do: 14 joints, hip root, mesh GT."""
 import importlib
 import os
 import sys
@@ -41,6 +42,7 @@ if __name__ == '__main__':
     importlib.import_module(PKG + '.vertex_report').check_flags(args._get())      # --eval_pve: likewise
     importlib.import_module(PKG + '.ci_report').check_flags(args._get())          # --eval_ci: likewise
     importlib.import_module(PKG + '.penetration_report').check_flags(args._get())  # --eval_penetration: likewise
+    importlib.import_module(PKG + '.eval_protocol').check_flags(args._get())      # --eval_protocol / --eval_gt_joints: likewise
     if args.fit_regressor:                                                   # Adam steps of the regressor on fixed meshes; no inner loop
         importlib.import_module(PKG + '.regressor_fit').fit_command()
         sys.exit(0)
