@@ -279,6 +279,29 @@ enum {
   JRR_BONE_ACC_TRAILER = 2          /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
 };
 
+/* jrr_place_translation / jrr_place_accumulate (`--place_refined`): the camera-frame translation of a posed body under the real
+ * intrinsics.  The status word of a pose, and the table: JRR_PLACE_ACC_ROW int64 per group, offsets in int64, then the trailer of the
+ * evaluation table behind the last row.  Layout version 1.
+ * Overflow: a pixel distance below the cap 1.0e3f gives llrintf(e * 2^24) < 2^34, so a SUM word stays below 2^63 for 5e8 poses. */
+enum {
+  JRR_PLACE_ACC_LAYOUT_VERSION = 1,
+  JRR_PLACE_MAX_ITERS = 64,
+  JRR_PLACE_FEW_OR_NONFINITE = 1,   /* bit 0: fewer than 2 taking-part joints, or a non-finite value among the pose's inputs */
+  JRR_PLACE_LINEAR_PIVOT = 2,       /* bit 1: a pivot of the linear start's factorisation is not positive */
+  JRR_PLACE_LINEAR_BEHIND = 4,      /* bit 2: the linear start leaves a taking-part joint at Z <= 0 */
+  JRR_PLACE_STEP_PIVOT = 8,         /* bit 3: a pivot failed inside a Levenberg-Marquardt step (the step was rejected; the result is kept) */
+  JRR_PLACE_BAD_BITS = 7,           /* a pose with one of bits 0 .. 2 holds NaN in trans and in both error rows */
+  JRR_PLACE_ACC_ROW = 55,
+  JRR_PLACE_ACC_COUNT = 0,          /* poses counted */
+  JRR_PLACE_ACC_BAD = 1,            /* poses of this group left out: a status bit 0 .. 2, or a summed value that fails |v| < 1.0e3f */
+  JRR_PLACE_ACC_STEP_PIVOT = 2,     /* counted poses with status bit 3 */
+  JRR_PLACE_ACC_SUM_TZ = 3,         /* sum over the counted poses of llrintf((float)trans_z * 2^24) (units of 2^-24 m) */
+  JRR_PLACE_ACC_JOINTS = 4,         /* 17: counted poses in which joint j takes part */
+  JRR_PLACE_ACC_SUM_ERR_LIN = 21,   /* 17: sum over those of llrintf(err_lin_j * 2^24) (units of 2^-24 px) */
+  JRR_PLACE_ACC_SUM_ERR = 38,       /* 17: the same for err_j */
+  JRR_PLACE_ACC_TRAILER = 2         /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
+};
+
 /* The paired bootstrap of the evaluation report (`--eval_ci`): jrr_paired_units fills two int64 tables, jrr_bootstrap_sums resamples
  * the first.  Layout version 1.
  *   units  [n_units][JRR_BOOT_UNIT_ROW]: per resampling unit (a video sequence, or a frame) the sums over its counted poses.
@@ -1039,6 +1062,54 @@ int jrr_bone_error(const float* pred_j3d_dev, const float* target_j3d_mm_dev, in
  * the sharding over ranks (sum the ranks' tables).  batch == 0 returns JRR_OK without a launch; JRR_ERR_ARG with a message for a NULL
  * vals_dev or acc_dev, batch < 0, n_groups out of range, vals_dev / group_dev not 4-byte or acc_dev not 8-byte aligned.            */
 int jrr_bone_accumulate(const float* vals_dev, const int32_t* group_dev, int batch, int n_groups, int64_t* acc_dev, void* stream);
+
+/* ---- placing a posed body in the real camera (`--place_refined`) -----------------------------------
+ * jrr_place_translation: per pose the translation t (SMPL `transl`: camera-frame point = model point + t) that brings the 17 joints
+ * S_j (joints_dev (B,17,3) fp32, metres, as jrr_find_joints_forward returns them) onto their pixels (u_j, v_j) (j2d_dev (B,17,2)
+ * fp32, full-frame pixels) under the pinhole camera fx = K[0][0], fy = K[1][1], cx = K[0][2], cy = K[1][2] of K_dev (B,3,3) fp32 (no
+ * other entry is read).  weight_dev (B,17) fp32 or NULL (all ones): joint j TAKES PART when its weight is finite and > 0.  The
+ * arithmetic is fp64 on the fp32 inputs, every operation rounded once in the order written (no contraction), sums over j ascending:
+ *   linear start   with a = u - cx, b = v - cy every taking-part joint gives the rows (fx, 0, -a | a Z - fx X) and (0, fy, -b | b Z - fy Y)
+ *                  of a system in t; A = sum w row row^T (the six entries of the upper triangle), y = sum w row rhs; t_lin solves
+ *                  A t = y by the root-free Cholesky factorisation A = L D L^T: d0 = A00, l10 = A01 / d0, l20 = A02 / d0,
+ *                  d1 = A11 - l10 A01, l21 = (A12 - l20 A01) / d1, d2 = (A22 - l20 A02) - l21 (A12 - l20 A01); z0 = y0,
+ *                  z1 = y1 - l10 z0, z2 = (y2 - l20 z0) - l21 z1; t2 = z2 / d2, t1 = z1 / d1 - l21 t2, t0 = (z0 / d0 - l10 t1) - l20 t2.
+ *                  A pivot d that fails d > 0 sets bit 1.
+ *   cost           c(t) = sum_j w_j (ru^2 + rv^2), ru = fx (X + t0) / (Z + t2) + cx - u, rv likewise
+ *   LM step        exactly n_iters of them, lambda = 1e-3 at first: with q = 1 / (Z + t2) the Jacobian rows (fx q, 0, -fx (X + t0) q q)
+ *                  and (0, fy q, -fy (Y + t1) q q); H = sum w row row^T, g = sum w row r; (H + lambda diag(H)) d = -g by the same
+ *                  factorisation (a failed pivot: bit 3, the step is rejected); t + d is accepted when c(t + d) < c(t) and every
+ *                  taking-part joint keeps Z + t2 > 0 -- then lambda = max(lambda / 10, 1e-7) -- otherwise lambda = min(10 lambda, 1e7)
+ *   errors         err_lin_j / err_j = sqrt(ru^2 + rv^2) at t_lin / at the result, for all 17 joints, rounded to fp32
+ * trans_dev (B,3) DOUBLE, err_lin_dev (B,17) fp32 or NULL, err_dev (B,17) fp32, status_dev (B) int32 (JRR_PLACE_* bits above; bit 0:
+ * fewer than 2 taking-part joints, or one of the pose's 51 + 34 coordinates or of its fx, fy, cx, cy is not finite -- a weight that is
+ * not finite only keeps its joint out; bit 2: t_lin leaves a taking-part joint at Z + t2 <= 0).  A pose with bit 0, 1 or 2 holds NaN in
+ * trans and in both error rows.  One pose per thread, staged through LDS; a pose's result depends on nothing but that pose -- not on
+ * the batch, its position in it or the launch.  0 <= n_iters <= JRR_PLACE_MAX_ITERS.  batch == 0 returns JRR_OK without a launch;
+ * JRR_ERR_ARG with a message, and no launch: a NULL joints_dev, j2d_dev, K_dev, trans_dev, err_dev or status_dev, batch < 0, n_iters
+ * out of range, trans_dev not 8-byte or another array not 4-byte aligned.                                                        */
+int jrr_place_translation(const float* joints_dev, const float* j2d_dev, const float* K_dev, const float* weight_dev, int batch, int n_iters,
+                          double* trans_dev, float* err_lin_dev, float* err_dev, int32_t* status_dev, void* stream);
+/* jrr_project_points: the pinhole projection itself, for the 17 joints and the 6890 vertices alike.  points_dev (B,N,3) fp32,
+ * trans_dev (B,3) double -- rounded to fp32 once --, K_dev (B,3,3) as above; in fp32, each operation rounded once:
+ *   d = Z + tz,  u = (fx * (X + tx)) / d + cx,  v = (fy * (Y + ty)) / d + cy
+ * -> uv_dev (B,N,2) fp32, NaN for a point with d <= 0 (or d NaN), and depth_dev (B,N) fp32 or NULL: d itself.  batch == 0 or
+ * n_points == 0 returns JRR_OK without a launch; JRR_ERR_ARG with a message: a NULL points_dev, trans_dev, K_dev or uv_dev, batch < 0,
+ * n_points < 0, batch * n_points >= 2^31, trans_dev not 8-byte or another array not 4-byte aligned.                                */
+int jrr_project_points(const float* points_dev, const double* trans_dev, const float* K_dev, int batch, int n_points, float* uv_dev,
+                       float* depth_dev, void* stream);
+/* jrr_place_accumulate ADDS the poses jrr_place_translation wrote to rows group_dev[b] of acc_dev: int64 [n_groups][JRR_PLACE_ACC_ROW]
+ * + JRR_PLACE_ACC_TRAILER words, layout above; the caller zeroes it once per report.  group_dev NULL: every pose in group 0;
+ * weight_dev NULL: every joint takes part; err_lin_dev NULL: the SUM_ERR_LIN words stay as they are.  A pose adds to exactly one class
+ * of words:  group < 0: trailer word 0 only;  group >= n_groups: trailer word 1 only;  a status bit 0 .. 2, a trans_z that fails
+ * |(float)trans_z| < 1.0e3f or an err / err_lin of a taking-part joint that fails e < 1.0e3f: BAD += 1 only;  otherwise COUNT += 1,
+ * STEP_PIVOT += 1 with status bit 3, SUM_TZ += fixed24((float)trans_z) and per taking-part joint j JOINTS[j] += 1, SUM_ERR_LIN[j] +=
+ * fixed24(err_lin_j), SUM_ERR[j] += fixed24(err_j), fixed24(v) = llrintf(v * 2^24).  Integer atomics only: the table is a function of
+ * the multiset of poses -- not of the order, the split into calls or the sharding over ranks.  batch == 0 returns JRR_OK without a
+ * launch; JRR_ERR_ARG with a message for a NULL trans_dev, err_dev, status_dev or acc_dev, batch < 0, n_groups out of range, trans_dev
+ * or acc_dev not 8-byte or another array not 4-byte aligned.                                                                       */
+int jrr_place_accumulate(const double* trans_dev, const float* err_lin_dev, const float* err_dev, const float* weight_dev,
+                         const int32_t* status_dev, const int32_t* group_dev, int batch, int n_groups, int64_t* acc_dev, void* stream);
 
 /* ---- 2-D reprojection --------------------------------------------
  * return_2d_joints core, scripts/renderer.py:35-49 (pytorch3d 0.3.0 PerspectiveCameras, R = I,

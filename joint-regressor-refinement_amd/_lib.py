@@ -91,6 +91,9 @@ SIGNATURES = {
     'jrr_penetration_accumulate': (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     'jrr_bone_error': (c_int, [_P, _P, c_int, _P, _P]),
     'jrr_bone_accumulate': (c_int, [_P, _P, c_int, c_int, _P, _P]),
+    'jrr_place_translation': (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
+    'jrr_project_points': (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P]),
+    'jrr_place_accumulate': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
     'jrr_project_joints': (c_int, [_P, _P, _P, c_int, _P]),
     'jrr_engine_set_reprojection': (c_int, [_P, _P, _P, _P, _P]),
     'jrr_camera_prefit': (c_int, [_P, _P, _P, _P, _P, c_int, c_float, _P, _P]),

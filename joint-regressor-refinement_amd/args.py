@@ -78,6 +78,16 @@ def build_parser() -> argparse.ArgumentParser:
                              'view disagreed and the joint error of both, print one line and exit (refined.fuse_views)')
     parser.add_argument('--fuse_max_deg', type=float, default=30.0,
                         help='--fuse_refined: a view further than this from the medoid view of a joint is left out of the mean; 0: the plain mean')
+    parser.add_argument('--place_refined', type=str, default=None, metavar='PATH',
+                        help='with --data_root: place every refined pose of the table --save_refined wrote (DIR, or a named .npz of it such as '
+                             'DIR/refined_fused.npz) in its real camera -- the translation that brings its 17 joints (--eval_j_regressor, else '
+                             'the initial regressor) onto the full-frame gt_j2d under the sample\'s intrinsics; write DIR/refined_placed.npz '
+                             'with trans / trans_linear / reproj_px / reproj_px_linear / place_status, DIR/place.json and DIR/place.md, '
+                             'print one line and exit (refined.place)')
+    parser.add_argument('--place_iters', type=int, default=10,
+                        help='--place_refined: Levenberg-Marquardt steps on the pixel error behind the linear start, 0 .. 64')
+    parser.add_argument('--place_weights', type=str, default=None, metavar='FILE.npy',
+                        help='--place_refined: per-joint weights (N,17); a joint takes part when its weight is finite and > 0 (default: ones)')
     parser.add_argument('--smooth_sigma', type=float, default=2.0, help='--smooth_refined: standard deviation of the Gaussian, in sampled frames')
     parser.add_argument('--smooth_radius', type=int, default=None,
                         help='--smooth_refined: the window reaches this many frames to either side, 0 .. 16 (default: min(16, ceil(3 sigma)))')
@@ -221,6 +231,17 @@ REFERENCE_FLAGS = {
     'learning_rate': 1e-4, 'opt_lr': 1e-2, 'disc_learning_rate': 1e-4, 'opt_disc_learning_rate': 1e-3,
     'translation_lr': 1e-6, 'j_reg_lr': 1e-2, 'optimization_rate': 1e4, 'wandb_log': False, 'compute_canada': False,
     'device': 'cuda:0'}
+
+
+PLACE_FLAGS = ('place_refined', 'place_iters', 'place_weights')
+
+
+def recorded(ns):
+    """the flags (a namespace, or a dict) as the output files of the OTHER commands record them: without the flags of `--place_refined`,
+    a command of its own that runs none of the code that records flags -- those files keep the bytes they had before the command existed"""
+    if isinstance(ns, dict):
+        return {k: v for k, v in ns.items() if k not in PLACE_FLAGS}
+    return argparse.Namespace(**{k: v for k, v in vars(ns).items() if k not in PLACE_FLAGS})
 
 
 def get_args(argv=None) -> argparse.Namespace:

@@ -1278,6 +1278,84 @@ def bone_accumulate(vals: torch.Tensor, group: Optional[torch.Tensor], n_groups:
     check(lib.jrr_bone_accumulate(ptr(vals), ptr(group), B, int(n_groups), ptr(acc), stream_ptr(vals.device)), 'bone_accumulate')
 
 
+PLACE_ACC_ROW, PLACE_ACC_TRAILER, PLACE_MAX_ITERS = 55, 2, 64     # include/jrr.h: JRR_PLACE_ACC_ROW, JRR_PLACE_ACC_TRAILER, JRR_PLACE_MAX_ITERS
+
+
+def _check_f32(t: torch.Tensor, shape, dev=None) -> torch.Tensor:
+    t = t.contiguous()
+    assert tuple(t.shape) == tuple(shape) and t.dtype == torch.float32 and t.is_cuda and (dev is None or t.device == dev), (t.shape, t.dtype, t.device)
+    return t
+
+
+def place_translation(joints: torch.Tensor, j2d: torch.Tensor, K: torch.Tensor, weight: Optional[torch.Tensor] = None, n_iters: int = 10, out=None):
+    """jrr_place_translation: joints (B,17,3) m, j2d (B,17,2) full-frame pixels, K (B,3,3), weight (B,17) or None (ones) ->
+    (trans (B,3) float64 m, err_lin (B,17) px, err (B,17) px, status (B,) int32); include/jrr.h has the algorithm and the
+    JRR_PLACE_* status bits.  `out`: the four tensors to fill (err_lin None: not wanted)."""
+    lib = _lib.load()
+    B = int(joints.shape[0])
+    dev = joints.device
+    joints, j2d, K = _check_f32(joints, (B, 17, 3)), _check_f32(j2d, (B, 17, 2), dev), _check_f32(K, (B, 3, 3), dev)
+    if weight is not None:
+        weight = _check_f32(weight, (B, 17), dev)
+    if not 0 <= int(n_iters) <= PLACE_MAX_ITERS:
+        raise ValueError(f'place_translation: n_iters {n_iters}: 0 .. {PLACE_MAX_ITERS}')
+    if out is None:
+        out = (torch.empty(B, 3, dtype=torch.float64, device=dev), torch.empty(B, 17, device=dev), torch.empty(B, 17, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev))
+    trans, err_lin, err, status = out
+    assert trans.shape == (B, 3) and trans.dtype == torch.float64 and trans.is_contiguous() and trans.device == dev
+    assert status.shape == (B,) and status.dtype == torch.int32 and status.is_contiguous() and status.device == dev
+    for t in (err_lin, err):
+        assert t is None or (t.shape == (B, 17) and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev)
+    if B == 0:                                      # an empty tensor has no address to pass
+        return out
+    check(lib.jrr_place_translation(ptr(joints), ptr(j2d), ptr(K), ptr(weight), B, int(n_iters), ptr(trans), ptr(err_lin), ptr(err), ptr(status),
+                                    stream_ptr(dev)), 'place_translation')
+    return out
+
+
+def project_points(points: torch.Tensor, trans: torch.Tensor, K: torch.Tensor, want_depth: bool = False, out=None):
+    """jrr_project_points: points (B,N,3) m, trans (B,3) float64, K (B,3,3) -> uv (B,N,2) pixels, NaN where Z + tz <= 0 (and, with
+    want_depth, depth (B,N) = Z + tz): the 17 joints and the 6890 vertices alike.  `out`: (uv, depth or None) to fill."""
+    lib = _lib.load()
+    B, N = int(points.shape[0]), int(points.shape[1])
+    dev = points.device
+    points, K = _check_f32(points, (B, N, 3)), _check_f32(K, (B, 3, 3), dev)
+    trans = trans.contiguous()
+    assert trans.shape == (B, 3) and trans.dtype == torch.float64 and trans.device == dev
+    if out is None:
+        out = (torch.empty(B, N, 2, device=dev), torch.empty(B, N, device=dev) if want_depth else None)
+    uv, depth = out
+    assert uv.shape == (B, N, 2) and uv.dtype == torch.float32 and uv.is_contiguous() and uv.device == dev
+    assert depth is None or (depth.shape == (B, N) and depth.dtype == torch.float32 and depth.is_contiguous() and depth.device == dev)
+    if B * N:
+        check(lib.jrr_project_points(ptr(points), ptr(trans), ptr(K), B, N, ptr(uv), ptr(depth), stream_ptr(dev)), 'project_points')
+    return out if want_depth or depth is not None else uv
+
+
+def place_accumulate(trans: torch.Tensor, err_lin: Optional[torch.Tensor], err: torch.Tensor, weight: Optional[torch.Tensor], status: torch.Tensor,
+                     group: Optional[torch.Tensor], n_groups: int, acc: torch.Tensor) -> None:
+    """jrr_place_accumulate: ADD the poses place_translation returned to rows `group` (B, int32; None: group 0) of the int64 table `acc`
+    (n_groups * 55 + 2 words, include/jrr.h JRR_PLACE_ACC_*)"""
+    lib = _lib.load()
+    B = int(err.shape[0])
+    dev = err.device
+    err = _check_f32(err, (B, 17))
+    err_lin = None if err_lin is None else _check_f32(err_lin, (B, 17), dev)
+    weight = None if weight is None else _check_f32(weight, (B, 17), dev)
+    trans, status = trans.contiguous(), status.contiguous()
+    assert trans.shape == (B, 3) and trans.dtype == torch.float64 and trans.device == dev
+    _check_ids(status, B, dev)
+    _check_acc(acc, n_groups, PLACE_ACC_ROW, PLACE_ACC_TRAILER, dev)
+    if group is not None:
+        group = group.contiguous()
+        _check_ids(group, B, dev)
+    if B == 0:
+        return
+    check(lib.jrr_place_accumulate(ptr(trans), ptr(err_lin), ptr(err), ptr(weight), ptr(status), ptr(group), B, int(n_groups), ptr(acc),
+                                   stream_ptr(dev)), 'place_accumulate')
+
+
 def project_joints(joints: torch.Tensor, cam: torch.Tensor) -> torch.Tensor:
     """return_2d_joints core (scripts/renderer.py:35-49): (B,17,3), (B,3) -> screen xy (B,17,2)"""
     lib = _lib.load()

@@ -32,6 +32,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import args as jargs
 from . import dist as jdist
 from . import eval_protocol
 from . import group_table
@@ -384,7 +385,7 @@ def evaluate_vertices(log=print) -> Optional[dict]:
             return shift_doc
     results = {k: r.finish() for k, r in reports.items()}
     entry = eval_protocol.document(protocol, gt_joints, JOINT_NAMES)
-    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', eval_protocol.flags_doc(penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(args._get()))))))), initial,
+    doc = write(args.eval_report, results, names, args.eval_groups, 'vertices', eval_protocol.flags_doc(penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(vertex_report.flags_doc(accel_report.flags_doc(jargs.recorded(args._get())))))))), initial,
                 retrained, entry)
     accel_doc = None
     if track is not None:      # every mesh is present and every rank knows it: the float all-reduce, the launches, the integer all-reduce

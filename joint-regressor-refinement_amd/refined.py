@@ -19,6 +19,10 @@ the rotations per run, the existing export writes the filtered records into a co
 reference camera, `relative_rotations` solves the 4x4 eigenproblems on the host, k_view_fuse averages the views of every frame (a
 medoid-trimmed quaternion mean per joint, the mean of the shapes), the existing export writes the fused records into a copy of the
 table, and `refined_fused.npz` holds every array of its input plus how far each view disagreed with the others.
+`place()` is `--place_refined PATH`: the table in the real camera.  The joints of every refined row (`_JointsOf`: the existing SMPL and
+find_joints operators under one regressor) against the split's full-frame 2-D joints under its intrinsics: k_place_translation
+(csrc/place.hip) solves the three-parameter least-squares problem per pose in fp64, k_place_accumulate fills the table of
+place_report.py, and `refined_placed.npz` holds every array of its input plus `trans`, the SMPL transl in the camera frame.
 """
 from __future__ import annotations
 
@@ -32,6 +36,7 @@ import torch
 
 from . import ci_report
 from . import eval_protocol
+from . import args as jargs
 from . import dist as jdist
 from .args import args
 
@@ -121,7 +126,7 @@ class RefinedExport:
     def finish(self):
         if self.table is None:
             raise RuntimeError('--save_refined: no batch was refined, there is nothing to save')
-        flags_doc = {k: v for k, v in eval_protocol.flags_doc(ci_report.flags_doc(args._get())).items() if isinstance(v, (bool, int, float, str, type(None))) and k not in ('eval_accel', 'regressor_report_depth', 'eval_bones', 'eval_penetration', 'eval_penetration_offset_mm')}
+        flags_doc = {k: v for k, v in eval_protocol.flags_doc(ci_report.flags_doc(jargs.recorded(args._get()))).items() if isinstance(v, (bool, int, float, str, type(None))) and k not in ('eval_accel', 'regressor_report_depth', 'eval_bones', 'eval_penetration', 'eval_penetration_offset_mm')}
         self.table.finish(self.directory, {'flags': flags_doc, 'body_model': self.body_model, 'j_regressor_sha256_16': self.j_hash,
                                            'inner_iters': int(args.inner_iters), 'data': 'dataset' if args.data_root else 'synthetic'})
 
@@ -331,41 +336,57 @@ def smooth(directory: str, paths, sigma: float = 2.0, radius: Optional[int] = No
     return out
 
 
+class _JointsOf:
+    """the 17 joints of table rows through the EXISTING operators: SMPL as the driver resolves it and RefineEngine.find_joints_forward
+    under ONE regressor (--eval_j_regressor, else the initial one) with the mask of the initial one.  Called with a table's arrays and
+    a chunk of row numbers; returns the (len(rows),17,3) device tensor, not pelvis-centred.  One engine per chunk size."""
+
+    def __init__(self, device):
+        from . import checkpoint, smpl_model, utils
+        from .smpl import SMPL
+        self.device = device
+        self.smpl = SMPL(args.smpl_dir, batch_size=1, allow_synthetic=args.synthetic or args.smpl_dir == 'SPIN/data/smpl').to(device)
+        J_np = smpl_model.default_h36m_regressor(args.j_regressor_init,
+                                                 allow_default=args.synthetic or args.j_regressor_init == 'SPIN/data/J_regressor_h36m.npy')
+        J_init = torch.from_numpy(J_np).float().to(device)
+        self.J = checkpoint.load_j_regressor(args.eval_j_regressor).float().to(device) if args.eval_j_regressor else J_init
+        self.mask = utils.find_j_reg_mask(J_init)
+        self.name = args.eval_j_regressor or args.j_regressor_init
+        self.engines: Dict[int, object] = {}
+
+    def __call__(self, arrays, rows) -> torch.Tensor:
+        from . import engine as _engine
+        B = int(len(rows))
+        if B not in self.engines:
+            self.engines[B] = _engine.RefineEngine(self.smpl.device_model, B)
+            self.engines[B].set_j_regressor(self.J, self.mask)
+        x6d = torch.from_numpy(arrays['pose6d'][rows]).to(self.device).float().contiguous()
+        betas = torch.from_numpy(arrays['shape'][rows]).to(self.device).float().contiguous()
+        return self.engines[B].find_joints_forward(betas, x6d=x6d)
+
+
 def _rescore_fn(gt_j3d_mm: torch.Tensor, device, tag: str = 'smooth', accel_paths=None):
     """the joint error of the raw and the smoothed (`tag`: the suffix of the second pair of names) rows through the EXISTING operators -- SMPL, find_joints, jrr_evaluate_joints -- in
     chunks of --batch_size under ONE regressor (--eval_j_regressor, else the initial one), the body as the driver resolves it.
     `accel_paths` (the split's frame paths, under --eval_accel): the joints of both passes are kept in device tables at their
     dataset indices, and jrr_accel_error gives accel_err_mm_raw / accel_err_mm_<tag> along the runs of the table's refined rows."""
-    from . import checkpoint, engine as _engine, smpl_model, utils
-    from .smpl import SMPL
+    from . import engine as _engine, utils
 
     def rescore(raw, smoothed):
-        smpl = SMPL(args.smpl_dir, batch_size=1, allow_synthetic=args.synthetic or args.smpl_dir == 'SPIN/data/smpl').to(device)
-        J_np = smpl_model.default_h36m_regressor(args.j_regressor_init,
-                                                 allow_default=args.synthetic or args.j_regressor_init == 'SPIN/data/J_regressor_h36m.npy')
-        J_init = torch.from_numpy(J_np).float().to(device)
-        J = checkpoint.load_j_regressor(args.eval_j_regressor).float().to(device) if args.eval_j_regressor else J_init
-        mask = utils.find_j_reg_mask(J_init)
+        joints_of = _JointsOf(device)
         rows = np.nonzero(raw['has_refined'])[0]
         N, bs = raw['has_refined'].shape[0], max(1, int(args.batch_size))
         acc = torch.full((4, N), float('nan'), device=device)
         kept = torch.zeros((3, N, 17, 3), device=device) if accel_paths is not None else None        # raw | processed | ground truth
-        engines: Dict[int, object] = {}
         with torch.no_grad():
             for a in range(0, rows.size, bs):
                 idx = torch.from_numpy(rows[a:a + bs])
-                B = int(idx.shape[0])
-                if B not in engines:
-                    engines[B] = _engine.RefineEngine(smpl.device_model, B)
-                    engines[B].set_j_regressor(J, mask)
                 gt = utils.move_pelvis(gt_j3d_mm[idx].to(device).float())
                 d_idx = idx.to(device)
                 if kept is not None:
                     kept[2, d_idx] = gt
                 for k, arrays in enumerate((raw, smoothed)):
-                    x6d = torch.from_numpy(arrays['pose6d'][rows[a:a + bs]]).to(device).float().contiguous()
-                    betas = torch.from_numpy(arrays['shape'][rows[a:a + bs]]).to(device).float().contiguous()
-                    joints = engines[B].find_joints_forward(betas, x6d=x6d)
+                    joints = joints_of(arrays, rows[a:a + bs])
                     err_j, err_pa_j = _engine.evaluate_joints(joints.float().contiguous(), gt.contiguous())
                     acc[2 * k, d_idx] = err_j.mean(1) * 1000
                     acc[2 * k + 1, d_idx] = err_pa_j.mean(1) * 1000
@@ -629,4 +650,134 @@ def fuse_command(log=print) -> Optional[dict]:
         f'{fmt(doc["fuse_delta_orient_deg_mean"])} deg, dropped {fmt(doc["dropped_share"])}, MPJPE {fmt(doc["mpjpe_eval_mm_raw_mean"])} -> '
         f'{fmt(doc["mpjpe_eval_mm_fused_mean"])}, PAMPJPE {fmt(doc["pampjpe_eval_mm_raw_mean"])} -> {fmt(doc["pampjpe_eval_mm_fused_mean"])}{accel}; '
         f'{os.path.join(directory, FUSE_NAME)}')
+    return out
+
+
+# ---- in the real camera (`--place_refined`) -----------------------------------------------------------------------------------
+PLACE_NAME = 'refined_placed.npz'
+PLACE_MAX_ITERS = 64          # include/jrr.h: JRR_PLACE_MAX_ITERS
+
+
+def place(directory_or_npz: str, intrinsics, gt_j2d, paths, joints_of, n_iters: int = 10, weights=None, weights_name: Optional[str] = None,
+          batch_size: int = 256, group_kind: str = 'action', gt_j3d_mm=None, device=None) -> Dict[str, np.ndarray]:
+    """`--place_refined PATH`: the camera-frame translation of every refined row of DIR/refined.npz -- or of the named `.npz` of its
+    directory, as load_path reads it -- under the split's real intrinsics (N,3,3) and FULL-FRAME 2-D joints gt_j2d (N,17,2).
+    `joints_of(arrays, rows)` gives the (len(rows),17,3) joints of table rows on the device (_JointsOf).  Per chunk of `batch_size`
+    rows: jrr_place_translation twice (0 steps: the linear start; n_iters steps: the result) and jrr_place_accumulate into the table of
+    place_report by the groups of `paths` (None: one group); then the table and everything per pose are read back once each.  Writes
+    DIR/refined_placed.npz -- every array of the input unchanged + trans / trans_linear (N,3) float64 m, reproj_px / reproj_px_linear
+    (N,17) float32, NaN on rows without a refined pose, and place_status (N,) int32, -1 there --, DIR/place.json, DIR/place.md and the
+    entry `place` of DIR/meta.json; the input file is not rewritten.  weights (N,17) or None: ones.  gt_j3d_mm (N,17,3): when some row's
+    pelvis lies further than 1 mm from the origin the ground truth is in the camera frame, and the distance of the placed pelvis from
+    the measured one is reported as root_err_mm; otherwise the key is absent.  Returns the arrays."""
+    from . import engine as _engine, eval_report, place_report
+    n_iters = int(n_iters)
+    if not 0 <= n_iters <= PLACE_MAX_ITERS:
+        raise ValueError(f'place: n_iters {n_iters}: 0 .. {PLACE_MAX_ITERS}')
+    directory = (os.path.dirname(directory_or_npz) or '.') if str(directory_or_npz).endswith('.npz') else directory_or_npz
+    raw = load_path(directory_or_npz)
+    meta = raw.pop('meta')
+    N = raw['has_refined'].shape[0]
+    as_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    intrinsics, gt_j2d = as_t(intrinsics).float(), as_t(gt_j2d).float()
+    for name, t, shape in (('intrinsics', intrinsics, (N, 3, 3)), ('gt_j2d', gt_j2d, (N, 17, 2))) + \
+            ((('weights', as_t(weights), (N, 17)),) if weights is not None else ()) + \
+            ((('gt_j3d', as_t(gt_j3d_mm), (N, 17, 3)),) if gt_j3d_mm is not None else ()):
+        if tuple(t.shape) != shape:
+            raise ValueError(f'place: {name} should be {shape} for a table of {N} samples, is {tuple(t.shape)}')
+    weights = None if weights is None else as_t(weights).float()
+    names, gid = eval_report.assign_groups(paths, group_kind, n=N)
+    if gid.shape[0] != N:
+        raise ValueError(f'place: {gid.shape[0]} paths for a table of {N} rows')
+    G = len(names)
+    device = torch.device(args.device if device is None else device)
+    rows = np.nonzero(raw['has_refined'])[0]
+    M, bs = int(rows.size), max(1, int(batch_size))
+    root_err = gt_j3d_mm is not None and bool((as_t(gt_j3d_mm).float()[:, 0].norm(dim=1) > 1.0).any())
+    trans, trans_lin = (torch.full((M, 3), float('nan'), dtype=torch.float64, device=device) for _ in range(2))
+    err, err_lin = (torch.full((M, 17), float('nan'), device=device) for _ in range(2))
+    status, status_lin = (torch.full((M,), -1, dtype=torch.int32, device=device) for _ in range(2))
+    root = torch.full((M,), float('nan'), dtype=torch.float64, device=device)
+    acc = torch.zeros(G * place_report.ROW + place_report.TRAILER, dtype=torch.int64, device=device)
+    with torch.no_grad():
+        for a in range(0, M, bs):
+            idx = torch.from_numpy(rows[a:a + bs])
+            s = slice(a, a + int(idx.shape[0]))
+            joints = joints_of(raw, rows[a:a + bs]).float().contiguous()
+            K, j2d = intrinsics[idx].to(device).contiguous(), gt_j2d[idx].to(device).contiguous()
+            w = None if weights is None else weights[idx].to(device).contiguous()
+            _engine.place_translation(joints, j2d, K, w, 0, out=(trans_lin[s], None, err_lin[s], status_lin[s]))
+            _engine.place_translation(joints, j2d, K, w, n_iters, out=(trans[s], None, err[s], status[s]))
+            _engine.place_accumulate(trans[s], err_lin[s], err[s], w, status[s], torch.from_numpy(gid[rows[a:a + bs]]).to(device), G, acc)
+            if root_err:
+                root[s] = (trans[s] + joints[:, 0].double() - as_t(gt_j3d_mm)[idx][:, 0].to(device).double() / 1000).norm(dim=1) * 1000
+    table = place_report.derive(acc.cpu().numpy(), names)                     # the table ...
+    flat = torch.cat([trans.reshape(-1), trans_lin.reshape(-1), err.double().reshape(-1), err_lin.double().reshape(-1), status.double(),
+                      root]).cpu().numpy()                                    # ... and everything per pose: the two read-backs
+    cut = np.cumsum([0, 3 * M, 3 * M, 17 * M, 17 * M, M, M])
+    h_trans, h_lin, h_err, h_err_lin, h_status, h_root = (flat[cut[k]:cut[k + 1]] for k in range(6))
+    out = dict(raw)
+    out['trans'], out['trans_linear'] = np.full((N, 3), np.nan), np.full((N, 3), np.nan)
+    out['reproj_px'], out['reproj_px_linear'] = np.full((N, 17), np.nan, np.float32), np.full((N, 17), np.nan, np.float32)
+    out['place_status'] = np.full(N, -1, np.int32)
+    out['trans'][rows], out['trans_linear'][rows] = h_trans.reshape(M, 3), h_lin.reshape(M, 3)
+    out['reproj_px'][rows], out['reproj_px_linear'][rows] = h_err.reshape(M, 17).astype(np.float32), h_err_lin.reshape(M, 17).astype(np.float32)
+    out['place_status'][rows] = h_status.astype(np.int32)
+    st = out['place_status'][rows]
+    good = (st & place_report.BAD_BITS) == 0
+    part = np.ones((M, 17), bool) if weights is None else (np.isfinite(weights.numpy()[rows]) & (weights.numpy()[rows] > 0))
+    per_pose = np.array([h_err.reshape(M, 17)[i][part[i]].mean() for i in np.nonzero(good)[0]], dtype=np.float64)
+    pose_error = {'n': int(per_pose.size), 'median': float(np.median(per_pose)) if per_pose.size else None,
+                  'p95': float(np.percentile(per_pose, 95)) if per_pose.size else None}
+    if root_err:
+        out['root_err_mm'] = np.full(N, np.nan)
+        out['root_err_mm'][rows] = h_root
+        g_rows = gid[rows]
+        for k, name in enumerate(names):
+            table['groups'][name]['root_err_mm'] = _nanmean(h_root[good & (g_rows == k)])
+        table[place_report.ALL]['root_err_mm'] = _nanmean(h_root[good])
+    counts = {str(bit): int(((st & bit) != 0).sum()) for bit in place_report.STATUS_BITS}
+    np.savez(os.path.join(directory, PLACE_NAME), **out)
+    doc = place_report.write(directory, table, names, group_kind, n_iters, getattr(joints_of, 'name', None), weights_name, pose_error, counts, root_err)
+    entry = {'source': os.path.basename(str(directory_or_npz)) if str(directory_or_npz).endswith('.npz') else 'refined.npz', 'placed': int(good.sum()),
+             'rows': M, 'n_iters': n_iters, 'j_regressor': getattr(joints_of, 'name', None), 'weights': weights_name, 'status_counts': counts,
+             'reproj_px_linear_mean': table[place_report.ALL]['reproj_linear_px'], 'reproj_px_mean': table[place_report.ALL]['reproj_px'],
+             'pose_error_px': pose_error, 'depth_m_mean': table[place_report.ALL]['depth_m']}
+    with open(os.path.join(directory, 'meta.json'), 'w') as f:
+        json.dump(dict(meta, place=entry), f, indent=1, sort_keys=True, default=str)
+    out['meta'] = dict(meta, place=entry)
+    out['report'] = doc
+    return out
+
+
+def place_command(log=print) -> Optional[dict]:
+    """`python main.py --place_refined PATH --data_root ROOT [--place_iters 10] [--place_weights FILE.npy] [--eval_j_regressor CKPT]`:
+    refined.place on the split the table was written from -- its intrinsics and its full-frame gt_j2d, the groups of --eval_groups from
+    its images.pkl.  One process: under torchrun rank 0 works and the other ranks return.  Prints one summary line."""
+    from . import data as jdata, place_report
+    if jdist.env_rank_world()[0] != 0:                      # the command joins no process group: the launcher's rank decides
+        return None
+    if not args.data_root:
+        raise ValueError('--place_refined needs --data_root (the intrinsics and the 2-D joints of the split the table was written from)')
+    if not 0 <= int(args.place_iters) <= PLACE_MAX_ITERS:
+        raise ValueError(f'--place_iters {args.place_iters}: 0 .. {PLACE_MAX_ITERS}')
+    location = jdata.split_location('validation', args.data_root)
+    paths = jdata.split_image_paths(location)
+    if paths is None:
+        raise FileNotFoundError(f'--place_refined: {os.path.join(location, "images.pkl")} is missing: the frame paths say which group a sample belongs to')
+    ds = jdata.data_set('validation', root=args.data_root)
+    n_table = load_path(args.place_refined)['has_refined'].shape[0]
+    if not (len(paths) == len(ds) == n_table):
+        raise ValueError(f'--place_refined: the table holds {n_table} samples, the split {len(ds)} with {len(paths)} frame paths')
+    weights = None
+    if args.place_weights:
+        weights = np.load(args.place_weights, allow_pickle=False)
+        if weights.shape != (n_table, 17):
+            raise ValueError(f'--place_weights {args.place_weights}: ({n_table}, 17) expected, got {weights.shape}')
+    device = torch.device(args.device)
+    torch.cuda.set_device(device)
+    out = place(args.place_refined, ds.intrinsics, ds.gt_j2d, paths, _JointsOf(device), n_iters=args.place_iters, weights=weights,
+                weights_name=args.place_weights, batch_size=args.batch_size, group_kind=args.eval_groups, gt_j3d_mm=ds.gt_j3d, device=device)
+    directory = (os.path.dirname(args.place_refined) or '.') if str(args.place_refined).endswith('.npz') else args.place_refined
+    log(place_report.summary_line(out['report']) + f'; {os.path.join(directory, PLACE_NAME)}')
     return out

@@ -25,6 +25,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import args as jargs
 from . import dist as jdist
 
 LAYOUT_VERSION = 1
@@ -168,7 +169,7 @@ def build_doc(source: str, flags: dict, n_train: int, n_holdout: int, support_be
 
 def flags_doc(ns) -> dict:
     from . import bones_report, ci_report, eval_protocol, penetration_report, regressor_report
-    return {k: v for k, v in eval_protocol.flags_doc(penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(ns))))).items() if isinstance(v, (bool, int, float, str, type(None)))}
+    return {k: v for k, v in eval_protocol.flags_doc(penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(jargs.recorded(ns)))))).items() if isinstance(v, (bool, int, float, str, type(None)))}
 
 
 # ---- the sources ---------------------------------------------------------------------------------------------------------------

@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import bones_report, ci_report, eval_protocol, penetration_report
+from . import args as jargs
 from . import group_table
 from .eval_report import JOINT_NAMES, sha16
 from .group_table import ALL, fmt as _f, rank as _rank
@@ -587,7 +588,7 @@ class Run:
                 for i in range(n_pose):
                     _report.write_png(os.path.join(d, f'pose_{i:05d}.png'), p[i])
             pictures = f'{NJ} weight pictures, {n_pose} pose pictures, {pics.size} x {2 * pics.size}'
-        doc = write(d, data, joints, self.names, self.source, eval_protocol.flags_doc(penetration_report.flags_doc(bones_report.flags_doc(flags_doc(ci_report.flags_doc(self.ns))))), initial, retrained, pictures,
+        doc = write(d, data, joints, self.names, self.source, eval_protocol.flags_doc(penetration_report.flags_doc(bones_report.flags_doc(flags_doc(ci_report.flags_doc(jargs.recorded(self.ns)))))), initial, retrained, pictures,
                     None if model_np is None else str(model_np.get('provenance', 'caller-supplied arrays')))
         log(f'regressor report: {os.path.join(d, "regressor.md")}')
         return doc

@@ -19,6 +19,7 @@ from typing import Dict, Optional
 import torch
 
 from . import accel_report, batches, bones_report, checkpoint, ci_report, engine as _engine, eval_protocol, eval_report, penetration_report, regressor_report, smpl_model, utils
+from . import args as jargs
 from .args import args
 from .smpl import SMPL
 
@@ -177,7 +178,7 @@ def test_pose_refiner_model(retrained_path: Optional[str] = None, log=print) -> 
     if reports is not None:    # this function runs in ONE process (main.py: rank 0) on whole batches: nothing to reduce
         results = {k: r.finish(reduce=False) for k, r in reports.items()}
         rep['eval_report'] = eval_report.write(args.eval_report, results, names, args.eval_groups if group_ids is not None else 'none', 'parameters',
-                                               eval_protocol.flags_doc(penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(accel_report.flags_doc(args._get())))))), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
+                                               eval_protocol.flags_doc(penetration_report.flags_doc(bones_report.flags_doc(regressor_report.flags_doc(ci_report.flags_doc(accel_report.flags_doc(jargs.recorded(args._get()))))))), (args.j_regressor_init, eval_report.sha16(args.j_regressor_init, J_np)),
                                                (path, eval_report.sha16(path)), eval_protocol.document(protocol, 'file', eval_report.JOINT_NAMES))
     if track is not None:      # one launch per regressor over the whole split's time order, one read-back
         rep['accel_report'] = accel_report.write(args.eval_report, track.finish(accel_paths, group_ids, names, ('before', 'after'), reduce=False),

@@ -7,7 +7,8 @@ main.py:26-27) need the external VIBE / MEVA checkouts: the networks are out of 
 networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evaluate_vertices), which runs alone and exits.
 `--regressor_report DIR` (regressor_report.py) adds to either evaluation what the retrained regressor did to each joint, with pictures.
 `--smooth_refined DIR` (refined.smooth_command) filters a `--save_refined` table along time and exits as well;
-`--fuse_refined DIR` (refined.fuse_command) fuses its camera views of each frame and exits.
+`--fuse_refined DIR` (refined.fuse_command) fuses its camera views of each frame and exits;
+`--place_refined PATH` (refined.place_command) gives every refined pose its translation in the real camera and exits.
 `--fit_regressor OUT --fit_from PATH` (regressor_fit.py) fits the regressor on a table of fixed meshes and exits; with `--fit_solve`
 (regressor_solve.py) it solves that fit exactly from the table's second moments instead of taking Adam epochs.
 `--eval_accel` (accel_report.py) adds the acceleration error along each video sequence to the evaluations and to those two commands.
@@ -58,6 +59,9 @@ if __name__ == '__main__':
         sys.exit(0)
     if args.fuse_refined:                                                    # ... across the camera views of each frame; no training
         importlib.import_module(PKG + '.refined').fuse_command()
+        sys.exit(0)
+    if args.place_refined:                                                   # ... into the real camera of each sample; no training
+        importlib.import_module(PKG + '.refined').place_command()
         sys.exit(0)
     res = optimize.optimize_pose_refiner()                                   # main.py:23
     if args.save_refined and int(os.environ.get('RANK', '0')) == 0:

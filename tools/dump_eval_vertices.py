@@ -15,7 +15,10 @@ regressors on them.  The arrays are written through numpy's open_memmap, batch b
 `--gt_refined PATH` (a `--save_refined` directory, or one of its .npz tables: the smoothed or the fused one) also writes
 OUT_DIR/gt_vertices.npy (N,6890,3) float32 metres for `--eval_pve`: the SMPL forward of `pose6d` / `shape` of the table's row at each
 emitted sample's dataset index.  Samples whose row holds no refined pose (has_refined == 0) are dropped from EVERY file, so the files
-keep the same rows."""
+keep the same rows.
+
+`--placed` (with `--gt_refined PATH/refined_placed.npz`, the table `--place_refined` wrote): also OUT_DIR/trans.npy (N,3) float64 metres, the
+camera-frame translation of each emitted sample -- vertices + trans stand in the sample's real camera.  Every other file keeps its bytes."""
 import importlib
 import os
 import sys
@@ -37,6 +40,11 @@ def main(argv):
             raise SystemExit('--gt_refined needs a path')
         gt_refined = flags[at + 1]
         del flags[at:at + 2]
+    placed = '--placed' in flags
+    if placed:
+        flags.remove('--placed')
+        if gt_refined is None:
+            raise SystemExit('--placed needs --gt_refined PATH: the table that holds trans')
     argsmod = importlib.import_module(PKG + '.args')
     argsmod._LazyArgs._ns = argsmod.get_args(flags)
     args = argsmod.args
@@ -56,7 +64,9 @@ def main(argv):
         if not args.data_root:
             raise SystemExit('--gt_refined needs --data_root: the table\'s rows are dataset indices')
         table = importlib.import_module(PKG + '.refined').load_path(gt_refined)
-    verts, gts, kept, gt_verts = [], [], [], []
+        if placed and 'trans' not in table:
+            raise SystemExit(f'--placed: {gt_refined} holds no trans (python main.py --place_refined writes refined_placed.npz)')
+    verts, gts, kept, gt_verts, trans = [], [], [], [], []
     engines = {}
     with torch.no_grad():
         for batch in evaluation.validation_batches(smpl.model_np, J_np, device, with_index=paths is not None or table is not None):
@@ -76,6 +86,8 @@ def main(argv):
                 has = table['has_refined'][index].astype(bool)
                 v, gt, index = v[has], gt[has], index[has]
                 gt_verts.append(g.cpu().numpy()[has])
+                if placed:
+                    trans.append(table['trans'][index])
             verts.append(v)
             gts.append(gt)
             if paths is not None:
@@ -95,6 +107,8 @@ def main(argv):
         vm.flush()
         del vm
     np.save(os.path.join(out, 'gt_j3d.npy'), np.concatenate(gts).astype(np.float32))
+    if placed:
+        np.save(os.path.join(out, 'trans.npy'), np.concatenate(trans).astype(np.float64))
     if paths is not None:
         with open(os.path.join(out, 'paths.txt'), 'w') as f:
             f.write(''.join(p + '\n' for p in kept))
