@@ -302,6 +302,34 @@ enum {
   JRR_PLACE_ACC_TRAILER = 2         /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
 };
 
+/* jrr_point_visibility / jrr_visibility_accumulate (`--visible_refined`): what the real camera sees of a placed body.  The bits of a
+ * query's code, and the table: JRR_VIS_ACC_ROW int64 per group, offsets in int64, then the trailer of the evaluation table behind the
+ * last row.  Layout version 1.
+ * Overflow: an error below the cap 1.0e5f mm gives llrintf(e * 2^24) < 2^41, so a SUM_ERR word stays below 2^63 for 4e6 poses. */
+enum {
+  JRR_VIS_ACC_LAYOUT_VERSION = 1,
+  JRR_VIS_MAX_POINTS = 65536,       /* queries per pose of one call; vertices per pose of jrr_visibility_accumulate */
+  JRR_VIS_JOINTS = 17,
+  JRR_VIS_OCCLUDED = 1,             /* code bit 0: at least min_crossings faces cross the ray in front of the query */
+  JRR_VIS_OUTSIDE = 2,              /* code bit 1: the pixel lies outside the window */
+  JRR_VIS_INVALID = 4,              /* code bit 2: depth <= 0 or a non-finite coordinate; bits 0 and 1 are then clear */
+  JRR_VIS_ACC_ROW = 154,
+  JRR_VIS_ACC_COUNT = 0,            /* poses counted */
+  JRR_VIS_ACC_BAD = 1,              /* poses of this group left out whole (see jrr_visibility_accumulate) */
+  JRR_VIS_ACC_SUM_VERT_SEEN = 2,    /* vertices of the counted poses with code 0 */
+  JRR_VIS_ACC_SUM_VERT_OCCLUDED = 3,/* ... with bit 0 */
+  JRR_VIS_ACC_SUM_VERT_OUTSIDE = 4, /* ... with bit 1 (a vertex with both bits counts in both words) */
+  JRR_VIS_ACC_J_SEEN = 5,           /* 17: counted poses in which joint j has code 0 */
+  JRR_VIS_ACC_J_OCCLUDED = 22,      /* 17: ... bit 0 set and bit 1 clear */
+  JRR_VIS_ACC_J_OUTSIDE = 39,       /* 17: ... bit 1 set */
+  JRR_VIS_ACC_SUM_ERR_SEEN = 56,    /* 17: sum over the poses of J_SEEN of llrintf(err_j * 2^24) (units of 2^-24 mm) */
+  JRR_VIS_ACC_SUM_ERR_OCCLUDED = 73,/* 17: the same over the poses of J_OCCLUDED */
+  JRR_VIS_ACC_PART_SEEN = 90,       /* [32]: vertices with code 0 by part[v]; a label outside [0, 32) goes to word 31, NULL parts to word 0 */
+  JRR_VIS_ACC_PART_ALL = 122,       /* [32]: all vertices of the counted poses by part[v] */
+  JRR_VIS_ACC_PARTS = 32,
+  JRR_VIS_ACC_TRAILER = 2           /* JRR_EVAL_ACC_TRAILER_IGNORED, JRR_EVAL_ACC_TRAILER_BAD_GROUP */
+};
+
 /* The paired bootstrap of the evaluation report (`--eval_ci`): jrr_paired_units fills two int64 tables, jrr_bootstrap_sums resamples
  * the first.  Layout version 1.
  *   units  [n_units][JRR_BOOT_UNIT_ROW]: per resampling unit (a video sequence, or a frame) the sums over its counted poses.
@@ -1110,6 +1138,50 @@ int jrr_project_points(const float* points_dev, const double* trans_dev, const f
  * or acc_dev not 8-byte or another array not 4-byte aligned.                                                                       */
 int jrr_place_accumulate(const double* trans_dev, const float* err_lin_dev, const float* err_dev, const float* weight_dev,
                          const int32_t* status_dev, const int32_t* group_dev, int batch, int n_groups, int64_t* acc_dev, void* stream);
+
+/* ---- what the real camera sees of a placed body (`--visible_refined`) ------------------------------
+ * jrr_point_visibility: verts_cam_dev (B,n_verts,3) fp32, camera-frame metres (the caller has added the translation), with the
+ * triangles faces_dev (n_faces,3) int32 the poses share.  The queries are points_cam_dev (B,n_points,3) fp32, or -- NULL, and then
+ * n_points == n_verts -- the pose's own vertices, and for query i every face that names vertex i is skipped.  For a query p with depth
+ * d = p_z and a face with corners a, b, c: the ray from the camera centre 0 to p meets the face's plane at s p, with barycentrics
+ * lambda0, lambda1, lambda2 that sum to 1; the face CROSSES IN FRONT when min lambda >= 0, s > 0 and s d < d - margin_m.
+ *   count   the number of such faces.  A face adds nothing when a corner is not finite, when (b - a) x (c - a) is zero in fp32, or
+ *           when its plane passes through the camera centre.  A face with an index outside [0, n_verts) adds nothing and sets bit 0
+ *           (JRR_DEPTH_STATUS_INDEX) of status_dev[0], which the caller zeroes; the other faces are counted.
+ *   code    bit 0 (JRR_VIS_OCCLUDED): count >= min_crossings (1 for a vertex; 2 for an interior point such as a regressed joint,
+ *           whose first crossing is its own skin);
+ *           bit 1 (JRR_VIS_OUTSIDE): K_dev (B,3,3) and rect_dev (B,4) = [x0,y0,x1,y1] pixels are given (both or neither) and
+ *           x0 <= u < x1, y0 <= v < y1 fails for the pixel u = (fx * X) / d + cx, v = (fy * Y) / d + cy of jrr_project_points: fp32,
+ *           each operation rounded once, no contraction -- bit-exact against a float32 restatement; a NaN in K or rect fails it;
+ *           bit 2 (JRR_VIS_INVALID): d <= 0 or a coordinate of p is not finite; count is then 0 and bits 0 and 1 stay clear.
+ * The intersection is done in 3-D in fp32 on differences (Moeller-Trumbore with origin 0: e1 = b - a, e2 = c - a, h = p x e2,
+ * det = e1 . h, lambda1 det = -(a . h), q = e1 x a, lambda2 det = p . q, s det = e2 . q; signs are compared against det, nothing is
+ * divided), so a face that straddles Z = 0 is no special case.  A pair closer than about 3e-4 to an edge in a barycentric, or than
+ * fp32 rounding of the depths to the margin, may fall either way; everywhere else count is the exact one.  One query per lane,
+ * integer counts, no cross-lane step: a query's result depends on its pose alone -- not on the batch, its column or the launch.
+ * count_dev (B,n_points) int32 or NULL, code_dev (B,n_points) uint8.  batch == 0 or n_points == 0 returns JRR_OK without a launch;
+ * JRR_ERR_ARG with a message, no launch and nothing written: a NULL verts_cam_dev, faces_dev, code_dev or status_dev, batch < 0,
+ * n_verts < 1, n_faces < 0, n_points < 0 or > JRR_VIS_MAX_POINTS, points NULL with n_points != n_verts, one of K_dev / rect_dev
+ * without the other, an array other than code_dev not 4-byte aligned, margin_m not finite or < 0, min_crossings outside 1 .. 255.  */
+int jrr_point_visibility(const float* verts_cam_dev, int batch, int n_verts, const int32_t* faces_dev, int n_faces, const float* points_cam_dev,
+                         int n_points, const float* K_dev, const float* rect_dev, float margin_m, int min_crossings, int32_t* count_dev,
+                         uint8_t* code_dev, int32_t* status_dev, void* stream);
+/* jrr_visibility_accumulate ADDS the poses to rows group_dev[b] of acc_dev: int64 [n_groups][JRR_VIS_ACC_ROW] + JRR_VIS_ACC_TRAILER
+ * words, layout above; the caller zeroes it once per report.  vert_code_dev (B,n_verts) and joint_code_dev (B,17) uint8 as
+ * jrr_point_visibility wrote them; err_j_dev (B,17) fp32 mm or NULL (the SUM_ERR words stay as they are); part_dev (n_verts) int32 or
+ * NULL (every vertex in part 0); pose_status_dev (B) int32 or NULL: the status of jrr_place_translation; group_dev NULL: every pose in
+ * group 0; per_vertex_dev (n_verts) int64 or NULL.  A pose adds to exactly one class of words:  group < 0: trailer word 0 only;
+ * group >= n_groups: trailer word 1 only;  BAD += 1 only, when its pose_status has one of the bits JRR_PLACE_BAD_BITS, when one of
+ * its n_verts + 17 codes has a bit other than bits 0 and 1 set, or when one of its 17 errors fails e < 1.0e5f (NaN, infinite,
+ * absurd);  otherwise COUNT += 1, the three SUM_VERT words, per joint J_SEEN / J_OCCLUDED / J_OUTSIDE and SUM_ERR_SEEN /
+ * SUM_ERR_OCCLUDED += fixed24(err_j) = llrintf(err_j * 2^24), PART_ALL[part[v]] += 1 for every vertex and PART_SEEN[part[v]] += 1
+ * and per_vertex_dev[v] += 1 for every vertex with code 0.  Integer atomics only: the tables are a function of the multiset of poses
+ * -- not of the order, the split into calls or the sharding over ranks.  batch == 0 returns JRR_OK without a launch; JRR_ERR_ARG with
+ * a message for a NULL vert_code_dev, joint_code_dev or acc_dev, batch < 0, n_groups out of range, n_verts outside
+ * 1 .. JRR_VIS_MAX_POINTS, acc_dev or per_vertex_dev not 8-byte or another int32 / fp32 array not 4-byte aligned.                    */
+int jrr_visibility_accumulate(const uint8_t* vert_code_dev, const uint8_t* joint_code_dev, const float* err_j_dev, const int32_t* part_dev,
+                              const int32_t* pose_status_dev, const int32_t* group_dev, int batch, int n_verts, int n_groups, int64_t* acc_dev,
+                              int64_t* per_vertex_dev, void* stream);
 
 /* ---- 2-D reprojection --------------------------------------------
  * return_2d_joints core, scripts/renderer.py:35-49 (pytorch3d 0.3.0 PerspectiveCameras, R = I,

@@ -94,6 +94,8 @@ SIGNATURES = {
     'jrr_place_translation': (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, _P, _P]),
     'jrr_project_points': (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P]),
     'jrr_place_accumulate': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, _P]),
+    'jrr_point_visibility': (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, _P, _P, c_float, c_int, _P, _P, _P, _P]),
+    'jrr_visibility_accumulate': (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     'jrr_project_joints': (c_int, [_P, _P, _P, c_int, _P]),
     'jrr_engine_set_reprojection': (c_int, [_P, _P, _P, _P, _P]),
     'jrr_camera_prefit': (c_int, [_P, _P, _P, _P, _P, c_int, c_float, _P, _P]),

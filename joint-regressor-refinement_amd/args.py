@@ -88,6 +88,19 @@ def build_parser() -> argparse.ArgumentParser:
                         help='--place_refined: Levenberg-Marquardt steps on the pixel error behind the linear start, 0 .. 64')
     parser.add_argument('--place_weights', type=str, default=None, metavar='FILE.npy',
                         help='--place_refined: per-joint weights (N,17); a joint takes part when its weight is finite and > 0 (default: ones)')
+    parser.add_argument('--visible_refined', type=str, default=None, metavar='PATH',
+                        help='with --data_root: what the real camera sees of every placed pose of DIR/refined_placed.npz (PATH: that file or its '
+                             'directory; --place_refined writes it) -- per vertex and per regressed joint (--eval_j_regressor, else the initial '
+                             'regressor) whether the body itself hides it or it lies outside the window; write DIR/vertex_visibility.npy, '
+                             'DIR/refined_visible.npz, DIR/visible.json, DIR/visible.md and DIR/visible_per_vertex.npy, print one line and exit '
+                             '(refined.visible)')
+    parser.add_argument('--visible_margin_mm', type=float, default=5.0,
+                        help='--visible_refined: a face hides a point when it crosses the ray from the camera centre more than this in front of it')
+    parser.add_argument('--visible_window', type=str, default='frame', choices=['frame', 'crop'],
+                        help='--visible_refined: outside means outside the frame (--visible_frame) or outside the square find_crop cuts from the '
+                             'sample\'s bounding box')
+    parser.add_argument('--visible_frame', type=int, nargs=2, default=[1000, 1000], metavar=('W', 'H'),
+                        help='--visible_refined --visible_window frame: the size of the frame in pixels')
     parser.add_argument('--smooth_sigma', type=float, default=2.0, help='--smooth_refined: standard deviation of the Gaussian, in sampled frames')
     parser.add_argument('--smooth_radius', type=int, default=None,
                         help='--smooth_refined: the window reaches this many frames to either side, 0 .. 16 (default: min(16, ceil(3 sigma)))')

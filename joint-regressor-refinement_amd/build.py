@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'build')
 LIB = os.path.join(HERE, 'libjrr_hip.so')
-SOURCES = ['api.hip', 'model.hip', 'refine.hip', 'rot.hip', 'chain.hip', 'loss.hip', 'flat.hip', 'lbs_fwd.hip', 'lbs_bwd.hip', 'jreg.hip', 'gemm.hip', 'disc.hip', 'eval.hip', 'fold.hip', 'sil.hip', 'sup.hip', 'image.hip', 'report.hip', 'shade.hip', 'export.hip', 'evalrep.hip', 'evalproto.hip', 'smooth.hip', 'regrep.hip', 'views.hip', 'accel.hip', 'pve.hip', 'jfit.hip', 'jmom.hip', 'jnorm.hip', 'boot.hip', 'jprice.hip', 'depth.hip', 'bones.hip', 'pen.hip', 'place.hip']
+SOURCES = ['api.hip', 'model.hip', 'refine.hip', 'rot.hip', 'chain.hip', 'loss.hip', 'flat.hip', 'lbs_fwd.hip', 'lbs_bwd.hip', 'jreg.hip', 'gemm.hip', 'disc.hip', 'eval.hip', 'fold.hip', 'sil.hip', 'sup.hip', 'image.hip', 'report.hip', 'shade.hip', 'export.hip', 'evalrep.hip', 'evalproto.hip', 'smooth.hip', 'regrep.hip', 'views.hip', 'accel.hip', 'pve.hip', 'jfit.hip', 'jmom.hip', 'jnorm.hip', 'boot.hip', 'jprice.hip', 'depth.hip', 'bones.hip', 'pen.hip', 'place.hip', 'vis.hip']
 HEADERS = ['jrr_common.h', 'kernels.h', 'lbs_tile.h', 'engine.h', 'engine_state.h','dconv.h', 'supk.h', 'chaink.h', 'proj.h', 'rot6.h', 'quat.h', 'evalk.h', 'procfit.h', 'jfitk.h', 'fixedpt.h', 'acctab.h', os.path.join('..', '..', 'include', 'jrr.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function']
 

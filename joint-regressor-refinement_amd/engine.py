@@ -1356,6 +1356,77 @@ def place_accumulate(trans: torch.Tensor, err_lin: Optional[torch.Tensor], err: 
                                    stream_ptr(dev)), 'place_accumulate')
 
 
+VIS_ACC_ROW, VIS_ACC_TRAILER, VIS_MAX_POINTS = 154, 2, 65536      # include/jrr.h: JRR_VIS_ACC_ROW, JRR_VIS_ACC_TRAILER, JRR_VIS_MAX_POINTS
+VIS_OCCLUDED, VIS_OUTSIDE, VIS_INVALID = 1, 2, 4                  # JRR_VIS_*: the bits of a code
+
+
+def point_visibility(verts_cam: torch.Tensor, faces: torch.Tensor, points_cam: Optional[torch.Tensor], K: Optional[torch.Tensor],
+                     rect: Optional[torch.Tensor], margin_m: float, min_crossings: int, status: torch.Tensor, want_count: bool = True, out=None):
+    """jrr_point_visibility: per query the number of faces of the pose's own mesh -- verts_cam (B,n_verts,3) float32, camera-frame
+    metres, with the triangles faces (n_faces,3) int32 -- that cross the ray from the camera centre at least margin_m in front of it,
+    and its code (bit 0: count >= min_crossings, bit 1: the pixel under K (B,3,3) lies outside rect (B,4) = [x0,y0,x1,y1], bit 2:
+    depth <= 0 or not finite).  points_cam (B,n_points,3), or None: the vertices themselves, the faces that name a query skipped.
+    K and rect: both or neither.  status: one zeroed int32 word on the device, bit 0 for a face index out of range.
+    -> (count (B,n_points) int32 or None, code (B,n_points) uint8); `out`: the two to fill.  One launch, nothing read back."""
+    lib = _lib.load()
+    if not (torch.is_tensor(verts_cam) and verts_cam.dim() == 3 and verts_cam.shape[2] == 3 and verts_cam.dtype == torch.float32 and verts_cam.is_cuda):
+        raise ValueError('point_visibility: verts_cam must be a float32 device tensor (B,n_verts,3)')
+    dev, B, n_verts = verts_cam.device, int(verts_cam.shape[0]), int(verts_cam.shape[1])
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32 or faces.device != dev:
+        raise ValueError(f'point_visibility: faces must be int32 (n_faces,3) on {dev}, got {tuple(faces.shape)} {faces.dtype} on {faces.device}')
+    if points_cam is not None and (points_cam.dim() != 3 or points_cam.shape[0] != B or points_cam.shape[2] != 3 or points_cam.dtype != torch.float32
+                                   or points_cam.device != dev):
+        raise ValueError(f'point_visibility: points_cam must be float32 ({B},n_points,3) on {dev}, got {tuple(points_cam.shape)} {points_cam.dtype}')
+    if (K is None) != (rect is None):
+        raise ValueError('point_visibility: K and rect go together, both or neither')
+    if status.dtype != torch.int32 or status.numel() != 1 or status.device != dev:
+        raise ValueError(f'point_visibility: status must be one int32 word on {dev}')
+    n_points = n_verts if points_cam is None else int(points_cam.shape[1])
+    if n_points > VIS_MAX_POINTS:
+        raise ValueError(f'point_visibility: {n_points} points per pose: at most {VIS_MAX_POINTS}')
+    if not (np.isfinite(float(margin_m)) and float(margin_m) >= 0.0) or not 1 <= int(min_crossings) <= 255:
+        raise ValueError(f'point_visibility: margin_m {margin_m} must be finite and >= 0, min_crossings {min_crossings} in 1 .. 255')
+    verts_cam, faces = verts_cam.contiguous(), faces.contiguous()
+    points_cam = None if points_cam is None else points_cam.contiguous()
+    if K is not None:
+        K, rect = _check_f32(K, (B, 3, 3), dev), _check_f32(rect, (B, 4), dev)
+    if out is None:
+        out = (torch.empty((B, n_points), dtype=torch.int32, device=dev) if want_count else None, torch.empty((B, n_points), dtype=torch.uint8, device=dev))
+    count, code = out
+    assert count is None or (count.shape == (B, n_points) and count.dtype == torch.int32 and count.is_contiguous() and count.device == dev)
+    assert code.shape == (B, n_points) and code.dtype == torch.uint8 and code.is_contiguous() and code.device == dev
+    if B * n_points == 0:                           # an empty tensor has no address to pass
+        return out
+    check(lib.jrr_point_visibility(ptr(verts_cam), B, n_verts, ptr(faces), int(faces.shape[0]), ptr(points_cam), n_points, ptr(K), ptr(rect),
+                                   float(margin_m), int(min_crossings), ptr(count), ptr(code), ptr(status), stream_ptr(dev)), 'point_visibility')
+    return out
+
+
+def visibility_accumulate(vert_code: torch.Tensor, joint_code: torch.Tensor, err_j: Optional[torch.Tensor], part: Optional[torch.Tensor],
+                          pose_status: Optional[torch.Tensor], group: Optional[torch.Tensor], n_groups: int, acc: torch.Tensor,
+                          per_vertex: Optional[torch.Tensor] = None) -> None:
+    """jrr_visibility_accumulate: ADD the poses -- vert_code (B,n_verts) and joint_code (B,17) uint8 as point_visibility wrote them,
+    err_j (B,17) float32 mm or None, pose_status (B,) int32 of place_translation or None -- to rows `group` (B, int32; None: group 0) of
+    the int64 table `acc` (n_groups * 154 + 2 words, include/jrr.h JRR_VIS_ACC_*), by part label `part` (n_verts, int32; None: all part
+    0), and the vertices with code 0 to `per_vertex` (n_verts, int64; optional)."""
+    lib = _lib.load()
+    assert vert_code.dim() == 2 and vert_code.dtype == torch.uint8 and vert_code.is_cuda and vert_code.is_contiguous()
+    B, n, dev = int(vert_code.shape[0]), int(vert_code.shape[1]), vert_code.device
+    assert joint_code.shape == (B, 17) and joint_code.dtype == torch.uint8 and joint_code.is_contiguous() and joint_code.device == dev
+    err_j = None if err_j is None else _check_f32(err_j, (B, 17), dev)
+    _check_acc(acc, n_groups, VIS_ACC_ROW, VIS_ACC_TRAILER, dev)
+    assert part is None or (part.shape == (n,) and part.dtype == torch.int32 and part.is_contiguous() and part.device == dev)
+    if pose_status is not None:
+        _check_ids(pose_status, B, dev)
+    if group is not None:
+        _check_ids(group, B, dev)
+    assert per_vertex is None or (per_vertex.shape == (n,) and per_vertex.dtype == torch.int64 and per_vertex.is_contiguous() and per_vertex.device == dev)
+    if B == 0:
+        return
+    check(lib.jrr_visibility_accumulate(ptr(vert_code), ptr(joint_code), ptr(err_j), ptr(part), ptr(pose_status), ptr(group), B, n, int(n_groups),
+                                        ptr(acc), ptr(per_vertex), stream_ptr(dev)), 'visibility_accumulate')
+
+
 def project_joints(joints: torch.Tensor, cam: torch.Tensor) -> torch.Tensor:
     """return_2d_joints core (scripts/renderer.py:35-49): (B,17,3), (B,3) -> screen xy (B,17,2)"""
     lib = _lib.load()

@@ -781,3 +781,205 @@ def place_command(log=print) -> Optional[dict]:
     directory = (os.path.dirname(args.place_refined) or '.') if str(args.place_refined).endswith('.npz') else args.place_refined
     log(place_report.summary_line(out['report']) + f'; {os.path.join(directory, PLACE_NAME)}')
     return out
+
+
+# ---- what that camera sees (`--visible_refined`) ------------------------------------------------------------------------------
+VISIBLE_NAME = 'refined_visible.npz'
+VISIBLE_CODES = 'vertex_visibility.npy'
+VISIBLE_PER_VERTEX = 'visible_per_vertex.npy'
+VISIBLE_NO_POSE = 255         # vertex_visibility.npy / joint_code: a row without a refined or placed pose
+VISIBLE_STATUS_BITS = {1: 'bit 0: the pose is left out of the report (not placed, a vertex or joint behind the camera, a non-finite error)'}
+
+
+class _MeshOf(_JointsOf):
+    """_JointsOf with the 6890 vertices beside the 17 joints: (joints (len(rows),17,3), verts (len(rows),6890,3)) on the device, neither
+    translated; and the faces and skinning weights of the body it poses"""
+
+    def __init__(self, device):
+        super().__init__(device)
+        self.faces = np.ascontiguousarray(np.asarray(self.smpl.model_np['faces']).astype(np.int32))
+        self.lbs_weights = np.asarray(self.smpl.model_np['lbs_weights'])
+
+    def __call__(self, arrays, rows):
+        from . import engine as _engine
+        B = int(len(rows))
+        if B not in self.engines:
+            self.engines[B] = _engine.RefineEngine(self.smpl.device_model, B, flags=_engine.FLAG_KEEP_VERTS)
+            self.engines[B].set_j_regressor(self.J, self.mask)
+        x6d = torch.from_numpy(arrays['pose6d'][rows]).to(self.device).float().contiguous()
+        betas = torch.from_numpy(arrays['shape'][rows]).to(self.device).float().contiguous()
+        return self.engines[B].find_joints_forward(betas, x6d=x6d, return_verts=True)
+
+
+def visible_window(kind: str, n: int, frame=(1000, 1000), bboxes=None) -> torch.Tensor:
+    """the window (n,4) float32 = [x0,y0,x1,y1] in full-frame pixels: the frame [0,0,W,H], or the square find_crop cuts from the
+    sample's bounding box (data.crop_params: corner (min_x, min_y), side 1000 scale)"""
+    from . import data as jdata
+    if kind == 'frame':
+        return torch.tensor([0.0, 0.0, float(frame[0]), float(frame[1])]).repeat(n, 1)
+    if kind != 'crop':
+        raise ValueError(f'visible: window {kind!r}: frame or crop')
+    if bboxes is None or tuple(bboxes.shape) != (n, 4):
+        raise ValueError(f'visible: the crop window needs bboxes ({n}, 4), got {None if bboxes is None else tuple(bboxes.shape)}')
+    min_x, min_y, scale = jdata.crop_params(torch.as_tensor(bboxes).float())
+    return torch.stack([min_x, min_y, min_x + 1000 * scale, min_y + 1000 * scale], 1).float()
+
+
+def visible(directory_or_npz: str, intrinsics, gt_j3d_mm, paths, mesh_of, faces, part=None, n_parts: int = 0, margin_mm: float = 5.0,
+            window: str = 'frame', frame=(1000, 1000), bboxes=None, batch_size: int = 256, group_kind: str = 'action', device=None) -> Dict[str, np.ndarray]:
+    """`--visible_refined PATH`: what the real camera sees of every placed row of DIR/refined_placed.npz (PATH: that file, another `.npz`
+    of the directory with `trans`, or the directory).  `mesh_of(arrays, rows)` gives (joints (len(rows),17,3), verts (len(rows),6890,3))
+    of table rows on the device (_MeshOf); faces (n_faces,3) int32 and part (6890,) labels (or None) belong to that body.  Per chunk
+    of `batch_size` refined rows: + (float)trans, jrr_point_visibility for the vertices (a face that names the vertex skipped, one
+    crossing hides) and for the joints (two crossings hide: the first is the joint's own skin) against the window of `window` under the
+    real intrinsics (N,3,3), jrr_evaluate_joints against the pelvis-centred gt_j3d_mm (N,17,3), jrr_visibility_accumulate into the
+    table of visibility_report by the groups of `paths` (None: one group); nothing is read back inside the loop.  Writes
+    DIR/vertex_visibility.npy -- uint8 (N,6890) codes (bit 0 hidden, bit 1 outside, bit 2 behind the camera), 255 on rows without a
+    refined or placed pose, chunk by chunk through a memory map --, DIR/refined_visible.npz -- every array of the input unchanged +
+    joint_code (N,17) uint8 (255 there), joint_crossings (N,17) int32 and n_vertices_seen (N,) int32 (-1 there), visible_status (N,)
+    int32 (-1 there; bit 0: left out of the report) --, DIR/visible.json, DIR/visible.md, DIR/visible_per_vertex.npy (6890 int64: in
+    how many counted poses the vertex is seen) and the entry `visible` of DIR/meta.json; the input file is not rewritten."""
+    from . import engine as _engine, eval_report, utils, vertex_report, visibility_report
+    margin_mm = float(margin_mm)
+    if not (np.isfinite(margin_mm) and margin_mm >= 0.0):
+        raise ValueError(f'visible: margin_mm {margin_mm}: finite and not negative')
+    is_file = str(directory_or_npz).endswith('.npz')
+    directory = (os.path.dirname(directory_or_npz) or '.') if is_file else directory_or_npz
+    source = directory_or_npz if is_file else os.path.join(directory, PLACE_NAME)
+    if not os.path.exists(source):
+        raise FileNotFoundError(f'visible: {source} is missing: --place_refined writes it')
+    raw = load_path(source)
+    meta = raw.pop('meta')
+    if 'trans' not in raw or 'place_status' not in raw:
+        raise ValueError(f'visible: {source} holds no trans / place_status: run --place_refined on the table first')
+    N = raw['has_refined'].shape[0]
+    as_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    intrinsics, gt_j3d_mm = as_t(intrinsics).float(), as_t(gt_j3d_mm).float()
+    for name, t, shape in (('intrinsics', intrinsics, (N, 3, 3)), ('gt_j3d', gt_j3d_mm, (N, 17, 3))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f'visible: {name} should be {shape} for a table of {N} samples, is {tuple(t.shape)}')
+    rect_all = visible_window(window, N, frame, None if bboxes is None else as_t(bboxes))
+    names, gid = eval_report.assign_groups(paths, group_kind, n=N)
+    if gid.shape[0] != N:
+        raise ValueError(f'visible: {gid.shape[0]} paths for a table of {N} rows')
+    G = len(names)
+    device = torch.device(args.device if device is None else device)
+    faces_d = as_t(np.ascontiguousarray(np.asarray(faces).astype(np.int32))).to(device)
+    part_np = None if part is None else np.ascontiguousarray(np.asarray(part).astype(np.int32))
+    part_d = None if part_np is None else torch.from_numpy(part_np).to(device)
+    rows = np.nonzero(raw['has_refined'])[0]
+    M, bs = int(rows.size), max(1, int(batch_size))
+    trans_all, pstatus_all = torch.from_numpy(raw['trans'][rows]), torch.from_numpy(raw['place_status'][rows].astype(np.int32))
+    n_verts, vcode = None, None
+    jcount = torch.zeros((M, 17), dtype=torch.int32, device=device)
+    jcode = torch.full((M, 17), VISIBLE_NO_POSE, dtype=torch.uint8, device=device)
+    n_seen = torch.full((M,), -1, dtype=torch.int32, device=device)
+    left_out = torch.zeros((M,), dtype=torch.int32, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    acc = torch.zeros(G * visibility_report.ROW + visibility_report.TRAILER, dtype=torch.int64, device=device)
+    per_vertex = None
+    with torch.no_grad():
+        for a in range(0, M, bs):
+            idx = torch.from_numpy(rows[a:a + bs])
+            s = slice(a, a + int(idx.shape[0]))
+            joints, verts = mesh_of(raw, rows[a:a + bs])
+            if vcode is None:                                                # the sizes of the body, from the first chunk
+                n_verts = int(verts.shape[1])
+                vcode = torch.full((M, n_verts), VISIBLE_NO_POSE, dtype=torch.uint8, device=device)
+                per_vertex = torch.zeros(n_verts, dtype=torch.int64, device=device)
+            t = trans_all[s].to(device).float()[:, None]
+            verts_cam, joints_cam = (verts.float() + t).contiguous(), (joints.float() + t).contiguous()
+            K, rect = intrinsics[idx].to(device).contiguous(), rect_all[idx].to(device).contiguous()
+            _engine.point_visibility(verts_cam, faces_d, None, K, rect, margin_mm / 1000.0, 1, status, out=(None, vcode[s]))
+            _engine.point_visibility(verts_cam, faces_d, joints_cam, K, rect, margin_mm / 1000.0, 2, status, out=(jcount[s], jcode[s]))
+            gt = utils.move_pelvis(gt_j3d_mm[idx].to(device).float())
+            err_mm = (_engine.evaluate_joints(joints.float().contiguous(), gt.contiguous())[0] * 1000).contiguous()
+            pst = pstatus_all[s].to(device)
+            _engine.visibility_accumulate(vcode[s], jcode[s], err_mm, part_d, pst, torch.from_numpy(gid[rows[a:a + bs]]).to(device), G, acc, per_vertex)
+            n_seen[s] = (vcode[s] == 0).sum(1).int()
+            left_out[s] = (((pst & 7) != 0) | ((vcode[s] & 0xFC) != 0).any(1) | ((jcode[s] & 0xFC) != 0).any(1) | ~(err_mm < 1.0e5).all(1)).int()
+    if vcode is None:                                                        # a table without a refined row
+        n_verts = 6890
+        vcode = torch.zeros((0, n_verts), dtype=torch.uint8, device=device)
+        per_vertex = torch.zeros(n_verts, dtype=torch.int64, device=device)
+    table = visibility_report.derive(acc.cpu().numpy(), names)               # the table ...
+    h_jcode, h_jcount, h_seen, h_left = jcode.cpu().numpy(), jcount.cpu().numpy(), n_seen.cpu().numpy(), left_out.cpu().numpy()
+    placed = (raw['place_status'][rows] >= 0) & ((raw['place_status'][rows] & 7) == 0) & np.isfinite(raw['trans'][rows]).all(1)
+    codes = np.lib.format.open_memmap(os.path.join(directory, VISIBLE_CODES), mode='w+', dtype=np.uint8, shape=(N, n_verts))
+    codes[:] = VISIBLE_NO_POSE
+    for a in range(0, M, bs):                                                # ... and the codes, chunk by chunk
+        keep = placed[a:a + bs]
+        codes[rows[a:a + bs][keep]] = vcode[a:a + bs].cpu().numpy()[keep]
+    codes.flush()
+    del codes
+    np.save(os.path.join(directory, VISIBLE_PER_VERTEX), per_vertex.cpu().numpy())
+    out = dict(raw)
+    out['joint_code'] = np.full((N, 17), VISIBLE_NO_POSE, np.uint8)
+    out['joint_crossings'] = np.full((N, 17), -1, np.int32)
+    out['n_vertices_seen'] = np.full(N, -1, np.int32)
+    out['visible_status'] = np.full(N, -1, np.int32)
+    pr = rows[placed]
+    out['joint_code'][pr], out['joint_crossings'][pr], out['n_vertices_seen'][pr] = h_jcode[placed], h_jcount[placed], h_seen[placed]
+    out['visible_status'][rows] = h_left
+    np.savez(os.path.join(directory, VISIBLE_NAME), **out)
+    parts = None
+    if part_np is not None:
+        n_parts = int(n_parts) if n_parts else int(part_np.max()) + 1
+        sizes = np.bincount(np.where((part_np >= 0) & (part_np < visibility_report.PARTS), part_np, visibility_report.PARTS - 1),
+                            minlength=visibility_report.PARTS)
+        parts = list(zip(vertex_report.part_names(min(n_parts, visibility_report.PARTS)), (int(x) for x in sizes)))
+    face_status = int(status.item())
+    doc = visibility_report.write(directory, table, names, group_kind, margin_mm, window, frame, getattr(mesh_of, 'name', None), parts, face_status)
+    a_ = table[visibility_report.ALL]
+    entry = {'source': os.path.basename(source), 'rows': M, 'placed': int(placed.sum()), 'counted': a_['n'], 'left_out': a_['n_bad'],
+             'margin_mm': margin_mm, 'window': window, 'frame': [int(x) for x in frame], 'j_regressor': getattr(mesh_of, 'name', None),
+             'vertices_seen': a_['vertices_seen'], 'vertices_occluded': a_['vertices_occluded'], 'vertices_outside': a_['vertices_outside'],
+             'err_seen_mm': a_['err_seen_mm'], 'err_occluded_mm': a_['err_occluded_mm'], 'face_index_status': face_status}
+    with open(os.path.join(directory, 'meta.json'), 'w') as f:
+        json.dump(dict(meta, visible=entry), f, indent=1, sort_keys=True, default=str)
+    out['meta'] = dict(meta, visible=entry)
+    out['report'] = doc
+    return out
+
+
+def visible_command(log=print) -> Optional[dict]:
+    """`python main.py --visible_refined PATH --data_root ROOT [--visible_margin_mm 5.0] [--visible_window frame|crop] [--visible_frame W H]
+    [--eval_j_regressor CKPT]`: refined.visible on the split the table was written from -- its intrinsics, bounding boxes and gt_j3d, the
+    groups of --eval_groups from its images.pkl.  One process: under torchrun rank 0 works and the other ranks return.  Prints one line."""
+    from . import data as jdata, vertex_report, visibility_report
+    if jdist.env_rank_world()[0] != 0:                      # the command joins no process group: the launcher's rank decides
+        return None
+    if not args.data_root:
+        raise ValueError('--visible_refined needs --data_root (the intrinsics, the bounding boxes and the 3-D joints of the split the table was written from)')
+    margin = float(args.visible_margin_mm)
+    if not (np.isfinite(margin) and margin >= 0.0):
+        raise ValueError(f'--visible_margin_mm {args.visible_margin_mm}: finite and not negative')
+    if args.visible_window not in visibility_report.WINDOWS:
+        raise ValueError(f'--visible_window {args.visible_window}: frame or crop')
+    frame = [int(x) for x in args.visible_frame]
+    if len(frame) != 2 or min(frame) < 1:
+        raise ValueError(f'--visible_frame {args.visible_frame}: two positive numbers, W H')
+    is_file = str(args.visible_refined).endswith('.npz')
+    directory = (os.path.dirname(args.visible_refined) or '.') if is_file else args.visible_refined
+    source = args.visible_refined if is_file else os.path.join(directory, PLACE_NAME)
+    if not os.path.exists(source):
+        raise FileNotFoundError(f'--visible_refined: {source} is missing: --place_refined writes it')
+    head = load_path(source)
+    if 'trans' not in head:
+        raise ValueError(f'--visible_refined: {source} holds no trans: run --place_refined on the table first')
+    location = jdata.split_location('validation', args.data_root)
+    paths = jdata.split_image_paths(location)
+    if paths is None:
+        raise FileNotFoundError(f'--visible_refined: {os.path.join(location, "images.pkl")} is missing: the frame paths say which group a sample belongs to')
+    ds = jdata.data_set('validation', root=args.data_root)
+    n_table = head['has_refined'].shape[0]
+    if not (len(paths) == len(ds) == n_table):
+        raise ValueError(f'--visible_refined: the table holds {n_table} samples, the split {len(ds)} with {len(paths)} frame paths')
+    device = torch.device(args.device)
+    torch.cuda.set_device(device)
+    mesh_of = _MeshOf(device)
+    out = visible(source, ds.intrinsics, ds.gt_j3d, paths, mesh_of, mesh_of.faces, part=vertex_report.part_labels(mesh_of.lbs_weights),
+                  n_parts=mesh_of.lbs_weights.shape[1], margin_mm=margin, window=args.visible_window, frame=frame, bboxes=ds.bboxes,
+                  batch_size=args.batch_size, group_kind=args.eval_groups, device=device)
+    log(visibility_report.summary_line(out['report']) + f'; {os.path.join(directory, VISIBLE_NAME)}')
+    return out

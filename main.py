@@ -8,7 +8,8 @@ networks' vertices is `--eval_vertices DIR --eval_report OUT` (eval_report.evalu
 `--regressor_report DIR` (regressor_report.py) adds to either evaluation what the retrained regressor did to each joint, with pictures.
 `--smooth_refined DIR` (refined.smooth_command) filters a `--save_refined` table along time and exits as well;
 `--fuse_refined DIR` (refined.fuse_command) fuses its camera views of each frame and exits;
-`--place_refined PATH` (refined.place_command) gives every refined pose its translation in the real camera and exits.
+`--place_refined PATH` (refined.place_command) gives every refined pose its translation in the real camera and exits;
+`--visible_refined PATH` (refined.visible_command) says which vertices and joints of the placed poses that camera sees and exits.
 `--fit_regressor OUT --fit_from PATH` (regressor_fit.py) fits the regressor on a table of fixed meshes and exits; with `--fit_solve`
 (regressor_solve.py) it solves that fit exactly from the table's second moments instead of taking Adam epochs.
 `--eval_accel` (accel_report.py) adds the acceleration error along each video sequence to the evaluations and to those two commands.
@@ -62,6 +63,9 @@ if __name__ == '__main__':
         sys.exit(0)
     if args.place_refined:                                                   # ... into the real camera of each sample; no training
         importlib.import_module(PKG + '.refined').place_command()
+        sys.exit(0)
+    if args.visible_refined:                                                 # ... and what that camera sees of it; no training
+        importlib.import_module(PKG + '.refined').visible_command()
         sys.exit(0)
     res = optimize.optimize_pose_refiner()                                   # main.py:23
     if args.save_refined and int(os.environ.get('RANK', '0')) == 0:
